@@ -24,7 +24,16 @@ no collective during EM, ONE all-gather of the per-restart result records at the
                           `--restarts` / `--total-restarts` split evenly between them
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`
-(dominant kernel, HIP-event timed on the batch stream) and `cpu_baseline`.
+(dominant kernel, HIP-event timed on the batch stream during the timed steps).
+
+A plain run sets up, warms up, times the steps and prints the line.  Everything
+else moves behind `--full`: the CPU baseline (`cpu_baseline`), the additional
+configurations at N = 1 (`fit_from_init`, `roofline_one_group`, `states_355`,
+`strong_scaling_proxy`, `unequal_chains`) and, at N > 1, the fixed 64-restart
+job (`configs3_strong_64`) and the gather of the result records (`final_gather`).
+
+`--dump-outputs DIR` writes what the timed steps computed in the last one, as
+float64 .npy files under DIR (see dump_outputs).
 """
 import argparse
 import json
@@ -61,8 +70,11 @@ def alg_flops_per_cell(name, S):
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=6)
+    ap.add_argument('--steps', type=int, default=6, help='timed EM iterations (at least 1)')
     ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--full', action='store_true', help='also the CPU baseline and the additional measurements (see the module docstring); '
+                                                        'a plain run only times the headline workload')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write what the last one computed as DIR/<name>.npy (float64)')
     ap.add_argument('--segments', type=int, default=50000)
     ap.add_argument('--clones', type=int, default=3)
     ap.add_argument('--max-cn', type=int, default=8)
@@ -89,6 +101,8 @@ def parse(argv=None):
     ap.add_argument('--cpu-leg', action='store_true', help=argparse.SUPPRESS)       # internal: the CPU baseline child process
     ap.add_argument('--sub-run', default=None, help=argparse.SUPPRESS)              # internal: one additional measurement in a process of its own (restarts,groups,max_cn,nsteps,warm,unequal)
     args = ap.parse_args(argv)
+    if args.steps < 1 and not (args.cpu_leg or args.sub_run):
+        ap.error('--steps must be at least 1')
     # (--groups given on the command line: honoured for several datasets too; otherwise DatasetGroups keeps two groups on the device at a time)
     args.groups_given = any(a == '--groups' or a.startswith('--groups=') for a in (argv if argv is not None else sys.argv[1:]))
     return args
@@ -270,6 +284,33 @@ def build_datasets(args):
     return out
 
 
+DUMP_BYTES = 60 * 2 ** 20       # --dump-outputs stays below 64 MB: the per-segment arrays are a sample of the segments
+
+
+def dump_outputs(rs, elbo, out_dir):
+    """--dump-outputs: what the last timed step computed for every restart of this rank (rank 0 only at N > 1), read back after
+    the timed region, as float64 arrays in out_dir: elbo (R,), h (R, M), param_<name> (R,) per likelihood parameter,
+    p_breakpoint (R, K, B) and, on a fixed seeded sample of n segments (the same rows for every restart, as many as the size
+    bound allows), posterior_marginals (R, n, S) and p_outlier_total / p_outlier_allele / p_allele_swap (R, n, 2)."""
+    os.makedirs(out_dir, exist_ok=True)
+    models = rs.models
+    R = len(models)
+    N, S = int(models[0].model.num_segments), int(models[0].model.num_cn_states)
+    out = {'elbo': np.asarray(elbo, dtype=np.float64).reshape(R),
+           'h': np.array([np.asarray(m.model.h, dtype=np.float64) for m in models])}
+    params = [m.get_likelihood_param_values() for m in models]
+    for name in models[0].likelihood_params:
+        out['param_' + name] = np.array([float(p[name]) for p in params])
+    out['p_breakpoint'] = np.array([np.asarray(m.model.p_breakpoint, dtype=np.float64) for m in models])
+    per_row = R * (S + 3 * 2) * 8
+    n = int(max(1, min(N, (DUMP_BYTES - sum(v.nbytes for v in out.values())) // per_row)))
+    rows = np.sort(np.random.RandomState(20240611).choice(N, n, replace=False))
+    for name in ('posterior_marginals', 'p_outlier_total', 'p_outlier_allele', 'p_allele_swap'):
+        out[name] = np.array([np.asarray(getattr(m.model, name), dtype=np.float64)[rows] for m in models])
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), v)
+
+
 def main(argv=None, kernel_module=None, dist_backend='nccl', script=None):
     """The benchmark.  The keyword arguments exist for tests/bench_rehearsal.py ONLY (a world of gloo ranks on a
     machine without GPUs rehearsing the launch / shard / gather logic over a stand-in kernel module): this program
@@ -292,7 +333,7 @@ def main(argv=None, kernel_module=None, dist_backend='nccl', script=None):
 
     # the CPU leg runs first, in a child process, before this process initialises the GPU
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
     import torch
@@ -391,6 +432,8 @@ def main(argv=None, kernel_module=None, dist_backend='nccl', script=None):
         for b_ in rs.batches:
             b_.profile_enable(0)
         prof = rs.profile()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(rs, elbo, args.dump_outputs)
     observed_world = 1
     gathered = None
     if world > 1:
@@ -402,6 +445,7 @@ def main(argv=None, kernel_module=None, dist_backend='nccl', script=None):
         cnt = torch.tensor([float(R)], dtype=torch.float64, device=cdev)
         dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
         total_fitted = int(round(float(cnt.item())))
+    if world > 1 and args.full:
         # final gather of the per-restart results (outside the timed region: it happens once per fit): the same
         # function and the same two records (float64 + int8) per restart as fit_restarts_distributed.  In the
         # weak / strong single-dataset modes unit j of rank g is restart g + j * world, i.e. shard_indices' order.
@@ -419,14 +463,14 @@ def main(argv=None, kernel_module=None, dist_backend='nccl', script=None):
             gathered['seconds'] += tm['seconds']; gathered['bytes_per_rank'] += tm['bytes_per_rank']
             gathered['float_record_bytes'] = tm['float_record_bytes']; gathered['int8_record_bytes'] = tm['int8_record_bytes']
         gathered['note'] = 'per dataset two all_gathers (float64 record + int8 record per restart) through restarts.gather_result_records'
-    else:
+    if world == 1:
         total_fitted = R
 
     # N > 1: the weak-scaling line above keeps BASELINE configs[2]'s 16 restarts on every GPU, so that the driver's N = 1, 2, 4, 8
     # values are the same per-GPU workload; the north-star's multi-GPU target is configs[3], a FIXED 64-restart job cut over the
     # GPUs -- measured here as well, in the same process group, and reported beside it (`configs3_strong_64`)
     strong64 = None
-    if world > 1 and not strong and ND == 1 and args.strong_total >= world:
+    if args.full and world > 1 and not strong and ND == 1 and args.strong_total >= world:
         try:
             strong64 = strong_64_over_ranks(args, rs, device, rank, world, dist, torch, on_gpu, kernel_module, host_kw)
         except Exception as err:
@@ -488,7 +532,7 @@ def main(argv=None, kernel_module=None, dist_backend='nccl', script=None):
             line['final_gather'] = gathered
         if strong64 is not None:
             line['configs3_strong_64'] = strong64
-        single = world == 1 and on_gpu and ND == 1 and not strong and not args.no_mstep
+        single = args.full and world == 1 and on_gpu and ND == 1 and not strong and not args.no_mstep
         if single and not args.no_fit_from_init:
             try:
                 line['fit_from_init'] = fit_from_init(args, rs, device)

@@ -57,7 +57,7 @@ def _bench(extra, env_extra=None):
 
 def test_bench_gpus_2_launches_two_ranks():
     """`python bench.py --gpus 2` outside torchrun starts the two ranks itself (--gpus was ignored)."""
-    line = _bench(['--gpus', '2', '--restarts', '2', '--strong-total', '5'])
+    line = _bench(['--gpus', '2', '--restarts', '2', '--strong-total', '5', '--full'])
     assert line['n_gpus'] == 2 and line['config']['world_size_observed'] == 2
     # ... and the fixed job of BASELINE configs[3] beside the weak-scaling line (5 restarts here: 3 + 2)
     s64 = line['configs3_strong_64']
@@ -72,12 +72,38 @@ def test_bench_gpus_2_launches_two_ranks():
 
 def test_bench_strong_scaling_and_two_datasets():
     """BASELINE configs[3] / configs[4] shapes: a fixed total sharded over the ranks, two datasets side by side."""
-    line = _bench(['--gpus', '2', '--total-restarts', '6', '--datasets', '2'])
+    line = _bench(['--gpus', '2', '--total-restarts', '6', '--datasets', '2', '--full'])
     assert line['n_gpus'] == 2 and line['scaling'] == 'strong'
     assert line['config']['restarts_total'] == 6 and line['config']['datasets'] == 2 and line['final_gather']['records'] == 6
     assert 'configs[4]' in line['config']['workload']
     one = _bench(['--gpus', '1', '--total-restarts', '6'])
     assert one['n_gpus'] == 1 and one['scaling'] == 'strong' and 'configs[3]' in one['config']['workload']
+
+
+def test_bench_plain_run_times_the_headline_only():
+    """Without --full the line carries the headline and nothing that needs work of its own (the fixed job, the gather)."""
+    line = _bench(['--gpus', '2', '--restarts', '2', '--strong-total', '5'])
+    assert line['n_gpus'] == 2 and line['config']['restarts_total'] == 4 and line['value'] > 0
+    assert line['steps'] == 1 and line['ms_per_step'] > 0
+    assert 'configs3_strong_64' not in line and 'final_gather' not in line and 'cpu_baseline' not in line
+
+
+def test_bench_dump_outputs_are_float_and_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: the last timed step's arrays as float64 .npy, identical for identical arguments."""
+    dirs = [tmp_path / 'a', tmp_path / 'b']
+    for d in dirs:
+        line = _bench(['--gpus', '1', '--restarts', '3', '--steps', '2', '--dump-outputs', str(d)])
+        assert line['steps'] == 2
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1]))
+    assert {'elbo.npy', 'h.npy', 'p_breakpoint.npy', 'posterior_marginals.npy'} <= set(names)
+    total = 0
+    for name in names:
+        a, b = np.load(dirs[0] / name), np.load(dirs[1] / name)
+        assert a.dtype == np.float64 and a.shape[0] == 3 and np.array_equal(a, b, equal_nan=True), name
+        total += a.nbytes
+    assert total <= 64 * 2 ** 20
+    assert np.isfinite(np.load(dirs[0] / 'elbo.npy')).all()
 
 
 def test_bench_refuses_a_world_size_that_contradicts_gpus():

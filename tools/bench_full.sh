@@ -1,10 +1,10 @@
 #!/bin/bash
-# the driver's default bench invocation, timed, with a digest of the extra objects of its JSON line
+# the full bench (--full), timed, with a digest of the extra objects of its JSON line
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out; mkdir -p $OUT
 cd /tmp
 t0=$(date +%s.%N)
-python3 $ROOT/bench.py "$@" > $OUT/bench_full.json 2> $OUT/bench_full.err
+python3 $ROOT/bench.py --full "$@" > $OUT/bench_full.json 2> $OUT/bench_full.err
 t1=$(date +%s.%N)
 echo "wall $(echo "$t1 - $t0" | bc) s"
 python3 - <<PY

@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/profiles_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 F="--steps 20 --warmup 5"
-python3 $ROOT/bench.py $F > $OUT/bench_line.json 2> $OUT/bench.err
+python3 $ROOT/bench.py $F --full > $OUT/bench_line.json 2> $OUT/bench.err
 echo "bench done: $(cut -c1-120 $OUT/bench_line.json)"
 rocprofv3 --kernel-trace --stats -d $OUT/prof_bench -o b --output-format csv -- python3 $ROOT/bench.py $F --no-cpu-baseline --no-extra-states --no-fit-from-init > $OUT/bench_line_under_rocprof.json 2> $OUT/prof_bench.err
 python3 $ROOT/tools/timeline.py $(find $OUT/prof_bench -name "b_kernel_trace.csv" | head -1) "k_fbm<42" > $OUT/timeline.txt 2>&1

@@ -2,7 +2,7 @@
 # A/B of a library option on the headline bench and its 355-state line: bash tools/opt_ab.sh "two_streams=0" ...
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd /tmp
-F="--steps 20 --warmup 5 --no-cpu-baseline --no-fit-from-init"
+F="--steps 20 --warmup 5 --full --no-cpu-baseline --no-fit-from-init"
 for o in "" "$@"; do
   opts=""; for kv in $o; do opts="$opts --option $kv"; done
   python3 $ROOT/bench.py $F $opts 2>/dev/null | python3 -c "

@@ -335,6 +335,15 @@ int rmx_infer_cn(rmx_batch *b, int32_t r, int64_t *cn_out, double *logprob_out);
  * [nr][N][M][2], logprob_out [nr] or NULL (the per-restart decode of analysis/pipeline.py:196-206) */
 int rmx_infer_cn_batch(rmx_batch *b, int32_t r0, int32_t nr, int64_t *cn_out, double *logprob_out);
 
+/* -- posterior sampling (no reference counterpart) -------------------------- */
+/* num_samples whole copy-number paths per restart r0 .. r0+nr-1 from the structured posterior q(c) of the last
+ * update_p_cn: the chain HMM of its framelogprob / log_transmat snapshot, the one infer_cn decodes and whose marginals
+ * are posterior_marginals.  states_out int16 [nr][num_samples][N]: indices into the segment's state table.  seeds
+ * [nr]: the stream of restart r0+i; a (seed, sample index) pair gives the same path in any call.  The model is not
+ * modified.  RMX_EVALUE (flagged restarts) before a restart's first update_p_cn; RMX_EASSERT (flagged) when a step
+ * has no finite positive weight. */
+int rmx_sample_cn(rmx_batch *b, int32_t r0, int32_t nr, int32_t num_samples, const uint64_t *seeds, int16_t *states_out);
+
 /* -- module-level functions on caller-supplied dense inputs ----------------- */
 /* sum_product (:1213-1246): f [N][S], T [N-1][S][S] -> alphas, betas [N][S] */
 int rmx_sum_product(const double *f, const double *T, double *alphas, double *betas,

@@ -6,9 +6,9 @@ import pickle
 
 import numpy as np
 
-from .. import defaults
+from .. import defaults, sampling
 from ..cn_model import BreakpointModel
-from ..restarts import RestartSet, collect_fit_results, fit_restarts_distributed, select_optimal  # noqa: F401
+from ..restarts import RestartSet, add_cn_sample_summaries, collect_fit_results, fit_restarts_distributed, select_optimal  # noqa: F401
 
 
 def _model_kwargs(experiment, config):
@@ -29,8 +29,9 @@ def _model_kwargs(experiment, config):
     )
 
 
-def fit(experiment, init_params, config, device=0, quiet=False):
-    """analysis/pipeline.py:127-228 (one restart)."""
+def fit(experiment, init_params, config, device=0, quiet=False, init_id=0):
+    """analysis/pipeline.py:127-228 (one restart).  init_id: the restart's id, which selects its posterior-sample stream
+    when config num_cn_samples > 0."""
     h_init = np.array([
         init_params['h_normal'],
         init_params['h_tumour'] * init_params['mix_frac'],
@@ -56,15 +57,20 @@ def fit(experiment, init_params, config, device=0, quiet=False):
     model.num_em_iter = defaults.get_param(config, 'num_em_iter')
     model.num_update_iter = defaults.get_param(config, 'num_update_iter')
     model.fit(h_init)
-    return collect_fit_results(model, experiment, init_params)
+    res = collect_fit_results(model, experiment, init_params)
+    num_samples = defaults.get_param(config, 'num_cn_samples')
+    if num_samples > 0:
+        seed = sampling.restart_seed(defaults.get_param(config, 'cn_sample_seed'), init_id)
+        sampling.add_sample_summary(res, model.sample_cn(num_samples, seed), experiment.l)
+    return res
 
 
-def fit_task(results_filename, experiment_filename, init_params, config, device=0, quiet=True):
+def fit_task(results_filename, experiment_filename, init_params, config, device=0, quiet=True, init_id=0):
     """analysis/pipeline.py:112-124 with the reference's arguments: one restart, experiment pickle in, pickled fit results out (the
     file `collate` reads).  The reference runs one such job per init_id; `fit_restarts_task` below is the batched form."""
     with open(experiment_filename, 'rb') as f:
         experiment = pickle.load(f)
-    fit_results = fit(experiment, init_params, config, device=device, quiet=quiet)
+    fit_results = fit(experiment, init_params, config, device=device, quiet=quiet, init_id=init_id)
     with open(results_filename, 'wb') as f:
         pickle.dump(fit_results, f)
 
@@ -95,7 +101,11 @@ def fit_restarts(experiment, init_params_by_id, config, device=0, quiet=True, se
         rs = RestartSet(experiment, params, max_cn, num_clones=3, device=device, quiet=quiet, seeds=seeds,
                         **_model_kwargs(experiment, config))
     rs.fit(defaults.get_param(config, 'num_em_iter'), defaults.get_param(config, 'num_update_iter'))
-    out = dict(zip(ids, rs.results()))
+    results = rs.results()
+    num_samples = defaults.get_param(config, 'num_cn_samples')
+    if num_samples > 0:
+        add_cn_sample_summaries(rs, results, experiment, num_samples, defaults.get_param(config, 'cn_sample_seed'), ids)
+    out = dict(zip(ids, results))
     rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     return out
 
@@ -231,6 +241,9 @@ def store_fit_results(store, experiment, fit_results, key_prefix):
     store[key_prefix + '/cn'] = cn_table
     store[key_prefix + '/mix'] = pd.Series(h / h.sum(), index=range(len(h)))
     store[key_prefix + '/brk_cn'] = brk_cn_table
+    if 'cn_sample_agreement' in fit_results:      # (config num_cn_samples > 0)
+        store[key_prefix + '/cn_sample_agreement'] = pd.DataFrame(np.asarray(fit_results['cn_sample_agreement']))
+        store[key_prefix + '/cn_state_agreement'] = pd.Series(np.asarray(fit_results['cn_state_agreement']))
 
 
 def store_optimal_solution(stats, store, config):

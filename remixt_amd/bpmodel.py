@@ -522,6 +522,23 @@ class RemixtBatch(object):
         self._ck(self._lib.rmx_infer_cn_batch(self._handle, int(r0), int(nr), cn.ctypes.data_as(_ip), lp.ctypes.data_as(_dp)))
         return cn, lp
 
+    def sample_states(self, r0, nr, num_samples, seeds):
+        """num_samples posterior paths of restarts r0 .. r0+nr-1 (forward-filtering backward-sampling over the
+        structured posterior of their last update_p_cn): int16 (nr, num_samples, N) indices into each segment's state
+        table.  seeds: nr 64-bit seeds, one stream per restart."""
+        seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+        if len(seeds) != nr:
+            raise ValueError('one seed per restart')
+        out = np.zeros((max(int(nr), 0), max(int(num_samples), 0), self.num_segments), dtype=np.int16)
+        self._ck(self._lib.rmx_sample_cn(self._handle, int(r0), int(nr), int(num_samples), seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                         out.ctypes.data_as(C.POINTER(C.c_int16))))
+        return out
+
+    def states_to_cn(self, states):
+        """state indices (..., N) -> copy numbers int64 (..., N, M, 2) through the segments' class tables."""
+        states = np.asarray(states)
+        return self.cn_classes[self.seg_class, states]
+
     # -- measurement ------------------------------------------------------------
     def timer_start(self):
         self._ck(self._lib.rmx_timer_start(self._handle))
@@ -734,6 +751,11 @@ class RemixtModel(object):
     def infer_cn(self, cn):
         out, _ = self._batch.infer_cn(self._r)
         cn[...] = out
+
+    def sample_cn(self, num_samples, seed):
+        """num_samples posterior copy-number paths (K, N, M, 2) int64 of this model (seed: 64-bit)."""
+        states = self._batch.sample_states(self._r, 1, num_samples, [seed])[0]
+        return self._batch.states_to_cn(states)
 
 
 def sum_product(framelogprob, log_transmat, alphas, betas, device=0):

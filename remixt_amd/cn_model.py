@@ -712,6 +712,14 @@ class BreakpointModel(object):
 
         return cn[self.seg_fwd_remap], brk_cn
 
+    def sample_cn(self, num_samples, seed=0):
+        """num_samples copy-number paths (K, N, M, 2) drawn from the structured posterior of the last variational
+        update, in experiment segment order (as optimal_cn).  seed: the 64-bit seed of this model's stream
+        (restart_seed(user seed, init_id) in the pipeline)."""
+        if not hasattr(self.model, 'sample_cn'):
+            raise NotImplementedError('kernel module %s has no posterior sampler' % getattr(self._kernel_module(), '__name__', '?'))
+        return self.model.sample_cn(num_samples, seed)[:, self.seg_fwd_remap]
+
     def breakpoint_prob(self):
         return dict(zip(self.breakpoints, np.asarray(self.model.p_breakpoint)))
 

@@ -39,12 +39,12 @@ static inline long long now_ns() { return std::chrono::duration_cast<std::chrono
 enum KernelId {
     KID_STATE_TABLES = 0, KID_SEG_CONST, KID_FRAMELOGPROB, KID_FB, KID_MARGINALS, KID_MARGINALS_AB, KID_OUTLIER_TOTAL,
     KID_OUTLIER_ALLELE, KID_ALLELE_SWAP, KID_BRK_LUT, KID_PAIRWISE, KID_BRK_UPDATE, KID_ELBO_SEG, KID_ELBO_FINAL,
-    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_COUNT
+    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_COUNT
 };
 static const char *kKernelNames[KID_COUNT] = {
     "k_state_tables", "k_seg_const", "k_framelogprob", "k_fb", "k_marginals<true>", "k_marginals<false>", "k_update_outlier_total",
     "k_update_outlier_allele", "k_update_allele_swap", "k_brk_lut", "k_pairwise", "k_brk_update", "k_elbo_seg", "k_elbo_final",
-    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other"};
+    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn"};
 
 struct ProfRec { int id; hipEvent_t a, b; };
 
@@ -159,6 +159,7 @@ struct rmx_batch {
     double *d_vrow = nullptr; size_t vrow_cap = 0;      // [nr][N][SR] lattice rows of k_viterbi_max / k_viterbi_code_max (pads 0)
     uint16_t *d_bp = nullptr; double *d_final = nullptr; int64_t *d_path = nullptr; double *d_logprob = nullptr;
     std::vector<int64_t> last_path; int vit_cap = 0; size_t bp_cap = 0;
+    int16_t *d_samp = nullptr; size_t samp_cap = 0; uint64_t *d_seeds = nullptr; uint32_t *d_sflags = nullptr;   // rmx_sample_cn: paths of a chunk of samples, seeds, flags [R]
     uint16_t *d_comp = nullptr; int32_t *d_ends = nullptr; size_t comp_cap = 0, ends_cap = 0; int last_traceback = 0;      // parallel trace-back: composed maps [nr][NBLK][S], block end states [nr][NBLK]
     uint8_t *d_vit_code = nullptr; double *d_vit_val = nullptr; bool vit_code_ok = false, vit_mul_ok = false;   // 8-bit codes of T(i, o) of class 0 + their values (k_viterbi_code)
     // FB launch configuration
@@ -3008,6 +3009,64 @@ int rmx_infer_cn_batch(rmx_batch *b, int32_t r0, int32_t nr, int64_t *cn_out, do
 int rmx_infer_cn(rmx_batch *b, int32_t r, int64_t *cn_out, double *logprob_out) { BIND(b);
     if (!b || r < 0 || r >= b->R || !cn_out) return fail(RMX_EARG, "bad argument");
     return rmx_infer_cn_batch(b, r, 1, cn_out, logprob_out);
+}
+
+// Posterior paths (forward-filtering backward-sampling, k_sample_cn) of restarts r0 .. r0+nr-1 from the fa plane and the
+// log_transmat snapshot of their last update_p_cn.  fa is written by the forward-backward kernels only: the marginal,
+// pairwise and ELBO passes, the decode and the array read-back read it, and a sweep's next transition snapshot is built
+// only when another forward-backward follows in the same call.  Samples go through a device buffer of at most 64 MiB.
+int rmx_sample_cn(rmx_batch *b, int32_t r0, int32_t nr, int32_t num_samples, const uint64_t *seeds, int16_t *states_out) { BIND(b);
+    if (!b || r0 < 0 || nr < 1 || r0 + nr > b->R || num_samples < 1 || !seeds || !states_out) return fail(RMX_EARG, "bad argument");
+    const Dev &d = b->d;
+    const int N = d.N;
+    if (d.S > 64 * SMP_NSL) return fail(RMX_EUNSUPPORTED, "sample_cn: more than 1024 states");
+    // no update_p_cn yet: there is no forward pass to sample from (the restart is reported like a device-side check)
+    g_err_restarts.clear();
+    for (int r = r0; r < r0 + nr; r++) if (!b->lt_valid[r]) g_err_restarts.push_back(r);
+    if (!g_err_restarts.empty()) {
+        char buf[160]; snprintf(buf, sizeof buf, "sample_cn before update_p_cn (restart %d)", g_err_restarts[0]);
+        return fail_flagged(RMX_EVALUE, buf);
+    }
+    int rc;
+    if (!b->d_seeds && (rc = dalloc(b, &b->d_seeds, b->R))) return rc;
+    if (!b->d_sflags && (rc = dalloc(b, &b->d_sflags, b->R))) return rc;
+    const size_t per_sample = (size_t)nr * N * sizeof(int16_t);
+    const int kc = (int)std::max<size_t>(1, std::min<size_t>((size_t)num_samples, ((size_t)64 << 20) / per_sample));
+    if (b->samp_cap < (size_t)kc * nr * N) {
+        dfree(b, b->d_samp); b->d_samp = nullptr; b->samp_cap = 0;
+        if ((rc = dalloc(b, &b->d_samp, (size_t)kc * nr * N))) return rc;
+        b->samp_cap = (size_t)kc * nr * N;
+    }
+    HIPCHK(hipMemcpyAsync(b->d_seeds, seeds, sizeof(uint64_t) * nr, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemsetAsync(b->d_sflags + r0, 0, sizeof(uint32_t) * nr, b->stream));
+    // runs of restarts whose snapshot was taken under the same transition model (its plain tables)
+    for (int i = 0; i < nr;) {
+        int j = i; while (j < nr && b->lt_model[r0 + j] == b->lt_model[r0 + i]) j++;
+        const int model = b->lt_model[r0 + i];
+        const Dev dv = dev_for_model(b, model);
+        for (int k0 = 0; k0 < num_samples; k0 += kc) {
+            const int nk = std::min(kc, num_samples - k0);
+            {
+                ProfScope ps(b, KID_SAMPLE);
+                hipLaunchKernelGGL(k_sample_cn, dim3(d.NC, j - i, (nk + SMP_WPB - 1) / SMP_WPB), dim3(64 * SMP_WPB), 0, b->stream, dv, r0 + i, k0, nk,
+                                   model == d.tmodel ? 1 : 0, (const uint64_t *)(b->d_seeds + i), b->d_samp, b->d_sflags);
+                HIPCHK(hipGetLastError());
+            }
+            // device [j-i][nk][N] -> host rows (r0+i .. r0+j)[k0 .. k0+nk)
+            HIPCHK(hipMemcpy2DAsync(states_out + ((size_t)i * num_samples + k0) * N, (size_t)num_samples * N * sizeof(int16_t), b->d_samp,
+                                    (size_t)nk * N * sizeof(int16_t), (size_t)nk * N * sizeof(int16_t), j - i, hipMemcpyDeviceToHost, b->stream));
+        }
+        i = j;
+    }
+    uint32_t *e = b->h_err;
+    HIPCHK(hipMemcpyAsync(e, b->d_sflags + r0, sizeof(uint32_t) * nr, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int i = 0; i < nr; i++) if (e[i]) g_err_restarts.push_back(r0 + i);
+    if (!g_err_restarts.empty()) {
+        char buf[160]; snprintf(buf, sizeof buf, "sample_cn: a step has no finite positive weight (restart %d)", g_err_restarts[0]);
+        return fail_flagged(RMX_EASSERT, buf);
+    }
+    return RMX_OK;
 }
 
 // ---- module-level functions -------------------------------------------------------------------

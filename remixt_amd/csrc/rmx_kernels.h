@@ -5324,3 +5324,117 @@ __global__ void k_materialize_joint(Dev d, int r, int uniform, double *out) {
     for (int idx = t; idx < S * S; idx += 256) o[idx] = o[idx] / zsh;
 }
 // cn_states_total / num_alleles_subclonal / is_hdel / is_loh expansions are done on the host.
+
+// =============================================================================
+// Posterior path sampling (forward-filtering backward-sampling).
+// The sampler draws from the chain HMM defined by the framelogprob and log_transmat snapshot of the last
+// update_p_cn: the same target that infer_cn decodes and whose marginals / adjacent joints are
+// posterior_marginals / joint_posterior_marginals.  Per chain, from the last segment backwards: the last
+// segment draws s ~ fa_N-1(s), segment n then s ~ fa_n(s) W_n(s, s_n+1) with W the class table exp(T) (the Wb row
+// s_n+1, contiguous in s) on a plain adjacency, the restart's snapshot weight exp(trans_value) on a breakend
+// adjacency and 1 at a telomere.  The row scales of fa cancel.  Nothing of the model is written.
+// Randomness: Philox4x32-10 keyed by the 64-bit restart seed, counter (segment, sample, 0, 0); one 53-bit uniform
+// per draw.  A (seed, sample) pair therefore gives the same path however restarts are grouped or batched.
+// =============================================================================
+__host__ __device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+    for (int i = 0; i < 10; i++) {
+        if (i) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+        c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
+    }
+}
+// uniform in [0, 1) with 53 random bits: the top 27 bits of word 0 over the top 26 bits of word 1
+__host__ __device__ inline double philox_uniform53(uint64_t seed, int sample, int n) {
+    uint32_t c[4] = {(uint32_t)n, (uint32_t)sample, 0u, 0u};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return (double)(((uint64_t)(c[0] >> 5) << 26) | (uint64_t)(c[1] >> 6)) * 0x1.0p-53;
+}
+
+#define SMP_WPB 4          // waves (= samples) per workgroup of k_sample_cn
+#define SMP_NSL 16         // states per lane: S <= 1024
+#define SMP_ERR_WEIGHT 1u  // a step had no finite positive weight even in the log domain
+// grid (NC, nr, ceil(nk / SMP_WPB)), block 64 * SMP_WPB.  One wave per (restart, chain, sample): lane l holds the
+// weights of states [l * nsl, (l + 1) * nsl), so the wave's prefix sum is the CDF in state order.  out [nr][nk][N]:
+// sample k0 + kk of restart r0 + ri at ((ri * nk) + kk) * N.  use_wb = 0: the plain weights from Tval (the snapshot's
+// transition model is not the current one, whose exp tables Wb holds).
+__global__ __launch_bounds__(64 * SMP_WPB) void k_sample_cn(Dev d, int r0, int k0, int nk, int use_wb, const uint64_t *seeds, int16_t *out,
+                                                           uint32_t *flags) {
+    const int c = blockIdx.x, ri = blockIdx.y, r = r0 + ri;
+    const int lane = threadIdx.x & 63, kk = blockIdx.z * SMP_WPB + (threadIdx.x >> 6);
+    if (kk >= nk) return;      // (the whole wave: no workgroup barrier below)
+    const int S = d.S, nsl = (S + 63) >> 6, sb = lane * nsl;
+    const uint64_t seed = seeds[ri];
+    const int n0 = d.chain_start[c], n1 = d.chain_end[c];
+    int16_t *o = out + ((size_t)ri * nk + kk) * d.N;
+    int snext = 0;
+    for (int n = n1; n >= n0; n--) {
+        const double *fa = d.fa + rs_off(d, r, n);
+        const int tc = n == n1 ? -1 : d.tclass[n];
+        const int bs = tc >= 0 ? d.brk_slot[n] : -1;
+        const double *pd = bs >= 0 ? d.pd_lt + ((size_t)r * d.NBE + bs) * d.M * d.D : nullptr;
+        const double *wrow = (tc >= 0 && bs < 0 && use_wb) ? d.Wb + ((size_t)tc * S + snext) * S : nullptr;
+        double w[SMP_NSL];
+        double ls = 0.;
+#pragma unroll
+        for (int q = 0; q < SMP_NSL; q++) {
+            const int s = sb + q;
+            double v = 0.;
+            if (q < nsl && s < S) {
+                v = fa[s];
+                if (tc >= 0) v *= wrow ? wrow[s] : exp(trans_value(d, n, s, snext, pd));
+            }
+            w[q] = v; ls += v;
+        }
+        double incl = ls;
+        for (int off = 1; off < 64; off <<= 1) { const double t = __shfl_up(incl, off, 64); if (lane >= off) incl += t; }
+        double tot = __shfl(incl, 63, 64);
+        if (!(tot > 0. && tot < INFINITY)) {
+            // fa * W underflowed (extreme penalties) or is not finite: the same step in the log domain
+            double mx = -INFINITY;
+#pragma unroll
+            for (int q = 0; q < SMP_NSL; q++) {
+                const int s = sb + q;
+                double lw = -INFINITY;
+                if (q < nsl && s < S) {
+                    const double a = fa[s];
+                    if (a > 0. && a < INFINITY) lw = log(a) + (tc >= 0 ? trans_value(d, n, s, snext, pd) : 0.);
+                    if (!(lw < INFINITY)) lw = -INFINITY;
+                }
+                w[q] = lw; mx = fmax(mx, lw);
+            }
+            for (int off = 1; off < 64; off <<= 1) mx = fmax(mx, __shfl_xor(mx, off, 64));
+            if (!(mx > -INFINITY)) {
+                if (lane == 0) atomicOr(&flags[r], SMP_ERR_WEIGHT);
+                for (int m = n - lane; m >= n0; m -= 64) o[m] = -1;
+                return;
+            }
+            ls = 0.;
+#pragma unroll
+            for (int q = 0; q < SMP_NSL; q++) { w[q] = w[q] > -INFINITY ? exp(w[q] - mx) : 0.; ls += w[q]; }
+            incl = ls;
+            for (int off = 1; off < 64; off <<= 1) { const double t = __shfl_up(incl, off, 64); if (lane >= off) incl += t; }
+            tot = __shfl(incl, 63, 64);
+        }
+        // inverse CDF: the first lane whose inclusive sum passes u * total, then the first of its states
+        const double tgt = philox_uniform53(seed, k0 + kk, n) * tot;
+        // (only lanes that hold weight: the shuffle scan groups its sums differently per lane, so a lane of zero weights -- padding above S,
+        // underflowed fa -- can still sit an ulp above its predecessor; rounding can leave u * total at the total: then the last state with weight)
+        const unsigned long long hit = __ballot(incl > tgt && ls > 0.), pos = __ballot(ls > 0.);
+        const int L = hit ? __builtin_ctzll(hit) : 63 - __builtin_clzll(pos);
+        double excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = 0.;
+        int pick = -1;
+        if (lane == L) {
+            double acc = excl;
+            int last = -1;
+#pragma unroll
+            for (int q = 0; q < SMP_NSL; q++) {
+                if (pick < 0 && w[q] > 0.) { last = sb + q; acc += w[q]; if (acc > tgt) pick = sb + q; }
+            }
+            if (pick < 0) pick = last;
+        }
+        snext = __shfl(pick, L, 64);
+        if (lane == 0) o[n] = (int16_t)snext;
+    }
+}

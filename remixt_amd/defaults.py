@@ -18,6 +18,10 @@ num_update_iter = 5
 disable_breakpoints = False
 do_h_update = True
 is_female = True
+# (no reference counterpart) posterior copy-number samples per restart behind every fit result: 0 = none (results unchanged);
+# K > 0 adds cn_sample_agreement, cn_state_agreement and ploidy / proportion_divergent quantiles (remixt_amd/sampling.py)
+num_cn_samples = 0
+cn_sample_seed = 0
 
 
 def get_param(config, name):

@@ -649,6 +649,18 @@ class RestartSet(object):
             out.append(res)
         return out
 
+    def sample_cn(self, num_samples, seed=0, init_ids=None):
+        """num_samples posterior copy-number paths of every restart: a list of (K, N, M, 2) int64 arrays in experiment
+        segment order.  Restart r's stream is restart_seed(seed, init_ids[r]) (init_ids default: the restart index), so
+        a restart's samples do not depend on the grouping.  All restarts of the batch are sampled in one call."""
+        from .sampling import restart_seed
+        ids = list(range(len(self.models))) if init_ids is None else list(init_ids)
+        seeds = [restart_seed(seed, i) for i in ids]
+        if self.batch is None or not hasattr(self.batch, 'sample_states'):
+            return [m.sample_cn(num_samples, sd) for m, sd in zip(self.models, seeds)]
+        states = self.batch.sample_states(0, len(self.models), num_samples, seeds)
+        return [self.batch.states_to_cn(states[r])[:, m.seg_fwd_remap] for r, m in enumerate(self.models)]
+
 
 class RestartGroups(object):
     """The restarts of one GPU split into `groups` RestartSets, each with its own device batch
@@ -772,6 +784,12 @@ class RestartGroups(object):
     def results(self):
         return [r for part in self._map(lambda rs: rs.results()) for r in part]
 
+    def sample_cn(self, num_samples, seed=0, init_ids=None):
+        """RestartSet.sample_cn over the groups, restarts in order (init_ids: of all restarts, default their index)."""
+        ids = list(range(self.num_restarts)) if init_ids is None else list(init_ids)
+        return [x for part in self._map(lambda rs: rs.sample_cn(num_samples, seed, ids[self.slices[self.sets.index(rs)]]))
+                for x in part]
+
     def profile(self):
         """{kernel: (ms, launches)} summed over the groups' batches."""
         out = {}
@@ -855,6 +873,10 @@ class DatasetGroups(object):
                 r['dataset'] = i
                 out.append(r)
         return out
+
+    def sample_cn(self, num_samples, seed=0):
+        """RestartGroups.sample_cn of every dataset, dataset after dataset (restart indices within each dataset)."""
+        return [x for part in self._map(lambda part: part.sample_cn(num_samples, seed)) for x in part]
 
     def results_by_dataset(self):
         return self._map(lambda part: part.results())
@@ -943,9 +965,15 @@ def _failure_code(message):
     return 3
 
 
-def _pack(res, N, M, K, nparams, brk_ids, param_names):
+def _sample_len(N, M, cn_samples):
+    """Float slots of the posterior-sample summary in a record (0 when sampling is off: the record is unchanged)."""
+    return 6 + N * M + N if cn_samples else 0
+
+
+def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False):
     """One restart's results as (float64 vector, int8 vector) of fixed length."""
-    f = np.zeros(_HDR + M + nparams + 4 * N, dtype=np.float64)
+    from .sampling import SUMMARY_STATS
+    f = np.zeros(_HDR + M + nparams + 4 * N + _sample_len(N, M, cn_samples), dtype=np.float64)
     st = res['stats']
     f[0] = st['elbo']; f[1] = st['elbo_diff'] if st['elbo_diff'] is not None else np.nan
     f[2] = st['ploidy']; f[3] = st['proportion_divergent']
@@ -954,6 +982,11 @@ def _pack(res, N, M, K, nparams, brk_ids, param_names):
     f[_HDR + M:_HDR + M + nparams] = [st[k] for k in param_names]
     o = _HDR + M + nparams
     f[o:o + 2 * N] = res['p_outlier_total'].ravel(); f[o + 2 * N:o + 4 * N] = res['p_outlier_allele'].ravel()
+    if cn_samples:
+        o += 4 * N
+        f[o:o + 6] = [st[k] for k in SUMMARY_STATS]
+        f[o + 6:o + 6 + N * M] = np.asarray(res['cn_sample_agreement']).ravel()
+        f[o + 6 + N * M:o + 6 + N * M + N] = res['cn_state_agreement']
     i8 = np.zeros(N * M * 2 + K * M + 2 * N, dtype=np.int8)
     i8[:N * M * 2] = res['cn'].ravel()
     i8[N * M * 2:N * M * 2 + K * M] = np.array([res['brk_cn'][k] for k in brk_ids]).ravel()
@@ -962,7 +995,8 @@ def _pack(res, N, M, K, nparams, brk_ids, param_names):
     return f, i8
 
 
-def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params):
+def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_samples=False):
+    from .sampling import SUMMARY_STATS
     res = dict()
     res['h'] = f[_HDR:_HDR + M].copy()
     o = _HDR + M + nparams
@@ -979,18 +1013,27 @@ def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params):
           'mode_idx': init_params.get('mode_idx', 0), 'divergence_weight': init_params['divergence_weight']}
     for j, k in enumerate(param_names):
         st[k] = float(f[_HDR + M + j])
+    if cn_samples:
+        o += 4 * N
+        for j, k in enumerate(SUMMARY_STATS):
+            st[k] = float(f[o + j])
+        res['cn_sample_agreement'] = f[o + 6:o + 6 + N * M].reshape(N, M).copy()
+        res['cn_state_agreement'] = f[o + 6 + N * M:o + 6 + N * M + N].copy()
     res['stats'] = st
     return res
 
 
 def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clones=3, num_em_iter=5, num_update_iter=5,
-                             device=None, kernel_module=None, seeds=None, quiet=True, groups=2, **model_kwargs):
+                             device=None, kernel_module=None, seeds=None, quiet=True, groups=2, num_cn_samples=0, cn_sample_seed=0,
+                             **model_kwargs):
     """Fit all restarts across the ranks of the default torch.distributed group.
 
     Every rank holds the (small, read-only) experiment; rank g fits restarts
     g, g+G, g+2G, ... on its own GPU; one all-gather of fixed-size result records
     returns every restart's results to every rank (`collate` stores all of them,
     analysis/pipeline.py:289-291).  Works on one process without torch.distributed.
+    num_cn_samples > 0: every result also summarises that many posterior samples (restart i's stream:
+    restart_seed(cn_sample_seed, i)), and the records carry the summary.
     """
     import torch
     import torch.distributed as dist
@@ -1009,16 +1052,28 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
                            **model_kwargs)
         rs.fit(num_em_iter, num_update_iter)
         local = rs.results()
+        if num_cn_samples > 0:
+            add_cn_sample_summaries(rs, local, experiment, num_cn_samples, cn_sample_seed, mine)
         param_names = list(rs.models[0].likelihood_params)
         rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     if param_names is None:
         nc = model_kwargs.get('normal_contamination', True)
         param_names = ['negbin_r_0', 'negbin_r_1', 'betabin_M_0', 'betabin_M_1'] + (
             [] if nc else ['negbin_hdel_mu', 'negbin_hdel_r_0', 'negbin_hdel_r_1', 'betabin_loh_p', 'betabin_loh_M_0', 'betabin_loh_M_1'])
-    return gather_result_records(local, experiment, init_params, num_clones, param_names, device=device)
+    return gather_result_records(local, experiment, init_params, num_clones, param_names, device=device, cn_samples=num_cn_samples > 0)
 
 
-def gather_result_records(local, experiment, init_params, num_clones, param_names, device=None, timing=None, local_ids=None):
+def add_cn_sample_summaries(rs, results, experiment, num_samples, seed, init_ids):
+    """Draw `num_samples` posterior paths of every restart of `rs` (a RestartSet / RestartGroups; restart r's stream is
+    restart_seed(seed, init_ids[r])) and add their summary to results[r] (sampling.add_sample_summary)."""
+    from .sampling import add_sample_summary
+    samples = rs.sample_cn(num_samples, seed, init_ids=list(init_ids))
+    for res, smp in zip(results, samples):
+        add_sample_summary(res, smp, experiment.l)
+    return results
+
+
+def gather_result_records(local, experiment, init_params, num_clones, param_names, device=None, timing=None, local_ids=None, cn_samples=False):
     """The one collective of the path: every rank contributes the fixed-size records of the restarts
     it fitted (`local`, in the order of shard_indices) -- one float64 record (ELBO, h, parameters, outlier
     probabilities, failure code) and one int8 record (cn, brk_cn, masks) per restart -- and every rank gets the
@@ -1047,11 +1102,11 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
             per_rank = int(cnt_.item())
     if len(local) > per_rank:
         raise ValueError('gather_result_records: %d local results for a share of %d (pass local_ids for shares that are not shard_indices\')' % (len(local), per_rank))
-    flen = _HDR + M + nparams + 4 * N
+    flen = _HDR + M + nparams + 4 * N + _sample_len(N, M, cn_samples)
     ilen = N * M * 2 + K * M + 2 * N
     fbuf = np.full((per_rank, flen), np.nan); ibuf = np.zeros((per_rank, ilen), dtype=np.int8)
     for j, res in enumerate(local):
-        fbuf[j], ibuf[j] = _pack(res, N, M, K, nparams, brk_ids, param_names)
+        fbuf[j], ibuf[j] = _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples)
     if local_ids is not None:
         ids_t = np.full((per_rank,), -1, dtype=np.int64); ids_t[:len(local_ids)] = local_ids
     t0 = time.perf_counter()
@@ -1083,7 +1138,7 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
     for g in range(world):
         ids_g = shard_indices(len(init_params), world, g) if ids_all is None else [int(i) for i in ids_all[g] if i >= 0]
         for j, i in enumerate(ids_g):
-            results[i] = _unpack(fall[g][j], iall[g][j], N, M, K, nparams, brk_ids, param_names, init_params[i])
+            results[i] = _unpack(fall[g][j], iall[g][j], N, M, K, nparams, brk_ids, param_names, init_params[i], cn_samples)
     return results
 
 

@@ -344,6 +344,21 @@ int rmx_infer_cn_batch(rmx_batch *b, int32_t r0, int32_t nr, int64_t *cn_out, do
  * has no finite positive weight. */
 int rmx_sample_cn(rmx_batch *b, int32_t r0, int32_t nr, int32_t num_samples, const uint64_t *seeds, int16_t *states_out);
 
+/* -- posterior summaries (no reference counterpart) -------------------------- */
+/* Linear functionals and row statistics of the attribute posterior_marginals of restarts r0 .. r0+nr-1, exactly as
+ * rmx_get_array would return it for each of them (whatever the last sweep or an rmx_set_array left there: there is no
+ * validity state), computed on the device in one read of it.  The model is not modified.
+ *   weights   [C][S][Q] one table per state class (C = num_classes of the problem), 1 <= Q <= 256; or NULL with Q = 0
+ *   states    int16 [nr][N] a state per segment (e.g. a decoded path), each in [0, S); or NULL
+ *   proj_out  [nr][N][Q]: sum over s < S of post[n][s] * weights[seg_class[n]][s][q]; or NULL
+ *   stats_out [nr][N][3]: the row maximum, the entropy -sum_{post > 0} post log(post), post[n][states[n]] (0 without
+ *             states); or NULL
+ *   argmax_out int16 [nr][N]: the first index of the row maximum (numpy.argmax); or NULL
+ * A restart's outputs are bit-identical in any [r0, r0+nr) range that holds it.  RMX_EARG, with nothing launched: a bad
+ * range, all outputs NULL, proj_out without weights, Q out of range, a states entry outside [0, S). */
+int rmx_posterior_summary(rmx_batch *b, int32_t r0, int32_t nr, int32_t Q, const double *weights, const int16_t *states,
+                          double *proj_out, double *stats_out, int16_t *argmax_out);
+
 /* -- module-level functions on caller-supplied dense inputs ----------------- */
 /* sum_product (:1213-1246): f [N][S], T [N-1][S][S] -> alphas, betas [N][S] */
 int rmx_sum_product(const double *f, const double *T, double *alphas, double *betas,

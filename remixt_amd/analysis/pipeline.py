@@ -6,9 +6,9 @@ import pickle
 
 import numpy as np
 
-from .. import defaults, sampling
+from .. import defaults, posteriors, sampling
 from ..cn_model import BreakpointModel
-from ..restarts import RestartSet, add_cn_sample_summaries, collect_fit_results, fit_restarts_distributed, select_optimal  # noqa: F401
+from ..restarts import RestartSet, add_cn_sample_summaries, add_posterior_summaries, collect_fit_results, fit_restarts_distributed, select_optimal  # noqa: F401
 
 
 def _model_kwargs(experiment, config):
@@ -62,6 +62,11 @@ def fit(experiment, init_params, config, device=0, quiet=False, init_id=0):
     if num_samples > 0:
         seed = sampling.restart_seed(defaults.get_param(config, 'cn_sample_seed'), init_id)
         sampling.add_sample_summary(res, model.sample_cn(num_samples, seed), experiment.l)
+    if defaults.get_param(config, 'cn_posterior_summary'):
+        b = model.model._batch
+        states = posteriors.states_in_model_order(res['cn'], b, model.seg_fwd_remap)[None]
+        s = posteriors.batch_summaries(b, model.model._r, 1, states=states)[0]
+        posteriors.add_posterior_summary(res, dict((k, v[model.seg_fwd_remap]) for k, v in s.items()), experiment.l)
     return res
 
 
@@ -105,6 +110,8 @@ def fit_restarts(experiment, init_params_by_id, config, device=0, quiet=True, se
     num_samples = defaults.get_param(config, 'num_cn_samples')
     if num_samples > 0:
         add_cn_sample_summaries(rs, results, experiment, num_samples, defaults.get_param(config, 'cn_sample_seed'), ids)
+    if defaults.get_param(config, 'cn_posterior_summary'):
+        add_posterior_summaries(rs, results, experiment)
     out = dict(zip(ids, results))
     rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     return out
@@ -244,6 +251,10 @@ def store_fit_results(store, experiment, fit_results, key_prefix):
     if 'cn_sample_agreement' in fit_results:      # (config num_cn_samples > 0)
         store[key_prefix + '/cn_sample_agreement'] = pd.DataFrame(np.asarray(fit_results['cn_sample_agreement']))
         store[key_prefix + '/cn_state_agreement'] = pd.Series(np.asarray(fit_results['cn_state_agreement']))
+    if 'cn_posterior_prob' in fit_results:        # (config cn_posterior_summary)
+        for k in posteriors.COMPACT_ARRAYS:
+            v = np.asarray(fit_results[k])
+            store[key_prefix + '/' + k] = pd.DataFrame(v) if v.ndim == 2 else pd.Series(v)
 
 
 def store_optimal_solution(stats, store, config):

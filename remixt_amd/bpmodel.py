@@ -539,6 +539,45 @@ class RemixtBatch(object):
         states = np.asarray(states)
         return self.cn_classes[self.seg_class, states]
 
+    def posterior_summary_raw(self, r0, nr, weights=None, states=None, want_stats=True, want_argmax=True):
+        """Linear functionals and row statistics of posterior_marginals of restarts r0 .. r0+nr-1 from one device pass
+        (rmx_posterior_summary): (proj, stats, argmax), each None where not requested.  weights (C, S, Q), or (S, Q) for
+        all classes alike, Q <= 256 -> proj (nr, N, Q) = marginals @ weights[seg_class]; stats (nr, N, 3): row maximum,
+        entropy, marginal at states[r, n] (states: int (nr, N) or (N,) with nr = 1; 0 without); argmax int16 (nr, N):
+        the first index of the row maximum."""
+        r0, nr = int(r0), int(nr)
+        N, S, C_ = self.num_segments, self.num_cn_states, self.cn_classes.shape[0]
+        rows = max(nr, 0)
+        Q, wp, proj = 0, _dp(), None
+        if weights is not None:
+            w = np.asarray(weights, dtype=np.float64)
+            if w.ndim == 2:
+                w = np.broadcast_to(w[None], (C_,) + w.shape)
+            if w.ndim != 3 or w.shape[:2] != (C_, S):
+                raise ValueError('weights must have shape (num_classes, num_cn_states, Q) or (num_cn_states, Q)')
+            w = np.ascontiguousarray(w)
+            Q = w.shape[2]
+            wbuf = w if w.size else np.zeros(1)      # (Q = 0 is the library's error to raise: a non-null pointer reaches it)
+            wp = wbuf.ctypes.data_as(_dp)
+            proj = np.zeros((rows, N, Q), dtype=np.float64)
+            pbuf = proj if proj.size else np.zeros(1)
+        i16p = C.POINTER(C.c_int16)
+        sp = i16p()
+        if states is not None:
+            st = np.asarray(states)
+            if st.shape != (rows, N) and not (rows == 1 and st.shape == (N,)):
+                raise ValueError('states must have shape (nr, num_segments)')
+            if st.size and (st.min() < -32768 or st.max() > 32767):
+                raise ValueError('state index out of range')
+            st = np.ascontiguousarray(st, dtype=np.int16)
+            sp = st.ctypes.data_as(i16p)
+        stats = np.zeros((rows, N, 3), dtype=np.float64) if want_stats else None
+        amax = np.zeros((rows, N), dtype=np.int16) if want_argmax else None
+        self._ck(self._lib.rmx_posterior_summary(
+            self._handle, r0, nr, Q, wp, sp, pbuf.ctypes.data_as(_dp) if proj is not None else _dp(),
+            stats.ctypes.data_as(_dp) if stats is not None else _dp(), amax.ctypes.data_as(i16p) if amax is not None else i16p()))
+        return proj, stats, amax
+
     # -- measurement ------------------------------------------------------------
     def timer_start(self):
         self._ck(self._lib.rmx_timer_start(self._handle))
@@ -756,6 +795,15 @@ class RemixtModel(object):
         """num_samples posterior copy-number paths (K, N, M, 2) int64 of this model (seed: 64-bit)."""
         states = self._batch.sample_states(self._r, 1, num_samples, [seed])[0]
         return self._batch.states_to_cn(states)
+
+    def posterior_summary_raw(self, weights=None, states=None, want_stats=True, want_argmax=True):
+        """RemixtBatch.posterior_summary_raw of this model: (proj (N, Q), stats (N, 3), argmax (N,)), None where not requested."""
+        out = self._batch.posterior_summary_raw(self._r, 1, weights=weights, states=states, want_stats=want_stats, want_argmax=want_argmax)
+        return tuple(None if a is None else a[0] for a in out)
+
+    def posterior_project(self, weights):
+        """posterior_marginals @ weights[class of the segment] -> (N, Q), on the device: weights (C, S, Q) or (S, Q), Q <= 256."""
+        return self.posterior_summary_raw(weights=weights, want_stats=False, want_argmax=False)[0]
 
 
 def sum_product(framelogprob, log_transmat, alphas, betas, device=0):

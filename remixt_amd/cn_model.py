@@ -720,6 +720,20 @@ class BreakpointModel(object):
             raise NotImplementedError('kernel module %s has no posterior sampler' % getattr(self._kernel_module(), '__name__', '?'))
         return self.model.sample_cn(num_samples, seed)[:, self.seg_fwd_remap]
 
+    def posterior_summary(self, cn=None, marginals=False):
+        """Exact per-segment summaries of the posterior marginals of the last variational update, in experiment segment
+        order (as optimal_cn): the arrays of posteriors.unpack -- total_cn_mean / total_cn_sd (N, M), p_subclonal, p_loh,
+        p_hdel, expected_alleles_subclonal, cn_posterior_max, cn_posterior_entropy, cn_mpm, and cn_marginals with
+        marginals=True.  cn: an already decoded path ([N][M][2], model segment order, e.g. what infer_cn fills); it
+        supplies cn_posterior_prob, the marginal probability of its state at every segment."""
+        from . import posteriors
+        if not hasattr(self.model, 'posterior_summary_raw'):
+            raise NotImplementedError('kernel module %s has no posterior summary' % getattr(self._kernel_module(), '__name__', '?'))
+        b = self.model._batch
+        states = None if cn is None else posteriors.cn_to_states(cn, b.cn_classes, b.seg_class)[None]
+        s = posteriors.batch_summaries(b, self.model._r, 1, states=states, marginals=marginals)[0]
+        return dict((k, v[self.seg_fwd_remap]) for k, v in s.items())
+
     def breakpoint_prob(self):
         return dict(zip(self.breakpoints, np.asarray(self.model.p_breakpoint)))
 

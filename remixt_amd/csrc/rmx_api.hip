@@ -39,12 +39,12 @@ static inline long long now_ns() { return std::chrono::duration_cast<std::chrono
 enum KernelId {
     KID_STATE_TABLES = 0, KID_SEG_CONST, KID_FRAMELOGPROB, KID_FB, KID_MARGINALS, KID_MARGINALS_AB, KID_OUTLIER_TOTAL,
     KID_OUTLIER_ALLELE, KID_ALLELE_SWAP, KID_BRK_LUT, KID_PAIRWISE, KID_BRK_UPDATE, KID_ELBO_SEG, KID_ELBO_FINAL,
-    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_COUNT
+    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_POST_SUMMARY, KID_COUNT
 };
 static const char *kKernelNames[KID_COUNT] = {
     "k_state_tables", "k_seg_const", "k_framelogprob", "k_fb", "k_marginals<true>", "k_marginals<false>", "k_update_outlier_total",
     "k_update_outlier_allele", "k_update_allele_swap", "k_brk_lut", "k_pairwise", "k_brk_update", "k_elbo_seg", "k_elbo_final",
-    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn"};
+    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn", "k_posterior_summary"};
 
 struct ProfRec { int id; hipEvent_t a, b; };
 
@@ -160,6 +160,7 @@ struct rmx_batch {
     uint16_t *d_bp = nullptr; double *d_final = nullptr; int64_t *d_path = nullptr; double *d_logprob = nullptr;
     std::vector<int64_t> last_path; int vit_cap = 0; size_t bp_cap = 0;
     int16_t *d_samp = nullptr; size_t samp_cap = 0; uint64_t *d_seeds = nullptr; uint32_t *d_sflags = nullptr;   // rmx_sample_cn: paths of a chunk of samples, seeds, flags [R]
+    double *d_psum = nullptr; size_t psum_cap = 0; double *d_psw = nullptr; size_t psw_cap = 0;   // rmx_posterior_summary: output staging of a chunk (doubles), weights [C][S][Q]
     uint16_t *d_comp = nullptr; int32_t *d_ends = nullptr; size_t comp_cap = 0, ends_cap = 0; int last_traceback = 0;      // parallel trace-back: composed maps [nr][NBLK][S], block end states [nr][NBLK]
     uint8_t *d_vit_code = nullptr; double *d_vit_val = nullptr; bool vit_code_ok = false, vit_mul_ok = false;   // 8-bit codes of T(i, o) of class 0 + their values (k_viterbi_code)
     // FB launch configuration
@@ -3066,6 +3067,73 @@ int rmx_sample_cn(rmx_batch *b, int32_t r0, int32_t nr, int32_t num_samples, con
         char buf[160]; snprintf(buf, sizeof buf, "sample_cn: a step has no finite positive weight (restart %d)", g_err_restarts[0]);
         return fail_flagged(RMX_EASSERT, buf);
     }
+    return RMX_OK;
+}
+
+// Posterior summaries (k_posterior_summary) of restarts r0 .. r0+nr-1: linear functionals, row statistics and arg-max of
+// d.post -- the plane rmx_get_array(RMX_A_POSTERIOR_MARGINALS) reads, whatever the last sweep or rmx_set_array left there --
+// in one pass.  Outputs go through one device staging buffer of at most 64 MiB, chunked over segment ranges (and over
+// restarts where 16 segments of all of them would not fit); every (restart, 16-segment tile) is computed by one wave on its
+// own, so a restart's results do not depend on the range or the chunking.
+int rmx_posterior_summary(rmx_batch *b, int32_t r0, int32_t nr, int32_t Q, const double *weights, const int16_t *states,
+                          double *proj_out, double *stats_out, int16_t *argmax_out) { BIND(b);
+    if (!b || r0 < 0 || nr < 1 || (int64_t)r0 + nr > b->R) return fail(RMX_EARG, "bad restart range");
+    if (!proj_out && !stats_out && !argmax_out) return fail(RMX_EARG, "posterior_summary: no output requested");
+    if (weights ? (Q < 1 || Q > 256) : Q != 0) return fail(RMX_EARG, "posterior_summary: Q must be 1 .. 256 with weights, 0 without");
+    if (proj_out && !weights) return fail(RMX_EARG, "posterior_summary: a projection needs weights");
+    const Dev &d = b->d;
+    const int N = d.N, S = d.S;
+    if (states) {       // before anything is queued: the kernel gathers post[n][states[n]] unchecked
+        const size_t cnt = (size_t)nr * N;
+        for (size_t i = 0; i < cnt; i++) if (states[i] < 0 || states[i] >= S) return fail(RMX_EARG, "posterior_summary: state index out of range");
+    }
+    const size_t lds = (size_t)PSM_TN * (d.SP + 4) * sizeof(double);
+    if (lds > kLdsBudget) return fail(RMX_EUNSUPPORTED, "posterior_summary: too many states for one LDS tile");
+    const bool want_proj = proj_out != nullptr, want_st = stats_out && states;
+    const size_t per_seg = (want_proj ? (size_t)Q * 8 : 0) + (stats_out ? 24 : 0) + (argmax_out ? 2 : 0) + (want_st ? 2 : 0);
+    const size_t budget = (size_t)64 << 20;
+    const int nrc = (int)std::min<size_t>({(size_t)nr, std::max<size_t>(1, budget / (PSM_TN * per_seg)), (size_t)65535});
+    size_t ncap = budget / ((size_t)nrc * per_seg);
+    ncap = ncap >= (size_t)N ? (size_t)N : std::max<size_t>(PSM_TN, ncap / PSM_TN * PSM_TN);
+    // staging layout in doubles: proj [nrc][ncap][Q], stats [nrc][ncap][3], then int16 argmax and states [nrc][ncap] each
+    const size_t rows = (size_t)nrc * ncap;
+    const size_t o_stats = want_proj ? rows * Q : 0, o_i16 = o_stats + (stats_out ? rows * 3 : 0), need = o_i16 + (rows * 4 + 7) / 8 + 1;
+    int rc;
+    if (b->psum_cap < need) {
+        dfree(b, b->d_psum); b->d_psum = nullptr; b->psum_cap = 0;
+        if ((rc = dalloc(b, &b->d_psum, need))) return rc;
+        b->psum_cap = need;
+    }
+    if (want_proj) {
+        const size_t wn = (size_t)d.C * S * Q;
+        if (b->psw_cap < wn) {
+            dfree(b, b->d_psw); b->d_psw = nullptr; b->psw_cap = 0;
+            if ((rc = dalloc(b, &b->d_psw, wn))) return rc;
+            b->psw_cap = wn;
+        }
+        HIPCHK(hipMemcpyAsync(b->d_psw, weights, wn * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    }
+    if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)k_posterior_summary, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    double *dproj = want_proj ? b->d_psum : nullptr, *dstats = stats_out ? b->d_psum + o_stats : nullptr;
+    int16_t *damax = (int16_t *)(b->d_psum + o_i16), *dst = damax + rows;
+    for (int ra = 0; ra < nr; ra += nrc) {
+        const int nrr = std::min(nrc, nr - ra);
+        for (size_t n0 = 0; n0 < (size_t)N; n0 += ncap) {
+            const size_t nc = std::min(ncap, (size_t)N - n0);
+            const size_t h0 = (size_t)ra * N + n0;      // first host row of the chunk; host rows of a restart are N apart, device rows nc
+            if (want_st) HIPCHK(hipMemcpy2DAsync(dst, nc * 2, states + h0, (size_t)N * 2, nc * 2, nrr, hipMemcpyHostToDevice, b->stream));
+            {
+                ProfScope ps(b, KID_POST_SUMMARY);
+                hipLaunchKernelGGL(k_posterior_summary, dim3((unsigned)((nc + PSM_TN - 1) / PSM_TN), nrr), dim3(64), lds, b->stream, d, r0 + ra, (int)n0, (int)nc,
+                                   want_proj ? Q : 0, (const double *)b->d_psw, want_st ? (const int16_t *)dst : nullptr, dproj, dstats, argmax_out ? damax : nullptr);
+                HIPCHK(hipGetLastError());
+            }
+            if (want_proj) HIPCHK(hipMemcpy2DAsync(proj_out + h0 * Q, (size_t)N * Q * 8, dproj, nc * Q * 8, nc * Q * 8, nrr, hipMemcpyDeviceToHost, b->stream));
+            if (stats_out) HIPCHK(hipMemcpy2DAsync(stats_out + h0 * 3, (size_t)N * 24, dstats, nc * 24, nc * 24, nrr, hipMemcpyDeviceToHost, b->stream));
+            if (argmax_out) HIPCHK(hipMemcpy2DAsync(argmax_out + h0, (size_t)N * 2, damax, nc * 2, nc * 2, nrr, hipMemcpyDeviceToHost, b->stream));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(b->stream));
     return RMX_OK;
 }
 

@@ -5438,3 +5438,101 @@ __global__ __launch_bounds__(64 * SMP_WPB) void k_sample_cn(Dev d, int r0, int k
         if (lane == 0) o[n] = (int16_t)snext;
     }
 }
+
+// =============================================================================
+// Posterior summaries: linear functionals and row statistics of posterior_marginals in one read.
+// proj[n][q] = sum_s post[n][s] W[seg_class[n]][s][q]; per row the maximum, its first index, the entropy
+// -sum_{post > 0} post log post and the entry at a caller-supplied state.  Nothing of the model is written.
+// One wave per tile of PSM_TN = 16 consecutive segments of one restart (grid (ceil(nc / 16), restarts), block 64):
+//  1. the 16 rows go to LDS with coalesced loads (lane = state index).  Only columns s < S are read; the pad columns
+//     [S, SP) of the LDS tile are written as 0, so what earlier kernels left in the pads of d.post is never loaded.
+//  2. statistics from LDS, four lanes per row (lane = 4 row + j takes states j, j + 4, ...), combined by a two-step
+//     butterfly: a fixed order per row, the same in every launch.
+//  3. the projection on v_mfma_f64_16x16x4_f64 in column tiles of 16: A[i = lane & 15][k = lane >> 4] is the LDS
+//     tile, B[k][j = lane & 15] the weight block read from global memory (128-byte rows, L2 resident), D row
+//     (lane >> 4) + 4 reg, column lane & 15.  A tile that mixes state classes takes one pass per class present, with the
+//     A operand of the other classes' rows selected (not multiplied) to 0; B is selected to 0 for s >= S and q >= Q.
+// LDS row stride SP + 4 doubles = 4 * odd: the eight rows a half-wave of phase 2 or 3 reads fall on distinct banks.
+// Outputs are relative to the chunk: segment nbeg + t of restart r0 + ri at row ri * nc + t.
+// =============================================================================
+#define PSM_TN 16
+typedef double psm_d4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(64) void k_posterior_summary(Dev d, int r0, int nbeg, int nc, int Q, const double *W, const int16_t *states,
+                                                          double *proj, double *stats, int16_t *amax) {
+    extern __shared__ double psm_tile[];                // [PSM_TN][SP + 4]
+    const int lane = threadIdx.x, ri = blockIdx.y, r = r0 + ri;
+    const int t0 = blockIdx.x * PSM_TN;
+    const int S = d.S, SP = d.SP, LR = SP + 4;
+    const int rows = min(PSM_TN, nc - t0);
+    // ---- 1. stage -----------------------------------------------------------------------------------
+    // (the load address is clamped to the last real column, so a pad column is never read, and the select keeps it out of the tile)
+    for (int s = lane; s < SP; s += 64) {
+        const double *pcol = d.post + rs_off(d, r, nbeg + t0) + (s < S ? s : S - 1);
+#pragma unroll
+        for (int i = 0; i < PSM_TN; i++) {
+            const double v = pcol[(size_t)(i < rows ? i : 0) * SP];
+            psm_tile[i * LR + s] = (i < rows && s < S) ? v : 0.;
+        }
+    }
+    __syncthreads();
+    // ---- 2. row statistics ----------------------------------------------------------------------------
+    if (stats || amax) {
+        const int row = lane >> 2, j = lane & 3;
+        const double *lrow = psm_tile + row * LR;
+        double mx = -INFINITY, ent = 0.;
+        int am = 0x7fffffff;
+        for (int s = j; s < S; s += 4) {
+            const double v = lrow[s];
+            if (v > mx) { mx = v; am = s; }
+            if (stats && v > 0.) ent += v * (v >= 2.2250738585072014e-308 ? fast_log_pos(v) : log(v));
+        }
+        for (int off = 1; off < 4; off <<= 1) {
+            const double omx = __shfl_xor(mx, off, 64);
+            const int oam = __shfl_xor(am, off, 64);
+            ent += __shfl_xor(ent, off, 64);
+            if (omx > mx || (omx == mx && oam < am)) { mx = omx; am = oam; }
+        }
+        if (am == 0x7fffffff) am = 0;       // (no entry compared greater than -inf: a row of NaN)
+        if (j == 0 && row < rows) {
+            const size_t o = (size_t)ri * nc + t0 + row;
+            if (amax) amax[o] = (int16_t)am;
+            if (stats) {
+                stats[o * 3] = mx;
+                stats[o * 3 + 1] = 0. - ent;
+                stats[o * 3 + 2] = states ? lrow[states[o]] : 0.;
+            }
+        }
+    }
+    // ---- 3. projection --------------------------------------------------------------------------------
+    if (!proj) return;
+    const int ai = lane & 15, kk = lane >> 4;
+    const int mycls = ai < rows ? d.seg_class[nbeg + t0 + ai] : -1;
+    const double *arow = psm_tile + ai * LR + kk;
+    for (int q0 = 0; q0 < Q; q0 += 16) {
+        const int q = q0 + ai;
+        const bool qok = q < Q;
+        psm_d4 acc = {0., 0., 0., 0.};
+        for (int c = 0; c < d.C; c++) {
+            const bool mine = mycls == c;
+            if (!__ballot(mine)) continue;
+            const double *wc = W + (size_t)c * S * Q + (qok ? q : 0);
+            // 16 states per round (SP rounded up: the extra columns are selected to 0 on both operands); the matrix instruction is
+            // convergent, so only a constant trip count unrolls, and the round's four operand pairs are then loaded together
+            for (int k0 = 0; k0 < SP; k0 += 16) {
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int s = k0 + 4 * u + kk;
+                    const bool sok = s < S;
+                    const double av = arow[sok ? s - kk : 0];
+                    const double bv = wc[(size_t)(sok ? s : 0) * Q];
+                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64((mine && sok) ? av : 0., (qok && sok) ? bv : 0., acc, 0, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const int row = kk + 4 * g;
+            if (qok && row < rows) proj[((size_t)ri * nc + t0 + row) * Q + q] = acc[g];
+        }
+    }
+}

@@ -22,6 +22,10 @@ is_female = True
 # K > 0 adds cn_sample_agreement, cn_state_agreement and ploidy / proportion_divergent quantiles (remixt_amd/sampling.py)
 num_cn_samples = 0
 cn_sample_seed = 0
+# (no reference counterpart) exact per-segment posterior summaries behind every fit result: False = none (results unchanged);
+# True adds cn_posterior_prob / _max / _entropy, p_subclonal, p_loh, p_hdel, total_cn_mean, total_cn_sd and the stats
+# ploidy_posterior_mean / proportion_divergent_posterior_mean (remixt_amd/posteriors.py)
+cn_posterior_summary = False
 
 
 def get_param(config, name):

@@ -661,6 +661,22 @@ class RestartSet(object):
         states = self.batch.sample_states(0, len(self.models), num_samples, seeds)
         return [self.batch.states_to_cn(states[r])[:, m.seg_fwd_remap] for r, m in enumerate(self.models)]
 
+    def posterior_summary(self, cn=None, marginals=False):
+        """Exact posterior summaries of every restart (BreakpointModel.posterior_summary): a list of dicts of arrays in
+        experiment segment order, from one device call for the whole batch.  cn: the restarts' decoded paths in
+        experiment order (the `cn` of results()), which supply cn_posterior_prob; None leaves that key out."""
+        from . import posteriors
+        if self.batch is None or not hasattr(self.batch, 'posterior_summary_raw'):
+            if cn is not None:
+                raise NotImplementedError('posterior summaries against a decoded path need the batched kernel module')
+            return [m.posterior_summary(marginals=marginals) for m in self.models]
+        b, R = self.batch, len(self.models)
+        states = None
+        if cn is not None:
+            states = np.stack([posteriors.states_in_model_order(cn[r], b, m.seg_fwd_remap) for r, m in enumerate(self.models)])
+        out = posteriors.batch_summaries(b, 0, R, states=states, marginals=marginals)
+        return [dict((k, v[m.seg_fwd_remap]) for k, v in s.items()) for s, m in zip(out, self.models)]
+
 
 class RestartGroups(object):
     """The restarts of one GPU split into `groups` RestartSets, each with its own device batch
@@ -790,6 +806,11 @@ class RestartGroups(object):
         return [x for part in self._map(lambda rs: rs.sample_cn(num_samples, seed, ids[self.slices[self.sets.index(rs)]]))
                 for x in part]
 
+    def posterior_summary(self, cn=None, marginals=False):
+        """RestartSet.posterior_summary over the groups, restarts in order (cn: of all restarts)."""
+        return [x for part in self._map(lambda rs: rs.posterior_summary(None if cn is None else cn[self.slices[self.sets.index(rs)]], marginals))
+                for x in part]
+
     def profile(self):
         """{kernel: (ms, launches)} summed over the groups' batches."""
         out = {}
@@ -877,6 +898,10 @@ class DatasetGroups(object):
     def sample_cn(self, num_samples, seed=0):
         """RestartGroups.sample_cn of every dataset, dataset after dataset (restart indices within each dataset)."""
         return [x for part in self._map(lambda part: part.sample_cn(num_samples, seed)) for x in part]
+
+    def posterior_summary(self, cn=None, marginals=False):
+        """RestartGroups.posterior_summary of every dataset, dataset after dataset (cn: per dataset, a list of its restarts' paths)."""
+        return [x for part in self._map(lambda part: part.posterior_summary(None if cn is None else cn[self.parts.index(part)], marginals)) for x in part]
 
     def results_by_dataset(self):
         return self._map(lambda part: part.results())
@@ -970,10 +995,22 @@ def _sample_len(N, M, cn_samples):
     return 6 + N * M + N if cn_samples else 0
 
 
-def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False):
+def _posterior_len(N, M, cn_posterior):
+    """Float slots of the exact posterior summary in a record (0 when it is off: the record is unchanged): six (N,)
+    arrays, two (N, M) arrays, two stats."""
+    return N * (6 + 2 * M) + 2 if cn_posterior else 0
+
+
+def _posterior_fields(N, M):
+    """(name, shape) of the arrays of posteriors.COMPACT_ARRAYS in record order."""
+    from .posteriors import COMPACT_ARRAYS
+    return [(k, (N, M) if k.startswith('total_cn') else (N,)) for k in COMPACT_ARRAYS]
+
+
+def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_posterior=False):
     """One restart's results as (float64 vector, int8 vector) of fixed length."""
     from .sampling import SUMMARY_STATS
-    f = np.zeros(_HDR + M + nparams + 4 * N + _sample_len(N, M, cn_samples), dtype=np.float64)
+    f = np.zeros(_HDR + M + nparams + 4 * N + _sample_len(N, M, cn_samples) + _posterior_len(N, M, cn_posterior), dtype=np.float64)
     st = res['stats']
     f[0] = st['elbo']; f[1] = st['elbo_diff'] if st['elbo_diff'] is not None else np.nan
     f[2] = st['ploidy']; f[3] = st['proportion_divergent']
@@ -987,6 +1024,14 @@ def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False):
         f[o:o + 6] = [st[k] for k in SUMMARY_STATS]
         f[o + 6:o + 6 + N * M] = np.asarray(res['cn_sample_agreement']).ravel()
         f[o + 6 + N * M:o + 6 + N * M + N] = res['cn_state_agreement']
+    if cn_posterior:
+        from . import posteriors
+        o = len(f) - _posterior_len(N, M, True)
+        f[o:o + 2] = [st[k] for k in posteriors.SUMMARY_STATS]
+        o += 2
+        for k, shape in _posterior_fields(N, M):
+            n = int(np.prod(shape))
+            f[o:o + n] = np.asarray(res[k]).ravel(); o += n
     i8 = np.zeros(N * M * 2 + K * M + 2 * N, dtype=np.int8)
     i8[:N * M * 2] = res['cn'].ravel()
     i8[N * M * 2:N * M * 2 + K * M] = np.array([res['brk_cn'][k] for k in brk_ids]).ravel()
@@ -995,7 +1040,7 @@ def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False):
     return f, i8
 
 
-def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_samples=False):
+def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_samples=False, cn_posterior=False):
     from .sampling import SUMMARY_STATS
     res = dict()
     res['h'] = f[_HDR:_HDR + M].copy()
@@ -1019,13 +1064,22 @@ def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_sampl
             st[k] = float(f[o + j])
         res['cn_sample_agreement'] = f[o + 6:o + 6 + N * M].reshape(N, M).copy()
         res['cn_state_agreement'] = f[o + 6 + N * M:o + 6 + N * M + N].copy()
+    if cn_posterior:
+        from . import posteriors
+        o = len(f) - _posterior_len(N, M, True)
+        for j, k in enumerate(posteriors.SUMMARY_STATS):
+            st[k] = float(f[o + j])
+        o += 2
+        for k, shape in _posterior_fields(N, M):
+            n = int(np.prod(shape))
+            res[k] = f[o:o + n].reshape(shape).copy(); o += n
     res['stats'] = st
     return res
 
 
 def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clones=3, num_em_iter=5, num_update_iter=5,
                              device=None, kernel_module=None, seeds=None, quiet=True, groups=2, num_cn_samples=0, cn_sample_seed=0,
-                             **model_kwargs):
+                             cn_posterior_summary=False, **model_kwargs):
     """Fit all restarts across the ranks of the default torch.distributed group.
 
     Every rank holds the (small, read-only) experiment; rank g fits restarts
@@ -1034,6 +1088,8 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
     analysis/pipeline.py:289-291).  Works on one process without torch.distributed.
     num_cn_samples > 0: every result also summarises that many posterior samples (restart i's stream:
     restart_seed(cn_sample_seed, i)), and the records carry the summary.
+    cn_posterior_summary: every result also carries the exact posterior summaries of posteriors.COMPACT_ARRAYS and
+    the two *_posterior_mean stats, and the records grow by them.
     """
     import torch
     import torch.distributed as dist
@@ -1054,13 +1110,26 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
         local = rs.results()
         if num_cn_samples > 0:
             add_cn_sample_summaries(rs, local, experiment, num_cn_samples, cn_sample_seed, mine)
+        if cn_posterior_summary:
+            add_posterior_summaries(rs, local, experiment)
         param_names = list(rs.models[0].likelihood_params)
         rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     if param_names is None:
         nc = model_kwargs.get('normal_contamination', True)
         param_names = ['negbin_r_0', 'negbin_r_1', 'betabin_M_0', 'betabin_M_1'] + (
             [] if nc else ['negbin_hdel_mu', 'negbin_hdel_r_0', 'negbin_hdel_r_1', 'betabin_loh_p', 'betabin_loh_M_0', 'betabin_loh_M_1'])
-    return gather_result_records(local, experiment, init_params, num_clones, param_names, device=device, cn_samples=num_cn_samples > 0)
+    return gather_result_records(local, experiment, init_params, num_clones, param_names, device=device, cn_samples=num_cn_samples > 0,
+                                 cn_posterior=bool(cn_posterior_summary))
+
+
+def add_posterior_summaries(rs, results, experiment):
+    """Add the exact posterior summary of every restart of `rs` (a RestartSet / RestartGroups; one device call per
+    batch) to results[r] (posteriors.add_posterior_summary); cn_posterior_prob is taken at results[r]['cn']."""
+    from .posteriors import add_posterior_summary
+    summaries = rs.posterior_summary(cn=[res['cn'] for res in results])
+    for res, s in zip(results, summaries):
+        add_posterior_summary(res, s, experiment.l)
+    return results
 
 
 def add_cn_sample_summaries(rs, results, experiment, num_samples, seed, init_ids):
@@ -1073,7 +1142,8 @@ def add_cn_sample_summaries(rs, results, experiment, num_samples, seed, init_ids
     return results
 
 
-def gather_result_records(local, experiment, init_params, num_clones, param_names, device=None, timing=None, local_ids=None, cn_samples=False):
+def gather_result_records(local, experiment, init_params, num_clones, param_names, device=None, timing=None, local_ids=None, cn_samples=False,
+                          cn_posterior=False):
     """The one collective of the path: every rank contributes the fixed-size records of the restarts
     it fitted (`local`, in the order of shard_indices) -- one float64 record (ELBO, h, parameters, outlier
     probabilities, failure code) and one int8 record (cn, brk_cn, masks) per restart -- and every rank gets the
@@ -1102,11 +1172,11 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
             per_rank = int(cnt_.item())
     if len(local) > per_rank:
         raise ValueError('gather_result_records: %d local results for a share of %d (pass local_ids for shares that are not shard_indices\')' % (len(local), per_rank))
-    flen = _HDR + M + nparams + 4 * N + _sample_len(N, M, cn_samples)
+    flen = _HDR + M + nparams + 4 * N + _sample_len(N, M, cn_samples) + _posterior_len(N, M, cn_posterior)
     ilen = N * M * 2 + K * M + 2 * N
     fbuf = np.full((per_rank, flen), np.nan); ibuf = np.zeros((per_rank, ilen), dtype=np.int8)
     for j, res in enumerate(local):
-        fbuf[j], ibuf[j] = _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples)
+        fbuf[j], ibuf[j] = _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples, cn_posterior)
     if local_ids is not None:
         ids_t = np.full((per_rank,), -1, dtype=np.int64); ids_t[:len(local_ids)] = local_ids
     t0 = time.perf_counter()
@@ -1138,7 +1208,7 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
     for g in range(world):
         ids_g = shard_indices(len(init_params), world, g) if ids_all is None else [int(i) for i in ids_all[g] if i >= 0]
         for j, i in enumerate(ids_g):
-            results[i] = _unpack(fall[g][j], iall[g][j], N, M, K, nparams, brk_ids, param_names, init_params[i], cn_samples)
+            results[i] = _unpack(fall[g][j], iall[g][j], N, M, K, nparams, brk_ids, param_names, init_params[i], cn_samples, cn_posterior)
     return results
 
 

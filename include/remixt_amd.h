@@ -359,6 +359,24 @@ int rmx_sample_cn(rmx_batch *b, int32_t r0, int32_t nr, int32_t num_samples, con
 int rmx_posterior_summary(rmx_batch *b, int32_t r0, int32_t nr, int32_t Q, const double *weights, const int16_t *states,
                           double *proj_out, double *stats_out, int16_t *argmax_out);
 
+/* -- region event probabilities (no reference counterpart) ------------------- */
+/* log-probabilities, under the structured posterior of the last update_p_cn, of path events over runs of model segments
+ * of restarts r0 .. r0+nr-1.  Query i = queries[i][0..3] = (first segment a, last segment b, mask index or
+ * -1, label index or -1) asks for log P(c_n in mask at every n in [a, b] with constrain[n] != 0, and
+ * label(c_n) == label(c_n+1) at every adjacency inside [a, b]).  The model is not modified.
+ *   queries   int32 [nq][4]; a <= b, both in [0, N) and in the same chain
+ *   masks     uint8 [C][nmask][S], non-zero = allowed state, one table per state class; NULL with nmask = 0
+ *   labels    int16 [C][nlabel][S], one table per state class; NULL with nlabel = 0
+ *   constrain uint8 [N]: whether a mask binds at the segment; NULL = everywhere
+ *   logp_out  [nr][nq]; -inf for an impossible event
+ * A (restart, query) result is bit-identical in any restart range and any batch of queries.  RMX_EARG, with nothing
+ * launched: a bad range, a query with a > b, an end outside [0, N), ends in different chains, a mask or label index out
+ * of range.  RMX_EVALUE with the restarts listed by rmx_last_error_restarts: a restart has had no update_p_cn.
+ * RMX_EASSERT with the restarts listed: a backward step met a zero or non-finite normaliser under positive mass (that
+ * query's result is NaN).  RMX_EUNSUPPORTED: more than 1024 states. */
+int rmx_region_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
+                    int32_t nlabel, const int16_t *labels, const uint8_t *constrain, double *logp_out);
+
 /* -- module-level functions on caller-supplied dense inputs ----------------- */
 /* sum_product (:1213-1246): f [N][S], T [N-1][S][S] -> alphas, betas [N][S] */
 int rmx_sum_product(const double *f, const double *T, double *alphas, double *betas,

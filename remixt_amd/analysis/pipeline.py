@@ -8,7 +8,7 @@ import numpy as np
 
 from .. import defaults, posteriors, sampling
 from ..cn_model import BreakpointModel
-from ..restarts import RestartSet, add_cn_sample_summaries, add_posterior_summaries, collect_fit_results, fit_restarts_distributed, select_optimal  # noqa: F401
+from ..restarts import RestartSet, add_cn_sample_summaries, add_posterior_summaries, add_region_events, collect_fit_results, fit_restarts_distributed, select_optimal  # noqa: F401
 
 
 def _model_kwargs(experiment, config):
@@ -67,6 +67,10 @@ def fit(experiment, init_params, config, device=0, quiet=False, init_id=0):
         states = posteriors.states_in_model_order(res['cn'], b, model.seg_fwd_remap)[None]
         s = posteriors.batch_summaries(b, model.model._r, 1, states=states)[0]
         posteriors.add_posterior_summary(res, dict((k, v[model.seg_fwd_remap]) for k, v in s.items()), experiment.l)
+    cn_regions = defaults.get_param(config, 'cn_regions')
+    if cn_regions is not None:
+        names, regions = posteriors.parse_regions(cn_regions)
+        posteriors.add_region_events(res, names, model.region_events(regions))
     return res
 
 
@@ -112,6 +116,8 @@ def fit_restarts(experiment, init_params_by_id, config, device=0, quiet=True, se
         add_cn_sample_summaries(rs, results, experiment, num_samples, defaults.get_param(config, 'cn_sample_seed'), ids)
     if defaults.get_param(config, 'cn_posterior_summary'):
         add_posterior_summaries(rs, results, experiment)
+    if defaults.get_param(config, 'cn_regions') is not None:
+        add_region_events(rs, results, defaults.get_param(config, 'cn_regions'))
     out = dict(zip(ids, results))
     rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     return out
@@ -255,6 +261,11 @@ def store_fit_results(store, experiment, fit_results, key_prefix):
         for k in posteriors.COMPACT_ARRAYS:
             v = np.asarray(fit_results[k])
             store[key_prefix + '/' + k] = pd.DataFrame(v) if v.ndim == 2 else pd.Series(v)
+    if 'region_events' in fit_results:            # (config cn_regions)
+        ev = fit_results['region_events']
+        store[key_prefix + '/region_names'] = pd.Series(list(ev['names']))
+        for k in posteriors.REGION_ARRAYS:
+            store[key_prefix + '/' + k] = pd.Series(np.asarray(ev[k]))
 
 
 def store_optimal_solution(stats, store, config):

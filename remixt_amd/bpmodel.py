@@ -578,6 +578,53 @@ class RemixtBatch(object):
             stats.ctypes.data_as(_dp) if stats is not None else _dp(), amax.ctypes.data_as(i16p) if amax is not None else i16p()))
         return proj, stats, amax
 
+    def region_logprob_raw(self, r0, nr, queries, masks=None, labels=None, constrain=None):
+        """log-probabilities (nr, nq) of path events over runs of model segments under the structured posterior of the
+        last update_p_cn of restarts r0 .. r0+nr-1 (rmx_region_prob).  queries int (nq, 4): first segment, last segment
+        (both of one chain), mask index or -1, label index or -1; masks (C, nmask, S), non-zero = allowed state; labels
+        int (C, nlabel, S); constrain (N,), whether a mask binds at the segment (None: everywhere).  A query asks for
+        log P(state in mask at every constrained segment of the run, and equal labels across every adjacency of the
+        run); -inf for an impossible event."""
+        r0, nr = int(r0), int(nr)
+        N, S, C_ = self.num_segments, self.num_cn_states, self.cn_classes.shape[0]
+        q = np.asarray(queries)
+        if q.ndim != 2 or q.shape[1] != 4:
+            raise ValueError('queries must have shape (nq, 4)')
+        if q.size and (q.min() < -2 ** 31 or q.max() >= 2 ** 31):
+            raise ValueError('query entry out of range')
+        q = np.ascontiguousarray(q, dtype=np.int32)
+        u8p, i16p = C.POINTER(C.c_uint8), C.POINTER(C.c_int16)
+        nmask, mp, nlabel, lp, cp = 0, u8p(), 0, i16p(), u8p()
+        if masks is not None:
+            mk = np.asarray(masks)
+            if mk.ndim != 3 or mk.shape[0] != C_ or mk.shape[2] != S:
+                raise ValueError('masks must have shape (num_classes, nmask, num_cn_states)')
+            mk = np.ascontiguousarray(mk != 0, dtype=np.uint8)
+            nmask = mk.shape[1]
+            if nmask:
+                mp = mk.ctypes.data_as(u8p)
+        if labels is not None:
+            lb = np.asarray(labels)
+            if lb.ndim != 3 or lb.shape[0] != C_ or lb.shape[2] != S:
+                raise ValueError('labels must have shape (num_classes, nlabel, num_cn_states)')
+            if lb.size and (lb.min() < -32768 or lb.max() > 32767):
+                raise ValueError('label out of the int16 range')
+            lb = np.ascontiguousarray(lb, dtype=np.int16)
+            nlabel = lb.shape[1]
+            if nlabel:
+                lp = lb.ctypes.data_as(i16p)
+        if constrain is not None:
+            cs = np.asarray(constrain)
+            if cs.shape != (N,):
+                raise ValueError('constrain must have shape (num_segments,)')
+            cs = np.ascontiguousarray(cs != 0, dtype=np.uint8)
+            cp = cs.ctypes.data_as(u8p)
+        out = np.zeros((max(nr, 0), q.shape[0]), dtype=np.float64)
+        obuf, qbuf = (out if out.size else np.zeros(1)), (q if q.size else np.zeros(4, dtype=np.int32))
+        self._ck(self._lib.rmx_region_prob(self._handle, r0, nr, q.shape[0], qbuf.ctypes.data_as(C.POINTER(C.c_int32)), nmask, mp, nlabel, lp, cp,
+                                           obuf.ctypes.data_as(_dp)))
+        return out
+
     # -- measurement ------------------------------------------------------------
     def timer_start(self):
         self._ck(self._lib.rmx_timer_start(self._handle))
@@ -800,6 +847,10 @@ class RemixtModel(object):
         """RemixtBatch.posterior_summary_raw of this model: (proj (N, Q), stats (N, 3), argmax (N,)), None where not requested."""
         out = self._batch.posterior_summary_raw(self._r, 1, weights=weights, states=states, want_stats=want_stats, want_argmax=want_argmax)
         return tuple(None if a is None else a[0] for a in out)
+
+    def region_logprob(self, queries, masks=None, labels=None, constrain=None):
+        """RemixtBatch.region_logprob_raw of this model: log-probabilities (nq,)."""
+        return self._batch.region_logprob_raw(self._r, 1, queries, masks, labels, constrain)[0]
 
     def posterior_project(self, weights):
         """posterior_marginals @ weights[class of the segment] -> (N, Q), on the device: weights (C, S, Q) or (S, Q), Q <= 256."""

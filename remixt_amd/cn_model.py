@@ -734,6 +734,29 @@ class BreakpointModel(object):
         s = posteriors.batch_summaries(b, self.model._r, 1, states=states, marginals=marginals)[0]
         return dict((k, v[self.seg_fwd_remap]) for k, v in s.items())
 
+    def _region_batch(self):
+        if not hasattr(self.model, 'region_logprob'):
+            raise NotImplementedError('kernel module %s has no region event probabilities' % getattr(self._kernel_module(), '__name__', '?'))
+        return self.model._batch, self.model._r
+
+    def region_events(self, regions):
+        """Exact probabilities, under the structured posterior of the last variational update, of copy-number events over
+        regions: regions is a list of (first, last) experiment segment indices; a dict of arrays (len(regions),):
+        p_all_loh, p_any_loh, p_all_hdel, p_any_hdel, p_any_subclonal (over the region's segments), p_no_change (the same
+        copy-number state along the whole region) and p_no_total_change (the same per-clone totals).  A region that spans
+        chain ends is the conjunction over its chains."""
+        from . import posteriors
+        b, r = self._region_batch()
+        out = posteriors.batch_region_events(b, r, 1, regions, self.seg_fwd_remap, self.seg_is_original, self.is_telomere)
+        return dict((k, v[0]) for k, v in out.items())
+
+    def cn_change_prob(self):
+        """(N - 1,): the posterior probability that the copy-number state changes between experiment segments n and n + 1
+        (1 - p_no_change of the region [n, n + 1]); NaN where no reference adjacency joins them."""
+        from . import posteriors
+        b, r = self._region_batch()
+        return posteriors.batch_change_prob(b, r, 1, self.seg_fwd_remap, self.seg_is_original, self.is_telomere)[0]
+
     def breakpoint_prob(self):
         return dict(zip(self.breakpoints, np.asarray(self.model.p_breakpoint)))
 

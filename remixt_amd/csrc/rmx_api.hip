@@ -39,12 +39,12 @@ static inline long long now_ns() { return std::chrono::duration_cast<std::chrono
 enum KernelId {
     KID_STATE_TABLES = 0, KID_SEG_CONST, KID_FRAMELOGPROB, KID_FB, KID_MARGINALS, KID_MARGINALS_AB, KID_OUTLIER_TOTAL,
     KID_OUTLIER_ALLELE, KID_ALLELE_SWAP, KID_BRK_LUT, KID_PAIRWISE, KID_BRK_UPDATE, KID_ELBO_SEG, KID_ELBO_FINAL,
-    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_POST_SUMMARY, KID_COUNT
+    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_POST_SUMMARY, KID_REGION, KID_COUNT
 };
 static const char *kKernelNames[KID_COUNT] = {
     "k_state_tables", "k_seg_const", "k_framelogprob", "k_fb", "k_marginals<true>", "k_marginals<false>", "k_update_outlier_total",
     "k_update_outlier_allele", "k_update_allele_swap", "k_brk_lut", "k_pairwise", "k_brk_update", "k_elbo_seg", "k_elbo_final",
-    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn", "k_posterior_summary"};
+    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn", "k_posterior_summary", "k_region_prob"};
 
 struct ProfRec { int id; hipEvent_t a, b; };
 
@@ -161,6 +161,7 @@ struct rmx_batch {
     std::vector<int64_t> last_path; int vit_cap = 0; size_t bp_cap = 0;
     int16_t *d_samp = nullptr; size_t samp_cap = 0; uint64_t *d_seeds = nullptr; uint32_t *d_sflags = nullptr;   // rmx_sample_cn: paths of a chunk of samples, seeds, flags [R]
     double *d_psum = nullptr; size_t psum_cap = 0; double *d_psw = nullptr; size_t psw_cap = 0;   // rmx_posterior_summary: output staging of a chunk (doubles), weights [C][S][Q]
+    double *d_rgn = nullptr; size_t rgn_cap = 0; uint8_t *d_rgt = nullptr; size_t rgt_cap = 0; uint32_t *d_rflags = nullptr;   // rmx_region_prob: outputs + queries of a chunk (doubles), label / mask / constrain tables (bytes), flags [R]
     uint16_t *d_comp = nullptr; int32_t *d_ends = nullptr; size_t comp_cap = 0, ends_cap = 0; int last_traceback = 0;      // parallel trace-back: composed maps [nr][NBLK][S], block end states [nr][NBLK]
     uint8_t *d_vit_code = nullptr; double *d_vit_val = nullptr; bool vit_code_ok = false, vit_mul_ok = false;   // 8-bit codes of T(i, o) of class 0 + their values (k_viterbi_code)
     // FB launch configuration
@@ -3134,6 +3135,101 @@ int rmx_posterior_summary(rmx_batch *b, int32_t r0, int32_t nr, int32_t Q, const
         }
     }
     HIPCHK(hipStreamSynchronize(b->stream));
+    return RMX_OK;
+}
+
+// Region event probabilities (k_region_prob) of restarts r0 .. r0+nr-1 from what the last update_p_cn left on the device: the
+// fa plane and transition snapshot rmx_sample_cn reads, and the marginals d.post.  Everything a query could index out of
+// range is checked here, before anything is queued: the kernel trusts the segment runs and the table indices.  Queries and
+// outputs go through one device buffer of at most 64 MiB, chunked over queries; one workgroup computes a (restart, query)
+// on its own, so a result depends on neither the restart range nor the chunking.
+int rmx_region_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
+                    int32_t nlabel, const int16_t *labels, const uint8_t *constrain, double *logp_out) { BIND(b);
+    if (!b || r0 < 0 || nr < 1 || (int64_t)r0 + nr > b->R) return fail(RMX_EARG, "bad restart range");
+    if (nq < 1 || !queries || !logp_out) return fail(RMX_EARG, "region_prob: no queries or no output");
+    if (nmask < 0 || nlabel < 0 || (nmask > 0 && !masks) || (nlabel > 0 && !labels)) return fail(RMX_EARG, "region_prob: bad mask or label tables");
+    const Dev &d = b->d;
+    const int N = d.N, S = d.S, C_ = d.C;
+    if (S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "region_prob: more than 1024 states");
+    {
+        // chain of a segment = the number of chain ends (tclass < 0) before it
+        std::vector<int32_t> chain(N);
+        int32_t c = 0;
+        for (int n = 0; n < N; n++) { chain[n] = c; if (b->tclass[n] < 0) c++; }
+        for (int i = 0; i < nq; i++) {
+            const int32_t *qq = queries + 4 * (size_t)i;
+            if (qq[0] < 0 || qq[1] >= N || qq[0] > qq[1]) return fail(RMX_EARG, "region_prob: a query needs 0 <= first <= last < num_segments");
+            if (chain[qq[0]] != chain[qq[1]]) return fail(RMX_EARG, "region_prob: a query crosses a chain end");
+            if (qq[2] < -1 || qq[2] >= nmask) return fail(RMX_EARG, "region_prob: mask index out of range");
+            if (qq[3] < -1 || qq[3] >= nlabel) return fail(RMX_EARG, "region_prob: label index out of range");
+        }
+    }
+    // no update_p_cn yet: there is no posterior to evaluate (reported as rmx_sample_cn does)
+    g_err_restarts.clear();
+    for (int r = r0; r < r0 + nr; r++) if (!b->lt_valid[r]) g_err_restarts.push_back(r);
+    if (!g_err_restarts.empty()) {
+        char buf[160]; snprintf(buf, sizeof buf, "region_prob before update_p_cn (restart %d)", g_err_restarts[0]);
+        return fail_flagged(RMX_EVALUE, buf);
+    }
+    int rc;
+    if (!b->d_rflags && (rc = dalloc(b, &b->d_rflags, b->R))) return rc;
+    // tables: labels (2-byte entries first), masks, constrain
+    const size_t lab_bytes = (size_t)C_ * nlabel * S * sizeof(int16_t), mask_bytes = (size_t)C_ * nmask * S, tab_bytes = lab_bytes + mask_bytes + (constrain ? (size_t)N : 0);
+    if (b->rgt_cap < tab_bytes) {
+        dfree(b, b->d_rgt); b->d_rgt = nullptr; b->rgt_cap = 0;
+        if ((rc = dalloc(b, &b->d_rgt, tab_bytes))) return rc;
+        b->rgt_cap = tab_bytes;
+    }
+    if (lab_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt, labels, lab_bytes, hipMemcpyHostToDevice, b->stream));
+    if (mask_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes, masks, mask_bytes, hipMemcpyHostToDevice, b->stream));
+    if (constrain) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes + mask_bytes, constrain, (size_t)N, hipMemcpyHostToDevice, b->stream));
+    // staging in doubles: outputs [nrc][qc], then the chunk's queries [qc][4] int32
+    const size_t budget = (size_t)64 << 20;
+    const int nrc = std::min(nr, 65535);
+    const size_t qc = std::max<size_t>(1, std::min<size_t>((size_t)nq, budget / ((size_t)nrc * 8 + 16)));
+    const size_t need = (size_t)nrc * qc + 2 * qc;
+    if (b->rgn_cap < need) {
+        dfree(b, b->d_rgn); b->d_rgn = nullptr; b->rgn_cap = 0;
+        if ((rc = dalloc(b, &b->d_rgn, need))) return rc;
+        b->rgn_cap = need;
+    }
+    double *dout = b->d_rgn;
+    int32_t *dq = (int32_t *)(b->d_rgn + (size_t)nrc * qc);
+    HIPCHK(hipMemsetAsync(b->d_rflags + r0, 0, sizeof(uint32_t) * nr, b->stream));
+    RgnArgs ra;
+    ra.queries = dq; ra.labels = (const int16_t *)b->d_rgt; ra.masks = b->d_rgt + lab_bytes; ra.constrain = constrain ? b->d_rgt + lab_bytes + mask_bytes : nullptr;
+    ra.nmask = nmask; ra.nlabel = nlabel; ra.pad_ = 0;
+    for (size_t q0 = 0; q0 < (size_t)nq; q0 += qc) {
+        const size_t nqc = std::min(qc, (size_t)nq - q0);
+        ra.nq = (int)nqc;
+        HIPCHK(hipMemcpyAsync(dq, queries + 4 * q0, nqc * 16, hipMemcpyHostToDevice, b->stream));
+        for (int rb = 0; rb < nr; rb += nrc) {
+            const int nrr = std::min(nrc, nr - rb);
+            // runs of restarts whose snapshot was taken under the same transition model (its plain tables)
+            for (int i = rb; i < rb + nrr;) {
+                int j = i; while (j < rb + nrr && b->lt_model[r0 + j] == b->lt_model[r0 + i]) j++;
+                const int model = b->lt_model[r0 + i];
+                const Dev dv = dev_for_model(b, model);
+                {
+                    ProfScope ps(b, KID_REGION);
+                    hipLaunchKernelGGL(k_region_prob, dim3((unsigned)nqc, j - i), dim3(RGN_NT), 0, b->stream, dv, r0 + i, model == d.tmodel ? 1 : 0, ra,
+                                       dout + (size_t)(i - rb) * nqc, b->d_rflags);
+                    HIPCHK(hipGetLastError());
+                }
+                i = j;
+            }
+            // device [nrr][nqc] -> host rows (rb .. rb+nrr)[q0 .. q0+nqc)
+            HIPCHK(hipMemcpy2DAsync(logp_out + (size_t)rb * nq + q0, (size_t)nq * 8, dout, nqc * 8, nqc * 8, nrr, hipMemcpyDeviceToHost, b->stream));
+        }
+    }
+    uint32_t *e = b->h_err;
+    HIPCHK(hipMemcpyAsync(e, b->d_rflags + r0, sizeof(uint32_t) * nr, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int i = 0; i < nr; i++) if (e[i]) g_err_restarts.push_back(r0 + i);
+    if (!g_err_restarts.empty()) {
+        char buf[160]; snprintf(buf, sizeof buf, "region_prob: a backward step has a zero or non-finite normaliser (restart %d)", g_err_restarts[0]);
+        return fail_flagged(RMX_EASSERT, buf);
+    }
     return RMX_OK;
 }
 

@@ -5536,3 +5536,191 @@ __global__ __launch_bounds__(64) void k_posterior_summary(Dev d, int r0, int nbe
         }
     }
 }
+
+// =============================================================================
+// Region event probabilities: log P(E) under the structured posterior of the last update_p_cn, for the event E of a
+// query over the model segments [a, b] of one chain: c_n in the mask's states at every n of the run with constrain[n]
+// set, and label(c_n) == label(c_n+1) at every adjacency of the run (either part optional).  The chain is Markov under
+// that posterior with the backward kernel k_sample_cn draws from, q(c_n = s | c_n+1 = s') = fa_n(s) W_n(s, s') / D_n(s'),
+// D_n(s') = sum_s fa_n(s) W_n(s, s'), and marginal post_n; so with g_b(s) = [mask] post_b(s),
+//   g_n(s) = [mask] fa_n(s) sum_s' [label(s) == label(s')] W_n(s, s') g_n+1(s') / D_n(s'),   P(E) = sum_s g_a(s).
+// g is divided by its sum after every step and the logarithms of the sums are added up.  Nothing of the model is written.
+// One workgroup of 256 threads per (restart, query); a step is two passes over the S x S weights, D then g, both with the
+// lanes along the dimension the weights are contiguous in (no LDS tile of the weights: each is used once per pass):
+//   Wb (plain adjacency, the snapshot's model is the current one): row s' is contiguous in s.  D(s') for the states s' with
+//     g(s') > 0 (compacted in state order by a ballot) takes 16 lanes per s' striding s and a fixed butterfly; g(s) then has
+//     the thread own s and walk the compacted s', every load again a run of consecutive s.
+//   exp(trans_value) (breakend adjacency, or the plain table Tval of the other transition model): contiguous in s', so the
+//     two mappings swap: the thread owns s' in the D pass, 16 lanes per s stride s' in the g pass.
+// Every sum has one order, fixed by the state count alone: a (restart, query) result does not depend on the launch.
+// Only columns s < S of fa / post are read.  A D(s') that is 0 or not finite under g(s') > 0, or a sum of g that is not a
+// finite number >= 0, sets RGN_ERR_DENOM in flags[r] and gives NaN; a sum of exactly 0 gives -inf.
+// grid (queries, restarts), block RGN_NT; out[ri * nq + query].
+// =============================================================================
+#define RGN_NT 256
+#define RGN_GL 16             // lanes per output state in the reducing pass
+#define RGN_MAXS 1024
+#define RGN_ERR_DENOM 1u
+struct RgnArgs {
+    const int32_t *queries;   // [nq][4]: a, b, mask index or -1, label index or -1
+    const uint8_t *masks;     // [C][nmask][S]
+    const int16_t *labels;    // [C][nlabel][S]
+    const uint8_t *constrain; // [N] or null (every segment binds)
+    int nq, nmask, nlabel, pad_;
+};
+// sum over the workgroup in a fixed order; every thread gets it (the barriers also publish what the callers wrote to LDS)
+__device__ inline double rgn_block_sum(double v, double *red) {
+    v = group_sum(v, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.;
+#pragma unroll
+    for (int i = 0; i < RGN_NT / 64; i++) t += red[i];
+    return t;
+}
+__global__ __launch_bounds__(RGN_NT) void k_region_prob(Dev d, int r0, int use_wb, RgnArgs q, double *out, uint32_t *flags) {
+    __shared__ double g[RGN_MAXS], h[RGN_MAXS], fas[RGN_MAXS];
+    __shared__ double red[RGN_NT / 64];
+    __shared__ int16_t lab[2][RGN_MAXS], idx[RGN_MAXS];
+    __shared__ int nact, s_bad;
+    const int qi = blockIdx.x, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x, lane = tid & 63;
+    const int grp = tid / RGN_GL, gl = tid % RGN_GL;
+    const int S = d.S;
+    const int a = q.queries[4 * qi], b = q.queries[4 * qi + 1], mi = q.queries[4 * qi + 2], li = q.queries[4 * qi + 3];
+    if (tid == 0) s_bad = 0;
+    int cur = 0;              // lab[cur]: the labels of segment n + 1
+    double logp = 0.;
+    bool failed = false;
+    // ---- start: g_b = [mask] post_b ---------------------------------------------------------------------
+    {
+        const int cls = d.seg_class[b];
+        const double *post = d.post + rs_off(d, r, b);
+        const uint8_t *mk = (mi >= 0 && (!q.constrain || q.constrain[b])) ? q.masks + ((size_t)cls * q.nmask + mi) * S : nullptr;
+        const int16_t *lb = li >= 0 ? q.labels + ((size_t)cls * q.nlabel + li) * S : nullptr;
+        double part = 0.;
+        for (int s = tid; s < S; s += RGN_NT) {
+            const double v = (!mk || mk[s]) ? post[s] : 0.;
+            g[s] = v; part += v;
+            if (lb) lab[cur][s] = lb[s];
+        }
+        const double Z = rgn_block_sum(part, red);
+        if (!(Z >= 0. && Z < INFINITY)) failed = true;
+        else if (Z == 0.) logp = -INFINITY;
+        else {
+            logp = log(Z);
+            for (int s = tid; s < S; s += RGN_NT) g[s] = g[s] / Z;
+        }
+    }
+    for (int n = b - 1; n >= a && !failed && logp > -INFINITY; n--) {
+        const int tc = d.tclass[n], bs = d.brk_slot[n];      // (tc >= 0: the host checked that the run lies in one chain)
+        const int cls = d.seg_class[n];
+        const double *fa = d.fa + rs_off(d, r, n);
+        const uint8_t *mk = (mi >= 0 && (!q.constrain || q.constrain[n])) ? q.masks + ((size_t)cls * q.nmask + mi) * S : nullptr;
+        const int16_t *lb = li >= 0 ? q.labels + ((size_t)cls * q.nlabel + li) * S : nullptr;
+        const int16_t *lab1 = lab[cur];
+        int16_t *lab0 = lab[cur ^ 1];
+        for (int s = tid; s < S; s += RGN_NT) {
+            fas[s] = fa[s];
+            if (lb) lab0[s] = lb[s];
+        }
+        __syncthreads();
+        if (bs < 0 && use_wb) {
+            const double *Wt = d.Wb + (size_t)tc * S * S;
+            // the states s' with g(s') > 0, in state order
+            if (tid < 64) {
+                int cnt = 0;
+                for (int base = 0; base < S; base += 64) {
+                    const int s = base + lane;
+                    const bool act = s < S && g[s] > 0.;
+                    const unsigned long long m = __ballot(act);
+                    if (act) idx[cnt + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = (int16_t)s;
+                    cnt += __builtin_popcountll(m);
+                }
+                if (lane == 0) nact = cnt;
+            }
+            __syncthreads();
+            const int na = nact;
+            // D(s') and h(s') = g(s') / D(s'): 16 lanes per s'
+            for (int j0 = 0; j0 < na; j0 += RGN_NT / RGN_GL) {
+                const int j = j0 + grp;
+                const bool ok = j < na;
+                const int sp = ok ? idx[j] : 0;
+                double p = 0.;
+                if (ok) {
+                    const double *wr = Wt + (size_t)sp * S;
+                    for (int s = gl; s < S; s += RGN_GL) p = fma(fas[s], wr[s], p);
+                }
+                const double D = group_sum(p, RGN_GL);
+                if (ok && gl == 0) {
+                    if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                    h[j] = g[sp] / D;
+                }
+            }
+            __syncthreads();
+            // g(s): the thread owns s
+            for (int s = tid; s < S; s += RGN_NT) {
+                double acc = 0.;
+                if (!mk || mk[s]) {
+                    const int ls = lb ? lab0[s] : 0;
+                    const double *wc = Wt + s;
+#pragma unroll 4
+                    for (int j = 0; j < na; j++) {
+                        const int sp = idx[j];
+                        if (!lb || lab1[sp] == ls) acc = fma(wc[(size_t)sp * S], h[j], acc);      // (off-label weights are not loaded)
+                    }
+                    acc *= fas[s];
+                }
+                g[s] = acc;
+            }
+        } else {
+            const double *pd = bs >= 0 ? d.pd_lt + ((size_t)r * d.NBE + bs) * d.M * d.D : nullptr;
+            // D(s') and h(s'): the thread owns s'
+            for (int sp = tid; sp < S; sp += RGN_NT) {
+                const double gv = g[sp];
+                double hv = 0.;
+                if (gv > 0.) {
+                    double D = 0.;
+                    for (int s = 0; s < S; s++) {
+                        const double f = fas[s];
+                        if (f != 0.) D = fma(f, exp(trans_value(d, n, s, sp, pd)), D);
+                    }
+                    if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                    hv = gv / D;
+                }
+                h[sp] = hv;
+            }
+            __syncthreads();
+            // g(s): 16 lanes per s
+            for (int s0 = 0; s0 < S; s0 += RGN_NT / RGN_GL) {
+                const int s = s0 + grp;
+                const bool ok = s < S && (!mk || mk[s]) && fas[s] != 0.;
+                double p = 0.;
+                if (ok) {
+                    const int ls = lb ? lab0[s] : 0;
+                    for (int sp = gl; sp < S; sp += RGN_GL) {
+                        const double hv = h[sp];
+                        if (hv != 0. && (!lb || lab1[sp] == ls)) p = fma(exp(trans_value(d, n, s, sp, pd)), hv, p);
+                    }
+                }
+                const double sum = group_sum(p, RGN_GL);
+                if (s < S && gl == 0) g[s] = ok ? sum * fas[s] : 0.;
+            }
+        }
+        __syncthreads();
+        double part = 0.;
+        for (int s = tid; s < S; s += RGN_NT) part += g[s];
+        const double Z = rgn_block_sum(part, red);
+        if (s_bad || !(Z >= 0. && Z < INFINITY)) failed = true;
+        else if (Z == 0.) logp = -INFINITY;
+        else {
+            logp += log(Z);
+            for (int s = tid; s < S; s += RGN_NT) g[s] = g[s] / Z;
+        }
+        cur ^= 1;
+    }
+    if (tid == 0) {
+        if (failed) atomicOr(&flags[r], RGN_ERR_DENOM);
+        out[(size_t)ri * q.nq + qi] = failed ? __builtin_nan("") : logp;
+    }
+}

@@ -26,6 +26,11 @@ cn_sample_seed = 0
 # True adds cn_posterior_prob / _max / _entropy, p_subclonal, p_loh, p_hdel, total_cn_mean, total_cn_sd and the stats
 # ploidy_posterior_mean / proportion_divergent_posterior_mean (remixt_amd/posteriors.py)
 cn_posterior_summary = False
+# (no reference counterpart) exact posterior probabilities of copy-number events over regions behind every fit result:
+# None = none (results unchanged); a list of (name, first, last) experiment segment intervals adds `region_events` -- the
+# names and p_all_loh, p_any_loh, p_all_hdel, p_any_hdel, p_any_subclonal, p_no_change, p_no_total_change per region
+# (remixt_amd/posteriors.py)
+cn_regions = None
 
 
 def get_param(config, name):

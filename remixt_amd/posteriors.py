@@ -152,3 +152,153 @@ def add_posterior_summary(res, summary, l):
         res[k] = summary[k]
     res['stats'].update(summary_stats(summary, l))
     return res
+
+
+# ---- probabilities of path events over regions (rmx_region_prob) ---------------------------------------
+MASK_NAMES = ('loh', 'not_loh', 'hdel', 'not_hdel', 'subclonal', 'not_subclonal')
+LABEL_NAMES = ('state', 'total', 'unphased')
+# the arrays of region_events: name -> (mask or None, label or None, complement).  The "any" events are the complements
+# of "all segments are not ..."
+REGION_EVENTS = (('p_all_loh', 'loh', None, False), ('p_any_loh', 'not_loh', None, True), ('p_all_hdel', 'hdel', None, False),
+                 ('p_any_hdel', 'not_hdel', None, True), ('p_any_subclonal', 'not_subclonal', None, True),
+                 ('p_no_change', None, 'state', False), ('p_no_total_change', None, 'total', False))
+REGION_ARRAYS = tuple(e[0] for e in REGION_EVENTS)
+
+
+def _ranks(keys):
+    """Equal keys (rows of the last axis) -> equal small integers, over the whole array."""
+    flat = keys.reshape(-1, keys.shape[-1])
+    _, inv = np.unique(flat, axis=0, return_inverse=True)
+    inv = np.asarray(inv).reshape(keys.shape[:-1])
+    if inv.size and inv.max() > 32767:
+        raise ValueError('too many distinct labels for int16')
+    return inv.astype(np.int16)
+
+
+def event_tables(cn_classes):
+    """State masks and labels of the region events: (masks uint8 (C, 6, S) in MASK_NAMES order, labels int16 (C, 3, S) in
+    LABEL_NAMES order).  Masks: is_loh, is_hdel and num_alleles_subclonal > 0 as feature_matrix (bpmodel.pyx:505-507)
+    defines them, and their complements.  Labels, each over the tumour clones (state classes differ only in the normal
+    row, so equal labels across classes mean equal tumour copies): 'state' the copy numbers themselves, 'total' the
+    per-clone totals, 'unphased' the copy numbers up to a swap of the two alleles in every clone at once."""
+    cn = np.asarray(cn_classes)
+    if cn.ndim != 4 or cn.shape[3] != 2:
+        raise ValueError('cn_classes must have shape (num_classes, num_cn_states, num_clones, 2)')
+    C, S, M, _ = cn.shape
+    nas = (cn[:, :, 1:, :].max(axis=-2) != cn[:, :, 1:, :].min(axis=-2)).sum(axis=-1)
+    is_hdel = np.all(cn == 0, axis=(-2, -1))
+    is_loh = np.any(cn.sum(axis=-2) == 0, axis=-1)
+    sub = nas > 0
+    masks = np.stack([is_loh, ~is_loh, is_hdel, ~is_hdel, sub, ~sub], axis=1).astype(np.uint8)
+    tum = cn[:, :, 1:, :].astype(np.int64)                                      # (C, S, M - 1, 2)
+    flat = tum.reshape(C, S, -1)
+    swapped = tum[..., ::-1].reshape(C, S, -1)
+    # the lexicographically smaller of the two phasings
+    diff = flat != swapped
+    first = diff.argmax(axis=-1)[..., None]
+    smaller = np.take_along_axis(swapped, first, -1) < np.take_along_axis(flat, first, -1)
+    canon = np.where(smaller & diff.any(axis=-1, keepdims=True), swapped, flat)
+    labels = np.stack([_ranks(flat), _ranks(tum.sum(axis=-1)), _ranks(canon)], axis=1)
+    return np.ascontiguousarray(masks), np.ascontiguousarray(labels)
+
+
+def chains_from_telomeres(is_telomere):
+    """(chain_start, chain_end) model segment indices from the is_telomere flags: a chain ends at a telomere segment and
+    at the last segment."""
+    tel = np.asarray(is_telomere) != 0
+    end = np.flatnonzero(tel)
+    if len(tel) and (len(end) == 0 or end[-1] != len(tel) - 1):
+        end = np.append(end, len(tel) - 1)
+    start = np.concatenate([[0], end[:-1] + 1]).astype(np.int64) if len(end) else end
+    return start, end.astype(np.int64)
+
+
+def region_queries(regions, seg_fwd_remap, seg_is_original, chain_start, chain_end):
+    """Experiment-order segment intervals [i, j] (regions: (R, 2) ints, i <= j) as runs of model segments:
+    (runs int32 (P, 2), piece_region int (P,), constrain uint8 (N1,)).  The run of [i, j] is seg_fwd_remap[i] ..
+    seg_fwd_remap[j] -- the remap is monotone, so the zero-length segments inserted between i and j lie inside it -- split
+    at chain ends into pieces (piece_region: the region a piece belongs to; pieces of a region are consecutive).
+    constrain is seg_is_original: a state mask binds only real segments, while a label constraint binds every adjacency
+    of a run, the ones through a breakend's inserted segment included."""
+    reg = np.asarray(regions, dtype=np.int64).reshape(-1, 2)
+    fwd = np.asarray(seg_fwd_remap, dtype=np.int64)
+    cs, ce = np.asarray(chain_start, dtype=np.int64), np.asarray(chain_end, dtype=np.int64)
+    if len(reg) and (reg.min() < 0 or reg.max() >= len(fwd) or (reg[:, 0] > reg[:, 1]).any()):
+        raise ValueError('a region needs 0 <= first <= last < number of segments')
+    A, B = fwd[reg[:, 0]], fwd[reg[:, 1]]
+    ca, cb = np.searchsorted(ce, A, side='left'), np.searchsorted(ce, B, side='left')      # the chains of the two ends
+    npieces = cb - ca + 1
+    piece_region = np.repeat(np.arange(len(reg)), npieces)
+    k = np.arange(len(piece_region)) - np.repeat(np.cumsum(npieces) - npieces, npieces)
+    chain = ca[piece_region] + k
+    runs = np.stack([np.maximum(A[piece_region], cs[chain]), np.minimum(B[piece_region], ce[chain])], axis=1).astype(np.int32)
+    return runs, piece_region, np.ascontiguousarray(np.asarray(seg_is_original) != 0, dtype=np.uint8)
+
+
+def combine(logp, piece_region, num_regions):
+    """log-probability of every region's event from its pieces' (last axis of logp: pieces): their sum.  Chains are
+    independent under the structured posterior, a mask event is a conjunction over segments, and a label event is a
+    conjunction over adjacencies -- a chain end is not an adjacency."""
+    logp = np.asarray(logp, dtype=float)
+    out = np.zeros(logp.shape[:-1] + (int(num_regions),))
+    with np.errstate(invalid='ignore'):
+        np.add.at(out, (Ellipsis, np.asarray(piece_region)), logp)
+    return out
+
+
+def batch_region_events(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, events=REGION_EVENTS):
+    """The arrays of `events` (default: the seven of REGION_EVENTS), each (nr, len(regions)), for restarts r0 .. r0+nr-1 of a
+    RemixtBatch from one device call.  regions: (first, last) experiment segment indices."""
+    masks, labels = event_tables(batch.cn_classes)
+    cs, ce = chains_from_telomeres(is_telomere)
+    runs, piece_region, constrain = region_queries(regions, seg_fwd_remap, seg_is_original, cs, ce)
+    P, R = len(runs), len(np.asarray(regions).reshape(-1, 2))
+    q = np.zeros((len(events), P, 4), dtype=np.int32)
+    q[:, :, :2] = runs[None]
+    for e, (_, mask, label, _) in enumerate(events):
+        q[e, :, 2] = -1 if mask is None else MASK_NAMES.index(mask)
+        q[e, :, 3] = -1 if label is None else LABEL_NAMES.index(label)
+    if P == 0:
+        return dict((ev[0], np.zeros((nr, 0))) for ev in events)
+    logp = batch.region_logprob_raw(r0, nr, q.reshape(-1, 4), masks, labels, constrain).reshape(nr, len(events), P)
+    out = {}
+    for e, (name, _, _, complement) in enumerate(events):
+        lp = np.minimum(combine(logp[:, e], piece_region, R), 0.)      # (a sum of rounded logs of 1 can sit an ulp above 0)
+        out[name] = -np.expm1(lp) if complement else np.exp(lp)
+    return out
+
+
+def adjacency_regions(seg_fwd_remap, is_telomere):
+    """(regions (A, 2), index (A,)): the experiment segment pairs [n, n + 1] that a reference adjacency joins -- no chain
+    end between their model segments -- and their n."""
+    fwd = np.asarray(seg_fwd_remap, dtype=np.int64)
+    ends_before = np.concatenate([[0], np.cumsum(np.asarray(is_telomere) != 0)])      # chain ends among model segments < n
+    joined = ends_before[fwd[1:]] == ends_before[fwd[:-1]]
+    n = np.flatnonzero(joined)
+    return np.stack([n, n + 1], axis=1), n
+
+
+def batch_change_prob(batch, r0, nr, seg_fwd_remap, seg_is_original, is_telomere):
+    """(nr, N - 1): the probability that the copy-number state changes between experiment segments n and n + 1 (anywhere
+    along the model segments that join them), NaN where no reference adjacency joins the two."""
+    regions, n = adjacency_regions(seg_fwd_remap, is_telomere)
+    out = np.full((nr, max(len(seg_fwd_remap) - 1, 0)), np.nan)
+    if len(n):
+        ev = (('p_change', None, 'state', True),)
+        out[:, n] = batch_region_events(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, events=ev)['p_change']
+    return out
+
+
+def add_region_events(res, names, events):
+    """Fit result dict `res` gains `region_events`: the region names and the seven arrays of REGION_ARRAYS."""
+    out = {'names': list(names)}
+    for k in REGION_ARRAYS:
+        out[k] = np.asarray(events[k])
+    res['region_events'] = out
+    return res
+
+
+def parse_regions(cn_regions):
+    """Config value cn_regions, a list of (name, first, last) -> (names, regions int (R, 2))."""
+    names = [str(r[0]) for r in cn_regions]
+    return names, np.array([[int(r[1]), int(r[2])] for r in cn_regions], dtype=np.int64).reshape(-1, 2)

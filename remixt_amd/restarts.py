@@ -677,6 +677,23 @@ class RestartSet(object):
         out = posteriors.batch_summaries(b, 0, R, states=states, marginals=marginals)
         return [dict((k, v[m.seg_fwd_remap]) for k, v in s.items()) for s, m in zip(out, self.models)]
 
+    def region_events(self, regions):
+        """BreakpointModel.region_events of every restart from one device call: a dict of arrays (restarts, len(regions))."""
+        from . import posteriors
+        if self.batch is None or not hasattr(self.batch, 'region_logprob_raw'):
+            per = [m.region_events(regions) for m in self.models]
+            return dict((k, np.stack([p[k] for p in per])) for k in posteriors.REGION_ARRAYS)
+        m = self.models[0]
+        return posteriors.batch_region_events(self.batch, 0, len(self.models), regions, m.seg_fwd_remap, m.seg_is_original, m.is_telomere)
+
+    def cn_change_prob(self):
+        """BreakpointModel.cn_change_prob of every restart from one device call: (restarts, N - 1)."""
+        from . import posteriors
+        if self.batch is None or not hasattr(self.batch, 'region_logprob_raw'):
+            return np.stack([m.cn_change_prob() for m in self.models])
+        m = self.models[0]
+        return posteriors.batch_change_prob(self.batch, 0, len(self.models), m.seg_fwd_remap, m.seg_is_original, m.is_telomere)
+
 
 class RestartGroups(object):
     """The restarts of one GPU split into `groups` RestartSets, each with its own device batch
@@ -811,6 +828,15 @@ class RestartGroups(object):
         return [x for part in self._map(lambda rs: rs.posterior_summary(None if cn is None else cn[self.slices[self.sets.index(rs)]], marginals))
                 for x in part]
 
+    def region_events(self, regions):
+        """RestartSet.region_events over the groups, restarts in order: a dict of arrays (restarts, len(regions))."""
+        parts = self._map(lambda rs: rs.region_events(regions))
+        return dict((k, np.concatenate([p[k] for p in parts])) for k in parts[0])
+
+    def cn_change_prob(self):
+        """RestartSet.cn_change_prob over the groups, restarts in order: (restarts, N - 1)."""
+        return np.concatenate(self._map(lambda rs: rs.cn_change_prob()))
+
     def profile(self):
         """{kernel: (ms, launches)} summed over the groups' batches."""
         out = {}
@@ -902,6 +928,14 @@ class DatasetGroups(object):
     def posterior_summary(self, cn=None, marginals=False):
         """RestartGroups.posterior_summary of every dataset, dataset after dataset (cn: per dataset, a list of its restarts' paths)."""
         return [x for part in self._map(lambda part: part.posterior_summary(None if cn is None else cn[self.parts.index(part)], marginals)) for x in part]
+
+    def region_events(self, regions):
+        """RestartGroups.region_events of every dataset: a list, one dict of arrays (restarts, len(regions)) per dataset."""
+        return self._map(lambda part: part.region_events(regions))
+
+    def cn_change_prob(self):
+        """RestartGroups.cn_change_prob of every dataset: a list of (restarts, N - 1) arrays."""
+        return self._map(lambda part: part.cn_change_prob())
 
     def results_by_dataset(self):
         return self._map(lambda part: part.results())
@@ -1001,16 +1035,23 @@ def _posterior_len(N, M, cn_posterior):
     return N * (6 + 2 * M) + 2 if cn_posterior else 0
 
 
+def _region_len(region_names):
+    """Float slots of the region event probabilities in a record (0 when config cn_regions is unset: the record is
+    unchanged): the seven arrays of posteriors.REGION_ARRAYS, one entry per region."""
+    return 7 * len(region_names) if region_names is not None else 0
+
+
 def _posterior_fields(N, M):
     """(name, shape) of the arrays of posteriors.COMPACT_ARRAYS in record order."""
     from .posteriors import COMPACT_ARRAYS
     return [(k, (N, M) if k.startswith('total_cn') else (N,)) for k in COMPACT_ARRAYS]
 
 
-def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_posterior=False):
+def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_posterior=False, region_names=None):
     """One restart's results as (float64 vector, int8 vector) of fixed length."""
     from .sampling import SUMMARY_STATS
-    f = np.zeros(_HDR + M + nparams + 4 * N + _sample_len(N, M, cn_samples) + _posterior_len(N, M, cn_posterior), dtype=np.float64)
+    f = np.zeros(_HDR + M + nparams + 4 * N + _sample_len(N, M, cn_samples) + _posterior_len(N, M, cn_posterior) + _region_len(region_names),
+                 dtype=np.float64)
     st = res['stats']
     f[0] = st['elbo']; f[1] = st['elbo_diff'] if st['elbo_diff'] is not None else np.nan
     f[2] = st['ploidy']; f[3] = st['proportion_divergent']
@@ -1026,12 +1067,18 @@ def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_post
         f[o + 6 + N * M:o + 6 + N * M + N] = res['cn_state_agreement']
     if cn_posterior:
         from . import posteriors
-        o = len(f) - _posterior_len(N, M, True)
+        o = len(f) - _region_len(region_names) - _posterior_len(N, M, True)
         f[o:o + 2] = [st[k] for k in posteriors.SUMMARY_STATS]
         o += 2
         for k, shape in _posterior_fields(N, M):
             n = int(np.prod(shape))
             f[o:o + n] = np.asarray(res[k]).ravel(); o += n
+    if region_names is not None:
+        from . import posteriors
+        nreg = len(region_names)
+        o = len(f) - _region_len(region_names)
+        for j, k in enumerate(posteriors.REGION_ARRAYS):
+            f[o + j * nreg:o + (j + 1) * nreg] = res['region_events'][k]
     i8 = np.zeros(N * M * 2 + K * M + 2 * N, dtype=np.int8)
     i8[:N * M * 2] = res['cn'].ravel()
     i8[N * M * 2:N * M * 2 + K * M] = np.array([res['brk_cn'][k] for k in brk_ids]).ravel()
@@ -1040,7 +1087,7 @@ def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_post
     return f, i8
 
 
-def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_samples=False, cn_posterior=False):
+def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_samples=False, cn_posterior=False, region_names=None):
     from .sampling import SUMMARY_STATS
     res = dict()
     res['h'] = f[_HDR:_HDR + M].copy()
@@ -1066,20 +1113,25 @@ def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_sampl
         res['cn_state_agreement'] = f[o + 6 + N * M:o + 6 + N * M + N].copy()
     if cn_posterior:
         from . import posteriors
-        o = len(f) - _posterior_len(N, M, True)
+        o = len(f) - _region_len(region_names) - _posterior_len(N, M, True)
         for j, k in enumerate(posteriors.SUMMARY_STATS):
             st[k] = float(f[o + j])
         o += 2
         for k, shape in _posterior_fields(N, M):
             n = int(np.prod(shape))
             res[k] = f[o:o + n].reshape(shape).copy(); o += n
+    if region_names is not None:
+        from . import posteriors
+        nreg = len(region_names)
+        o = len(f) - _region_len(region_names)
+        posteriors.add_region_events(res, region_names, dict((k, f[o + j * nreg:o + (j + 1) * nreg].copy()) for j, k in enumerate(posteriors.REGION_ARRAYS)))
     res['stats'] = st
     return res
 
 
 def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clones=3, num_em_iter=5, num_update_iter=5,
                              device=None, kernel_module=None, seeds=None, quiet=True, groups=2, num_cn_samples=0, cn_sample_seed=0,
-                             cn_posterior_summary=False, **model_kwargs):
+                             cn_posterior_summary=False, cn_regions=None, **model_kwargs):
     """Fit all restarts across the ranks of the default torch.distributed group.
 
     Every rank holds the (small, read-only) experiment; rank g fits restarts
@@ -1090,6 +1142,8 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
     restart_seed(cn_sample_seed, i)), and the records carry the summary.
     cn_posterior_summary: every result also carries the exact posterior summaries of posteriors.COMPACT_ARRAYS and
     the two *_posterior_mean stats, and the records grow by them.
+    cn_regions: a list of (name, first, last) experiment segment intervals; every result also carries `region_events`
+    (posteriors.add_region_events), and the records grow by seven floats per region.
     """
     import torch
     import torch.distributed as dist
@@ -1112,6 +1166,8 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
             add_cn_sample_summaries(rs, local, experiment, num_cn_samples, cn_sample_seed, mine)
         if cn_posterior_summary:
             add_posterior_summaries(rs, local, experiment)
+        if cn_regions is not None:
+            add_region_events(rs, local, cn_regions)
         param_names = list(rs.models[0].likelihood_params)
         rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     if param_names is None:
@@ -1119,7 +1175,19 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
         param_names = ['negbin_r_0', 'negbin_r_1', 'betabin_M_0', 'betabin_M_1'] + (
             [] if nc else ['negbin_hdel_mu', 'negbin_hdel_r_0', 'negbin_hdel_r_1', 'betabin_loh_p', 'betabin_loh_M_0', 'betabin_loh_M_1'])
     return gather_result_records(local, experiment, init_params, num_clones, param_names, device=device, cn_samples=num_cn_samples > 0,
-                                 cn_posterior=bool(cn_posterior_summary))
+                                 cn_posterior=bool(cn_posterior_summary),
+                                 region_names=None if cn_regions is None else [str(r[0]) for r in cn_regions])
+
+
+def add_region_events(rs, results, cn_regions):
+    """Add the region event probabilities of config cn_regions, a list of (name, first, last), of every restart of `rs`
+    (a RestartSet / RestartGroups; one device call per batch) to results[r] (posteriors.add_region_events)."""
+    from . import posteriors
+    names, regions = posteriors.parse_regions(cn_regions)
+    events = rs.region_events(regions)
+    for r, res in enumerate(results):
+        posteriors.add_region_events(res, names, dict((k, v[r]) for k, v in events.items()))
+    return results
 
 
 def add_posterior_summaries(rs, results, experiment):
@@ -1143,7 +1211,7 @@ def add_cn_sample_summaries(rs, results, experiment, num_samples, seed, init_ids
 
 
 def gather_result_records(local, experiment, init_params, num_clones, param_names, device=None, timing=None, local_ids=None, cn_samples=False,
-                          cn_posterior=False):
+                          cn_posterior=False, region_names=None):
     """The one collective of the path: every rank contributes the fixed-size records of the restarts
     it fitted (`local`, in the order of shard_indices) -- one float64 record (ELBO, h, parameters, outlier
     probabilities, failure code) and one int8 record (cn, brk_cn, masks) per restart -- and every rank gets the
@@ -1172,11 +1240,11 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
             per_rank = int(cnt_.item())
     if len(local) > per_rank:
         raise ValueError('gather_result_records: %d local results for a share of %d (pass local_ids for shares that are not shard_indices\')' % (len(local), per_rank))
-    flen = _HDR + M + nparams + 4 * N + _sample_len(N, M, cn_samples) + _posterior_len(N, M, cn_posterior)
+    flen = _HDR + M + nparams + 4 * N + _sample_len(N, M, cn_samples) + _posterior_len(N, M, cn_posterior) + _region_len(region_names)
     ilen = N * M * 2 + K * M + 2 * N
     fbuf = np.full((per_rank, flen), np.nan); ibuf = np.zeros((per_rank, ilen), dtype=np.int8)
     for j, res in enumerate(local):
-        fbuf[j], ibuf[j] = _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples, cn_posterior)
+        fbuf[j], ibuf[j] = _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples, cn_posterior, region_names)
     if local_ids is not None:
         ids_t = np.full((per_rank,), -1, dtype=np.int64); ids_t[:len(local_ids)] = local_ids
     t0 = time.perf_counter()
@@ -1208,7 +1276,7 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
     for g in range(world):
         ids_g = shard_indices(len(init_params), world, g) if ids_all is None else [int(i) for i in ids_all[g] if i >= 0]
         for j, i in enumerate(ids_g):
-            results[i] = _unpack(fall[g][j], iall[g][j], N, M, K, nparams, brk_ids, param_names, init_params[i], cn_samples, cn_posterior)
+            results[i] = _unpack(fall[g][j], iall[g][j], N, M, K, nparams, brk_ids, param_names, init_params[i], cn_samples, cn_posterior, region_names)
     return results
 
 

@@ -149,11 +149,9 @@ enum rmx_option_id {
     RMX_OPT_SEARCH_MODE,        /* parameter searches: 5 (default since round 5) the four standard searches together in rounds the device drives: optimiser
                                    state on the device, a kernel pair per round, queued back to back (half the latency of the host-driven rounds);
                                    0 the same shared rounds driven from the host (the default until round 4);
-                                   1 one parameter at a time; 2 with table rebuilds per candidate; 3 with look-ahead evaluations;
-                                   4 on the full objective; 6 = 0 with the final sums of a Nelder-Mead round folded into the objective kernel (last-block ticket: same bits, one launch
-                                   fewer per round, but a release fence per block -- measured 5 % slower on the headline, not the default);
-                                   7 = 5 as ONE launch: a request's blocks stay resident, publish their partial sums (sc1 stores, no fence) and each advances its own
-                                   copy of the request's optimiser on all of them (same bits as 5) */
+                                   1 one parameter at a time, table-free (what the caller falls back to when rmx_param_search_multi answers RMX_EUNSUPPORTED);
+                                   2 one parameter at a time with table rebuilds per candidate (the path of every non-standard parameter).
+                                   No other value is accepted: 3, 4, 6 and 7 were experiments that lost their measurements and were taken out again */
     RMX_OPT_ELL_DENSE,          /* 1: sampled objectives over all states instead of the lists of states with posterior mass */
     RMX_OPT_STRIP,              /* 1 (default): strip kernels for the (segment x state) passes when 32 < S <= 384 */
     RMX_OPT_CELL_CACHE,         /* creation time, 1 (default): cache the six likelihood values of every cell */
@@ -181,8 +179,6 @@ enum rmx_option_id {
     RMX_OPT_TRACEBACK,          /* trace-back of the kept lattice rows (default transition model): 0 (default) in parallel -- the first arg-maximum of every target
                                    state of every row on the whole chip (k_bp_all), then the walk as a composition of maps (k_chase_compose / _ends / _fill);
                                    1 the sequential walk on one wave per restart (k_backtrace_max / k_backtrace_sad) */
-    RMX_OPT_CU_PARTITION,       /* creation time: 0 (default) the batch's streams use the whole device; parts * 16 + index (parts 2 / 4 / 8): they are created with a CU mask
-                                   -- range `index` of `parts` equal ranges of the device's CUs (hipExtStreamCreateWithCUMask): restart groups that do not share CUs */
     RMX_OPT_COUNT
 };
 int rmx_set_default_option(int32_t option_id, int32_t value);

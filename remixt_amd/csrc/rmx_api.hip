@@ -9,6 +9,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -55,37 +56,26 @@ struct ProfRec { int id; hipEvent_t a, b; };
 // launches serialised: 106-111 instead of 148 EM iterations/s at 355 states, profiles/r04_hw_queues.txt).  Pooled streams are created on demand,
 // handed back when their batch is destroyed and never destroyed themselves: a role's queue is decided once per process, and a batch built later
 // gets a stream with the placement the first ones got (profiles/r05_stream_pool.txt).
-// (pool key: role 0 / 1 and the CU partition of option cu_partition -- 0: the whole device; parts * 16 + index: partition `index` of `parts` equal ranges of the CU mask)
-struct StreamPool { std::mutex mu; std::map<int, std::vector<hipStream_t>> idle; int created[2] = {0, 0}; };
+struct StreamPool { std::mutex mu; std::vector<hipStream_t> idle[2]; int created[2] = {0, 0}; };
 static StreamPool g_stream_pool[16];
-static hipError_t create_stream_for(int dev, int part, hipStream_t *out) {
-    if (part <= 0) return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
-    const int parts = part >> 4, idx = part & 15;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorUnknown;
-    const int ncu = prop.multiProcessorCount, per = ncu / parts;
-    std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-    for (int c = idx * per; c < (idx + 1) * per; c++) mask[c >> 5] |= 1u << (c & 31);
-    return hipExtStreamCreateWithCUMask(out, (uint32_t)mask.size(), mask.data());
-}
-static int pool_acquire(int dev, int role, hipStream_t *out, int part = 0) {
+static int pool_acquire(int dev, int role, hipStream_t *out) {
     StreamPool &p = g_stream_pool[dev & 15];
     std::lock_guard<std::mutex> lk(p.mu);
-    std::vector<hipStream_t> &idle = p.idle[role + 2 * part];
+    std::vector<hipStream_t> &idle = p.idle[role];
     if (!idle.empty()) { *out = idle.front(); idle.erase(idle.begin()); return RMX_OK; }      // (the oldest first)
-    if (create_stream_for(dev, part, out) != hipSuccess) return RMX_EDEVICE;
+    if (hipStreamCreateWithFlags(out, hipStreamNonBlocking) != hipSuccess) return RMX_EDEVICE;
     p.created[role]++;
     return RMX_OK;
 }
-static void pool_release(int dev, int role, hipStream_t s, int part = 0) {
+static void pool_release(int dev, int role, hipStream_t s) {
     hipStreamSynchronize(s);
     StreamPool &p = g_stream_pool[dev & 15];
     std::lock_guard<std::mutex> lk(p.mu);
-    p.idle[role + 2 * part].push_back(s);
+    p.idle[role].push_back(s);
 }
 
 // tuning options (include/remixt_amd.h rmx_option_id): process-wide defaults, copied into a batch at creation
-static int g_opt_default[RMX_OPT_COUNT] = {0, 0, 1, 1, 1, 0, 5, 0, 1, 1, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0};      // (search_mode 5 since round 5)
+static int g_opt_default[RMX_OPT_COUNT] = {0, 0, 1, 1, 1, 0, 5, 0, 1, 1, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0};      // (search_mode 5 since round 5)
 static std::mutex g_opt_mu;
 
 struct rmx_batch {
@@ -151,7 +141,7 @@ struct rmx_batch {
     void *h_batch = nullptr;           // pinned staging for the batched objective
     std::vector<int32_t> plain_list; int32_t *d_plain_list = nullptr; double *d_plain_jt = nullptr;
     // viterbi
-    int last_search_blocks = 0, last_search_persist = 0;
+    int last_search_blocks = 0;
     unsigned *d_vflag = nullptr; int cluster_timeouts = 0;      // "a cluster member gave up waiting" of the last lattice launch; how often that has happened
     int last_viterbi_wgs = 1;      // workgroups per restart of the last lattice (k_viterbi_sad_max<., true>: clusters)
     int32_t *d_vit_special = nullptr; int n_vit_special = -1;      // adjacencies that are not plain class-0 ones, ascending (k_viterbi_max)
@@ -302,7 +292,6 @@ static int translate_error(rmx_batch *b, int r, uint32_t v) {
     if (v & RMX_ERR_BAD_P) { snprintf(buf, sizeof buf, "p <= 0 or (1 - p) <= 0. (restart %d)", r); return fail_flagged(RMX_EVALUE, buf); }
     if (v & RMX_ERR_DIGAMMA) { snprintf(buf, sizeof buf, "x <= 0.0 in digamma (restart %d)", r); return fail_flagged(RMX_EVALUE, buf); }
     if (v & RMX_ERR_NAN_GRAD) { snprintf(buf, sizeof buf, "partial derivative is nan (restart %d)", r); return fail_flagged(RMX_EVALUE, buf); }
-    if (v & RMX_ERR_WAIT) { snprintf(buf, sizeof buf, "a one-launch parameter search (search_mode 7) gave up waiting for a block that was not resident (restart %d)", r); return fail_flagged(RMX_EDEVICE, buf); }
     if (v & RMX_ERR_NAN_F) { snprintf(buf, sizeof buf, "nan in framelogprob (restart %d)", r); return fail_flagged(RMX_EASSERT, buf); }
     if (v & RMX_ERR_NAN_AB) { snprintf(buf, sizeof buf, "nan in alphas/betas (restart %d)", r); return fail_flagged(RMX_EASSERT, buf); }
     if (v & RMX_ERR_NAN_POST) { snprintf(buf, sizeof buf, "nan in posterior marginals (restart %d)", r); return fail_flagged(RMX_EASSERT, buf); }
@@ -765,13 +754,12 @@ static bool option_value_ok(int id, int v) {
     switch (id) {
     case RMX_OPT_FB_KERNEL: return v >= 0 && v <= 3;
     case RMX_OPT_FB_NV: return v == 0 || v == 1 || v == 2 || v == 4;      // the workgroup shapes that exist (k_fbm and k_fbv / k_fbk 1 / 2 / 4, k_fbq 4)
-    case RMX_OPT_SEARCH_MODE: return v >= 0 && v <= 7;
+    case RMX_OPT_SEARCH_MODE: return v == 0 || v == 1 || v == 2 || v == 5;      // (the numbers of the modes that were taken out again stay unused)
     case RMX_OPT_PAIRWISE_KERNEL: return v >= 0 && v <= 4;
     case RMX_OPT_FB_WG_BUDGET: return v >= 0 && v <= 4096;
     case RMX_OPT_GRAD_KERNEL: return v >= 0 && v <= 2;
     case RMX_OPT_VITERBI_CLUSTER: return v == 0 || v == 1 || v == 2 || v == 4 || v == 8 || v == 102 || v == 104 || v == 108;
     case RMX_OPT_TRACEBACK: return v == 0 || v == 1;
-    case RMX_OPT_CU_PARTITION: return v == 0 || (((v >> 4) == 2 || (v >> 4) == 4 || (v >> 4) == 8) && (v & 15) < (v >> 4));
     case RMX_OPT_VITERBI_PLAIN: return v >= 0 && v <= 2;
     default: return v == 0 || v == 1;
     }
@@ -785,7 +773,7 @@ int rmx_set_default_option(int32_t id, int32_t value) {
 static void configure_fb(rmx_batch *b);
 int rmx_set_option(rmx_batch *b, int32_t id, int32_t value) {
     if (!b || id < 0 || id >= RMX_OPT_COUNT || !option_value_ok(id, value)) return fail(RMX_EARG, "bad option id / value");
-    if (id == RMX_OPT_CELL_CACHE || id == RMX_OPT_SPARSE_TRIAL || id == RMX_OPT_FB_DEBUG || id == RMX_OPT_STREAM_POOL || id == RMX_OPT_CU_PARTITION) return fail(RMX_EARG, "creation-time option: use rmx_set_default_option before rmx_batch_create");
+    if (id == RMX_OPT_CELL_CACHE || id == RMX_OPT_SPARSE_TRIAL || id == RMX_OPT_FB_DEBUG || id == RMX_OPT_STREAM_POOL) return fail(RMX_EARG, "creation-time option: use rmx_set_default_option before rmx_batch_create");
     BIND(b);      // configure_fb sets function attributes (the > 64 KiB LDS opt-in) on the calling thread's current device
     b->opt[id] = value;
     if (id == RMX_OPT_FB_KERNEL) configure_fb(b);
@@ -827,8 +815,8 @@ int rmx_batch_create(const rmx_problem *pr, int32_t R, const double *h_init, con
     { std::lock_guard<std::mutex> lk(g_opt_mu); memcpy(b->opt, g_opt_default, sizeof b->opt); }
     b->device = device; b->R = R;
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) b->num_cus = cus; }
-    if (b->opt[RMX_OPT_STREAM_POOL]) { if (pool_acquire(device, 0, &b->stream, b->opt[RMX_OPT_CU_PARTITION]) != RMX_OK) { delete b; return fail(RMX_EDEVICE, "hipStreamCreate failed"); } b->pooled_stream = true; }
-    else HIPCHK(create_stream_for(device, b->opt[RMX_OPT_CU_PARTITION], &b->stream));
+    if (b->opt[RMX_OPT_STREAM_POOL]) { if (pool_acquire(device, 0, &b->stream) != RMX_OK) { delete b; return fail(RMX_EDEVICE, "hipStreamCreate failed"); } b->pooled_stream = true; }
+    else HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
     b->own_stream = true;
     Dev &d = b->d;
     d.N = N; d.S = S; d.SP = ((S + 7) / 8) * 8; d.M = M; d.K = K; d.B = B; d.C = C; d.nc = pr->normal_contamination ? 1 : 0;
@@ -1080,11 +1068,11 @@ int rmx_batch_destroy(rmx_batch *b) { BIND(b);
     if (b->tm_a) hipEventDestroy(b->tm_a);
     if (b->tm_b) hipEventDestroy(b->tm_b);
     for (auto e : b->done_ev) hipEventDestroy(e);
-    if (b->stream2) { hipStreamSynchronize(b->stream2); if (b->pooled_stream2) pool_release(b->device, 1, b->stream2, b->opt[RMX_OPT_CU_PARTITION]); else hipStreamDestroy(b->stream2); hipEventDestroy(b->ev_fb); hipEventDestroy(b->ev_brk); }
+    if (b->stream2) { hipStreamSynchronize(b->stream2); if (b->pooled_stream2) pool_release(b->device, 1, b->stream2); else hipStreamDestroy(b->stream2); hipEventDestroy(b->ev_fb); hipEventDestroy(b->ev_brk); }
     if (b->ev_copy) hipEventDestroy(b->ev_copy);
     if (b->ev_pace) hipEventDestroy(b->ev_pace);
     if (b->h_ind) { hipHostUnregister(b->h_ind); free(b->h_ind); }
-    if (b->own_stream && b->stream) { if (b->pooled_stream) pool_release(b->device, 0, b->stream, b->opt[RMX_OPT_CU_PARTITION]); else hipStreamDestroy(b->stream); }
+    if (b->own_stream && b->stream) { if (b->pooled_stream) pool_release(b->device, 0, b->stream); else hipStreamDestroy(b->stream); }
     delete b;
     return RMX_OK;
 }
@@ -1092,7 +1080,7 @@ int rmx_batch_destroy(rmx_batch *b) { BIND(b);
 int rmx_set_stream(rmx_batch *b, void *s) { BIND(b);
     if (!b) return fail(RMX_EARG, "null batch");
     HIPCHK(hipStreamSynchronize(b->stream));
-    if (b->own_stream) { if (b->pooled_stream) pool_release(b->device, 0, b->stream, b->opt[RMX_OPT_CU_PARTITION]); else hipStreamDestroy(b->stream); b->own_stream = false; b->pooled_stream = false; }
+    if (b->own_stream) { if (b->pooled_stream) pool_release(b->device, 0, b->stream); else hipStreamDestroy(b->stream); b->own_stream = false; b->pooled_stream = false; }
     if (s) b->stream = (hipStream_t)s;
     else { HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking)); b->own_stream = true; }
     return RMX_OK;
@@ -1108,9 +1096,9 @@ int rmx_info(rmx_batch *b, int32_t what, int64_t *out) { BIND(b);
     case 12: *out = b->last_fb_kernel; break; case 13: *out = b->last_fb_nv; break; case 14: *out = b->last_viterbi; break; case 15: *out = b->last_fb_nv_max; break;
     case 18: *out = b->last_viterbi_wgs; break; case 19: *out = b->last_traceback; break;
     case 54: *out = b->cluster_timeouts; break;      // decodes repeated with one workgroup per restart after a lattice cluster's watchdog ran out
-    case 52: *out = b->last_search_blocks; break; case 53: *out = b->last_search_persist; break;      // blocks of the last device-driven search; 1: one launch (k_search_persist)
+    case 52: *out = b->last_search_blocks; break;      // blocks of the last device-driven search
     case 16: { StreamPool &p_ = g_stream_pool[b->device & 15]; std::lock_guard<std::mutex> lk(p_.mu); *out = p_.created[0] + p_.created[1]; break; }      // streams the device's pool has created so far
-    case 17: { StreamPool &p_ = g_stream_pool[b->device & 15]; std::lock_guard<std::mutex> lk(p_.mu); { size_t n_ = 0; for (auto &kv : p_.idle) n_ += kv.second.size(); *out = (int64_t)n_; } break; }   // ... of them idle
+    case 17: { StreamPool &p_ = g_stream_pool[b->device & 15]; std::lock_guard<std::mutex> lk(p_.mu); *out = (int64_t)(p_.idle[0].size() + p_.idle[1].size()); break; }   // ... of them idle
     case 20: case 21: case 22: case 23: case 24: case 25: case 26: case 27: case 28: case 29: case 30: case 31: case 32: case 33: case 34: case 35: case 36: case 37: case 38: case 39:
     case 40: case 41: case 42: case 43: case 44: case 45: case 46: case 47: case 48: case 49: case 50: case 51:
         { if (!b->d_dbg) { *out = 0; break; } unsigned long long v[32]; HIPCHK(hipStreamSynchronize(b->stream)); HIPCHK(hipMemcpy(v, b->d_dbg, 256, hipMemcpyDeviceToHost)); *out = (int64_t)v[what - 20]; break; }
@@ -1664,8 +1652,8 @@ int rmx_variational_update(rmx_batch *b, int32_t r0, int32_t r1, int32_t iters) 
     // the breakend branch of a sweep (pairwise reductions, update_p_breakpoint) next to its marginal pass
     const bool two_streams = use_strip(b) && b->d.NBE > 0 && b->opt[RMX_OPT_TWO_STREAMS];
     if (two_streams && !b->stream2) {
-        if (b->opt[RMX_OPT_STREAM_POOL]) { if (pool_acquire(b->device, 1, &b->stream2, b->opt[RMX_OPT_CU_PARTITION]) != RMX_OK) return fail(RMX_EDEVICE, "hipStreamCreate failed"); b->pooled_stream2 = true; }
-        else HIPCHK(create_stream_for(b->device, b->opt[RMX_OPT_CU_PARTITION], &b->stream2));
+        if (b->opt[RMX_OPT_STREAM_POOL]) { if (pool_acquire(b->device, 1, &b->stream2) != RMX_OK) return fail(RMX_EDEVICE, "hipStreamCreate failed"); b->pooled_stream2 = true; }
+        else HIPCHK(hipStreamCreateWithFlags(&b->stream2, hipStreamNonBlocking));
         HIPCHK(hipEventCreateWithFlags(&b->ev_fb, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&b->ev_brk, hipEventDisableTiming));
     }
@@ -2139,6 +2127,40 @@ int rmx_expected_ll_batch(rmx_batch *b, int32_t nreq, const int32_t *restarts, i
 namespace {
 using rmxh::Nm1;
 }  // namespace
+// np.argmin over one optimiser's grid, nll = -ell[g]: the grid point of the FIRST minimum
+static double grid_first_argmin(const double *grid, const double *ell, int G) {
+    double best = INFINITY, x0 = grid[0];
+    for (int g = 0; g < G; g++) { const double J = -ell[g]; if (g == 0 || J < best) { best = J; x0 = grid[g]; } }
+    return x0;
+}
+// The Nelder-Mead polish of n optimisers in lock step, optimiser i from x0[i] within [lo[i], hi[i]]: every optimiser
+// is advanced until it needs a value or has finished -- a point outside its bounds is +inf at once, nothing evaluated
+// (cn_model.py:542-543) --, then eval(m, idx, pts, ell) evaluates ONE round: E[ll] of optimiser idx[k] at pts[k] into
+// ell[k], k < m, in the order the optimisers asked; nll = -ell.  xopt[i] receives the result, lastval[i] the last
+// point evaluated for optimiser i (the caller's value stays where nothing was).
+static int nm_lockstep(int n, const double *x0, const double *lo, const double *hi, const std::function<int(int, const int *, const double *, double *)> &eval,
+                       double *xopt, double *lastval) {
+    std::vector<Nm1> nm(n);
+    std::vector<int> want, cur;          // optimisers waiting for an evaluation; those of the round under way
+    std::vector<double> pts(n), ell(n);
+    auto pump = [&](int i, double f) {
+        while (nm[i].advance(x0[i], f)) {
+            if (nm[i].req < lo[i] || nm[i].req > hi[i]) { f = INFINITY; continue; }
+            want.push_back(i);
+            return;
+        }
+    };
+    for (int i = 0; i < n; i++) pump(i, 0.);
+    while (!want.empty()) {
+        cur.clear();
+        cur.swap(want);
+        for (size_t k = 0; k < cur.size(); k++) { pts[k] = nm[cur[k]].req; lastval[cur[k]] = pts[k]; }
+        if (int rc = eval((int)cur.size(), cur.data(), pts.data(), ell.data())) return rc;
+        for (size_t k = 0; k < cur.size(); k++) pump(cur[k], -ell[k]);
+    }
+    for (int i = 0; i < n; i++) xopt[i] = nm[i].xopt();
+    return RMX_OK;
+}
 
 // scipy.optimize.brute(nll, ranges=[(lo, hi)], Ns=G, full_output=True)[0] for one likelihood parameter
 // of every listed restart in lock step (BreakpointModel.update_param, cn_model.py:553-561): grid of G
@@ -2155,15 +2177,19 @@ int rmx_param_search(rmx_batch *b, int32_t nreq, const int32_t *restarts, int32_
     // One likelihood parameter moves one or two of the four likelihood components (negbin_r_0: the
     // non-outlier total-count term, ...).  The rest of E[ll] is constant over the search: it is taken
     // once from a full evaluation at the first grid value, and every later evaluation computes only the
-    // moving part.  (Differs from the full sum by rounding only; RMX_SEARCH_FULL=1 evaluates everything.)
+    // moving part.  (Differs from the full sum by rounding only.)
     static const int comp_bits[RMX_P_HMM_LOG_NORM_CONST] = {CM_LT0, CM_LT1, CM_LT0 | CM_LT1, CM_LT0, CM_LT1, CM_LA0, CM_LA1, CM_LA0 | CM_LA1, CM_LA0, CM_LA1, 0, 0, 0};
     int mask = comp_bits[param_id] & CM_ALL;
-    if (mask == 0 || b->opt[RMX_OPT_SEARCH_MODE] == 4) mask = CM_ALL;
-    std::vector<double> vals(nreq), out(nreq), best(nreq, INFINITY), x0(nreq), cst(nreq, 0.);
-    auto eval = [&](int n_, const int32_t *rl_, const double *v_, double *o_, const int *who) -> int {
-        for (int i = 0; i < n_; i++)
-            if (int e_ = rmx_set_param(b, rl_[i], param_id, v_[i])) return e_;
-        int e_ = run_ell_batch(b, n_, rl_, false, o_, mask);
+    if (mask == 0) mask = CM_ALL;
+    std::vector<double> vals(nreq), x0(nreq), cst(nreq, 0.);
+    std::vector<int32_t> rl(nreq);
+    // who: indices into restarts[] (nullptr: all, in order), here and in search_eval
+    auto eval = [&](int n_, const int *who, const double *v_, double *o_) -> int {
+        for (int i = 0; i < n_; i++) {
+            rl[i] = restarts[who ? who[i] : i];
+            if (int e_ = rmx_set_param(b, rl[i], param_id, v_[i])) return e_;
+        }
+        int e_ = run_ell_batch(b, n_, rl.data(), false, o_, mask);
         if (e_) return e_;
         if (mask != CM_ALL) for (int i = 0; i < n_; i++) o_[i] += cst[who ? who[i] : i];
         return RMX_OK;
@@ -2184,15 +2210,13 @@ int rmx_param_search(rmx_batch *b, int32_t nreq, const int32_t *restarts, int32_
     const bool table_free = (mask == CM_LT0 || mask == CM_LT1 || mask == CM_LA0 || mask == CM_LA1) && nreq <= 16 && G <= 32 &&
                             (param_id == RMX_P_NEGBIN_R_0 || param_id == RMX_P_NEGBIN_R_1 || param_id == RMX_P_BETABIN_M_0 || param_id == RMX_P_BETABIN_M_1) &&
                             b->opt[RMX_OPT_SEARCH_MODE] != 2;
-    std::vector<double> lastval(nreq, grid[0]);
     const bool sparse_search = ell_sparse_ok(b, nreq, restarts);
     auto search_eval = [&](int n_, const int *who, const double *v_, int Gz, bool per_request, double *o_) -> int {
-        // who: indices into restarts[] (nullptr: all, in order); v_: Gz grid values or n_ per-request values
+        // v_: Gz grid values shared by the requests, or (per_request, Gz = 1) one value per request
         const Dev &d = b->d;
         SearchVals sv;
         sv.per_request = per_request ? 1 : 0; sv.Gz = Gz; sv.pad0 = sv.pad1 = 0;
-        const int nv_ = per_request ? n_ * Gz : Gz;
-        if (per_request && Gz > 1) sv.per_request = 2;
+        const int nv_ = per_request ? n_ : Gz;
         for (int i = 0; i < 64; i++) { sv.v[i] = i < nv_ ? v_[i] : v_[0]; sv.lv[i] = std::log(sv.v[i]); }
         int maxcnt = 0;
         for (int i = 0; i < 16; i++) { const int r_ = restarts[who ? who[i < n_ ? i : 0] : (i < n_ ? i : 0)]; sv.rlist[i] = r_; if (i < n_) maxcnt = std::max(maxcnt, b->sample_count[r_]); }
@@ -2215,74 +2239,25 @@ int rmx_param_search(rmx_batch *b, int32_t nreq, const int32_t *restarts, int32_
             for (int g = 0; g < Gz; g++) o_[i * Gz + g] = b->h_pinned[i * Gz + g] + cst[who ? who[i] : i];
         return RMX_OK;
     };
+    // the grid: E[ll] of request i at grid[g] in og[i * G + g]
+    std::vector<double> og((size_t)nreq * G), out(nreq);
     if (table_free) {
-        std::vector<double> og((size_t)nreq * G);
         if ((rc = search_eval(nreq, nullptr, grid, G, false, og.data()))) return rc;
-        for (int g = 0; g < G; g++)
-            for (int i = 0; i < nreq; i++) { const double J = -og[(size_t)i * G + g]; if (g == 0 || J < best[i]) { best[i] = J; x0[i] = grid[g]; } }
-        for (int i = 0; i < nreq; i++) lastval[i] = grid[G - 1];
     } else
     for (int g = 0; g < G; g++) {
         for (int i = 0; i < nreq; i++) vals[i] = grid[g];
-        if ((rc = eval(nreq, restarts, vals.data(), out.data(), nullptr))) return rc;
-        for (int i = 0; i < nreq; i++) { const double J = -out[i]; if (g == 0 || J < best[i]) { best[i] = J; x0[i] = grid[g]; } }   // np.argmin: first minimum
+        if ((rc = eval(nreq, nullptr, vals.data(), out.data()))) return rc;
+        for (int i = 0; i < nreq; i++) og[(size_t)i * G + g] = out[i];
     }
-    std::vector<Nm1> nm(nreq);
-    std::vector<int> want;          // requests waiting for a device evaluation
-    std::vector<int32_t> rl(nreq);
-    // RMX_SEARCH_LOOKAHEAD=1: table-free rounds also evaluate, in the same launch, the points each
-    // optimiser may ask for next (Nm1::lookahead); when the next request is one of them its value is
-    // already here and the round trip is saved.  A value is a function of the point only, so the sequence
-    // of (point, value) pairs every optimiser sees -- and with it the result and the restart's last
-    // evaluated point -- is unchanged.  Off by default: the evaluation kernel is bound by FP64
-    // transcendental throughput, not by launch latency, so 4 candidates per request cost more device time
-    // (taken from the other restart group's sweeps) than the halved round count returns (measured on
-    // MI355X at the benchmark shape: 69.3 ms per step with, 66.2 ms without).
-    constexpr int LOOK = 4;
-    const bool lookahead = table_free && b->opt[RMX_OPT_SEARCH_MODE] == 3;
-    struct Seen { double x[LOOK], f[LOOK]; int n = 0; };
-    std::vector<Seen> seen(nreq);
-    auto pump = [&](int i, double f) {
-        // advance optimiser i until it needs a device evaluation or finishes; out-of-bounds points are +inf at once
-        while (nm[i].advance(x0[i], f)) {
-            const double v = nm[i].req;
-            if (v < lo || v > hi) { f = INFINITY; continue; }
-            bool hit = false;
-            for (int c = 0; c < seen[i].n && !hit; c++) if (seen[i].x[c] == v) { f = seen[i].f[c]; hit = true; }
-            if (hit) { lastval[i] = v; continue; }
-            want.push_back(i);
-            return;
-        }
-    };
-    for (int i = 0; i < nreq; i++) pump(i, 0.);
-    std::vector<double> cand((size_t)nreq * LOOK), oc((size_t)nreq * LOOK);
-    while (!want.empty()) {
-        std::vector<int> cur;
-        cur.swap(want);
-        for (size_t k = 0; k < cur.size(); k++) { rl[k] = restarts[cur[k]]; vals[k] = nm[cur[k]].req; lastval[cur[k]] = vals[k]; }
-        if (lookahead) {
-            for (size_t k = 0; k < cur.size(); k++) {
-                double la[3];
-                const int nl = nm[cur[k]].lookahead(la);
-                for (int c = 0; c < LOOK; c++) cand[k * LOOK + c] = vals[k];                       // unused slots repeat the pending point
-                for (int c = 0; c < nl; c++) if (la[c] >= lo && la[c] <= hi) cand[k * LOOK + 1 + c] = la[c];
-            }
-            if ((rc = search_eval((int)cur.size(), cur.data(), cand.data(), LOOK, true, oc.data()))) return rc;
-            for (size_t k = 0; k < cur.size(); k++) {
-                Seen &sn = seen[cur[k]];
-                sn.n = LOOK;
-                for (int c = 0; c < LOOK; c++) { sn.x[c] = cand[k * LOOK + c]; sn.f[c] = -oc[k * LOOK + c]; }
-                out[k] = oc[k * LOOK];
-            }
-        }
-        else if (table_free) { if ((rc = search_eval((int)cur.size(), cur.data(), vals.data(), 1, true, out.data()))) return rc; }
-        else if ((rc = eval((int)cur.size(), rl.data(), vals.data(), out.data(), cur.data()))) return rc;
-        for (size_t k = 0; k < cur.size(); k++) pump(cur[k], -out[k]);
-    }
+    for (int i = 0; i < nreq; i++) x0[i] = grid_first_argmin(grid, og.data() + (size_t)i * G, G);
+    std::vector<double> los(nreq, lo), his(nreq, hi), lastval(nreq, grid[G - 1]);
+    rc = nm_lockstep(nreq, x0.data(), los.data(), his.data(), [&](int n_, const int *who, const double *v_, double *o_) -> int {
+        return table_free ? search_eval(n_, who, v_, 1, true, o_) : eval(n_, who, v_, o_);
+    }, xopt, lastval.data());
+    if (rc) return rc;
     // the table-free evaluations did not touch the model: leave the parameter at the value of the restart's
     // last evaluation, as the sequential scipy run (and the table-rebuilding path) does
     if (table_free) for (int i = 0; i < nreq; i++) if ((rc = rmx_set_param(b, restarts[i], param_id, lastval[i]))) return rc;
-    for (int i = 0; i < nreq; i++) xopt[i] = nm[i].xopt();
     return RMX_OK;
 }
 
@@ -2417,9 +2392,8 @@ int rmx_param_search_multi(rmx_batch *b, int32_t nreq, const int32_t *restarts, 
             i = j;
         }
     }
-    // one round: requests cur[0..n) (indices q = j * nreq + i), their values vals[] (ignored in the grid stage)
-    std::vector<double> out((size_t)Q * G);
-    auto round = [&](int n_, const int *cur, const double *vals, bool grid_stage) -> int {
+    // one round: requests cur[0..n) (indices q = j * nreq + i), their values vals[] (ignored in the grid stage) -> o_[k * Gz + g]
+    auto round = [&](int n_, const int *cur, const double *vals, bool grid_stage, double *o_) -> int {
         MultiVals m2 = mv;
         m2.grid_stage = grid_stage ? 1 : 0; m2.Gz = grid_stage ? G : 1;
         int mc = 0;
@@ -2432,16 +2406,6 @@ int rmx_param_search_multi(rmx_batch *b, int32_t nreq, const int32_t *restarts, 
         for (int k = n_; k < 64; k++) { m2.rlist[k] = m2.rlist[0]; m2.slot[k] = m2.slot[0]; m2.v[k] = m2.v[0]; m2.lv[k] = m2.lv[0]; }
         {
             std::lock_guard<std::mutex> lk(b->mu);
-            if (mc > 0 && !grid_stage && b->opt[RMX_OPT_SEARCH_MODE] == 6) {
-                // search_mode 6 (round 5, measured and NOT the default): a Nelder-Mead round whose objective kernel sums its own partials (the last block of a
-                // request, behind a release fence per block).  One launch fewer per round -- and 5 % off the headline (397 against 418-421 EM it/s, two
-                // alternating runs each on one box): an agent-scope release writes the XCD's dirty L2 lines back, and next to the other restart
-                // group's forward-backward and marginal passes the L2s are full of their rows; 800 blocks x 52 rounds of that per M-step
-                ProfScope ps(b, KID_ELL_LIST);
-                hipLaunchKernelGGL(k_ell_search_multi_final, dim3((mc + SEG_PER_BLOCK - 1) / SEG_PER_BLOCK, n_), dim3(256), 0, b->stream, b->d, m2, (const int32_t *)b->d_msample,
-                                   (const int32_t *)b->d_mcounts, b->d_mpartial, std::max(mc, 1), b->d_done, b->h_pinned, b->h_err);
-                HIPCHK(hipGetLastError());
-            } else {
             if (mc > 0) {
                 ProfScope ps(b, KID_ELL_LIST);
                 hipLaunchKernelGGL(k_ell_search_multi, dim3((mc + SEG_PER_BLOCK - 1) / SEG_PER_BLOCK, n_, m2.Gz), dim3(256), 0, b->stream, b->d, m2, (const int32_t *)b->d_msample,
@@ -2450,11 +2414,10 @@ int rmx_param_search_multi(rmx_batch *b, int32_t nreq, const int32_t *restarts, 
             { ProfScope ps(b, KID_ELL_FINAL); hipLaunchKernelGGL(k_ell_multi_final, dim3(n_ * m2.Gz), dim3(256), 0, b->stream, b->d, m2, (const int32_t *)b->d_mcounts,
                                                                  (const double *)b->d_mpartial, std::max(mc, 1), b->h_pinned, b->h_err); }
             HIPCHK(hipGetLastError());
-            }
         }
         HIPCHK(hipStreamSynchronize(b->stream));
         if (int rc_ = report_request_errors(b, n_, b->h_err, [&](int k) { return (int)m2.rlist[k]; })) return rc_;
-        for (int k = 0; k < n_ * m2.Gz; k++) out[k] = b->h_pinned[k];
+        for (int k = 0; k < n_ * m2.Gz; k++) o_[k] = b->h_pinned[k];
         return RMX_OK;
     };
     std::vector<int> all(Q);
@@ -2466,7 +2429,7 @@ int rmx_param_search_multi(rmx_batch *b, int32_t nreq, const int32_t *restarts, 
     // the GPU to themselves (next to another group's sweeps 415-416 against 424-426 EM it/s for the host rounds); with round 5's flat trial
     // passes it wins there too -- 440.7 / 440.8 against 402-422 EM it/s, alternating runs on one box (profiles/r05_mstep_ab.txt): a restart
     // group's EM period is its sweeps plus its OWN M-step chain (the other group's sweeps hide it only while it is the shorter of the two).
-    if ((b->opt[RMX_OPT_SEARCH_MODE] == 5 || b->opt[RMX_OPT_SEARCH_MODE] == 7) && maxcnt <= NM_MAX_SAMPLE) {
+    if (b->opt[RMX_OPT_SEARCH_MODE] == 5 && maxcnt <= NM_MAX_SAMPLE) {
         if (!b->d_nm_state) {
             if ((rc = dalloc(b, &b->d_nm_state, (size_t)64)) ||
                 (rc = dalloc(b, &b->nm_lay.pre, (size_t)64 * (NM_MAX_SAMPLE + 1))) || (rc = dalloc(b, &b->nm_lay.fix, (size_t)64 * NM_MAX_SAMPLE)) ||
@@ -2493,34 +2456,7 @@ int rmx_param_search_multi(rmx_batch *b, int32_t nreq, const int32_t *restarts, 
         for (int q = Q; q < 64; q++) na.blk0[q + 1] = na.blk0[Q];
         const int TB = std::max(na.blk0[Q], 1);
         uint32_t *done = b->h_err;                  // [Q]: 0 while the request's optimiser runs, then 1 + the restart's error word
-        // search_mode 7: the whole search as ONE launch of resident blocks (k_search_persist) -- where every request has cells
-        // (a block waits only for the blocks of its own request -- consecutive indices, dispatched in order --, so what must be resident together is one request's blocks)
-        bool persist = b->opt[RMX_OPT_SEARCH_MODE] == 7 && na.blk0[Q] >= 1;
-        for (int q = 0; q < Q && persist; q++) persist = na.blk0[q + 1] > na.blk0[q] && na.blk0[q + 1] - na.blk0[q] <= 128;
-        b->last_search_blocks = na.blk0[Q]; b->last_search_persist = persist ? 1 : 0;
-        if (persist) {
-            const size_t need = (size_t)(G + Nm1::maxfun + 2) * TB;
-            if (b->nm_partial_cap < need) {
-                dfree(b, b->d_nm_partial); b->d_nm_partial = nullptr; b->nm_partial_cap = 0;
-                if ((rc = dalloc(b, &b->d_nm_partial, need))) return rc;
-                b->nm_partial_cap = need;
-            }
-            na.grid_stage = 0;
-            {
-                std::lock_guard<std::mutex> lk(b->mu);
-                ProfScope ps(b, KID_ELL_LIST);
-                HIPCHK(hipMemsetAsync(b->d_nm_partial, 0xff, need * 8, b->stream));      // "not yet published"
-                hipLaunchKernelGGL(k_search_persist, dim3(TB), dim3(256), 0, b->stream, b->d, na, (const int32_t *)b->d_msample, (const int32_t *)b->d_mcounts,
-                                   b->nm_lay, b->d_nm_partial, b->h_pinned);
-                hipLaunchKernelGGL(k_search_flags, dim3(1), dim3(64), 0, b->stream, b->d, na, done);
-                HIPCHK(hipGetLastError());
-            }
-            HIPCHK(hipStreamSynchronize(b->stream));
-            for (int q = 0; q < Q; q++) done[q] -= 1u;
-            if (int rc_ = report_request_errors(b, Q, done, [&](int q) { return (int)mv.rlist[q]; })) return rc_;
-            for (int q = 0; q < Q; q++) { xopt[q] = b->h_pinned[2 * q]; lastval[q] = b->h_pinned[2 * q + 1]; }
-            return RMX_OK;
-        }
+        b->last_search_blocks = na.blk0[Q];
         const size_t pneed = (size_t)G * TB;
         if (b->nm_partial_cap < pneed) {
             dfree(b, b->d_nm_partial); b->d_nm_partial = nullptr; b->nm_partial_cap = 0;
@@ -2560,35 +2496,18 @@ int rmx_param_search_multi(rmx_batch *b, int32_t nreq, const int32_t *restarts, 
         for (int q = 0; q < Q; q++) { xopt[q] = b->h_pinned[2 * q]; lastval[q] = b->h_pinned[2 * q + 1]; }
         return RMX_OK;
     }
-    if ((rc = round(Q, all.data(), nullptr, true))) return rc;
-    std::vector<double> x0(Q), best(Q, INFINITY);
+    // search_mode 0, or a sample above NM_MAX_SAMPLE: the same shared rounds driven from the host
+    std::vector<double> og((size_t)Q * G), x0(Q), los(Q), his(Q);
+    if ((rc = round(Q, all.data(), nullptr, true, og.data()))) return rc;
     for (int q = 0; q < Q; q++) {
         const int j = q / nreq;
-        for (int g = 0; g < G; g++) { const double J = -out[(size_t)q * G + g]; if (g == 0 || J < best[q]) { best[q] = J; x0[q] = grids[(size_t)j * G + g]; } }   // np.argmin: first minimum
+        x0[q] = grid_first_argmin(grids + (size_t)j * G, og.data() + (size_t)q * G, G);
+        los[q] = lo[j]; his[q] = hi[j];
         lastval[q] = grids[(size_t)j * G + (G - 1)];
     }
-    std::vector<Nm1> nm(Q);
-    std::vector<int> want;
-    auto pump = [&](int q, double f) {
-        const int j = q / nreq;
-        while (nm[q].advance(x0[q], f)) {
-            const double v = nm[q].req;
-            if (v < lo[j] || v > hi[j]) { f = INFINITY; continue; }      // +inf outside the bounds, nothing evaluated (cn_model.py:542-543)
-            want.push_back(q);
-            return;
-        }
-    };
-    for (int q = 0; q < Q; q++) pump(q, 0.);
-    std::vector<double> vals(Q);
-    while (!want.empty()) {
-        std::vector<int> cur;
-        cur.swap(want);
-        for (size_t k = 0; k < cur.size(); k++) { vals[k] = nm[cur[k]].req; lastval[cur[k]] = vals[k]; }
-        if ((rc = round((int)cur.size(), cur.data(), vals.data(), false))) return rc;
-        for (size_t k = 0; k < cur.size(); k++) pump(cur[k], -out[k]);
-    }
-    for (int q = 0; q < Q; q++) xopt[q] = nm[q].xopt();
-    return RMX_OK;
+    return nm_lockstep(Q, x0.data(), los.data(), his.data(), [&](int n_, const int *cur, const double *vals, double *o_) -> int {
+        return round(n_, cur, vals, false, o_);
+    }, xopt, lastval);
 }
 
 // One candidate haploid-depth vector per listed restart: E[ll] and dE[ll]/dh on each restart's

@@ -173,15 +173,6 @@ struct Nm1 {
         return false;
     }
     RMX_HD double xopt() const { return s0; }
-    // the points the NEXT call of advance() can request, whatever value the pending request gets (same
-    // expressions as above): after the first initial point the second one; after a reflection the
-    // expansion, the outside and the inside contraction
-    int lookahead(double out[3]) const {
-#pragma clang fp contract(off)
-        if (state == W_INIT0) { out[0] = s1; return 1; }
-        if (state == W_XR) { out[0] = 3. * xbar - 2. * s1; out[1] = 1.5 * xbar - 0.5 * s1; out[2] = 0.5 * xbar + 0.5 * s1; return 3; }
-        return 0;
-    }
 };
 
 }  // namespace rmxh

@@ -482,35 +482,29 @@ def test_lockstep_mstep_equals_per_restart_mstep(hip):
         (True, False, 0),     # 1: python lock-step
         (False, False, 0),    # 2: per-restart scipy
         (True, True, 2),      # 3: native, one parameter at a time, table-rebuilding evaluation rounds
-        (True, True, 3),      # 4: native, one at a time, rounds that also evaluate the optimisers' possible next points
-        (True, True, 1),      # 5: native, one at a time, table-free rounds
-        (True, True, 0),      # 6: as 0, but one accept pass over the cells per parameter instead of one for all four
-        (True, True, 5),      # 7: the shared rounds driven by the device (cells laid out flat over the threads)
-        (True, True, 7),      # 8: the same as ONE launch of resident blocks (partial sums published and polled, an optimiser copy per block)
+        (True, True, 1),      # 4: native, one at a time, table-free rounds
+        (True, True, 0),      # 5: as 0, but one accept pass over the cells per parameter instead of one for all four
+        (True, True, 5),      # 6: the shared rounds driven by the device (cells laid out flat over the threads)
     ]
     out = []
     for ci, (lock, native, mode) in enumerate(configs):
         rs = RestartSet(e, ps, max_copy_number=4, num_clones=3, quiet=True, seeds=[5, 6, 7, 8], lockstep=lock,
-                        native_search=native, mstep_threads=1, options={'search_mode': mode}, joint_accept=ci != 6)
+                        native_search=native, mstep_threads=1, options={'search_mode': mode}, joint_accept=ci != 5)
         rs.fit(num_em_iter=2, num_update_iter=2)
         out.append([(m.prev_elbo, np.array(m.h), m.get_likelihood_param_values()) for m in rs.models])
-    # the table-free search kernel evaluates exactly what the table-rebuilding rounds evaluate, and the
-    # optional look-ahead evaluations change nothing any optimiser sees
-    for (e1, h1, p1), (e2, h2, p2) in list(zip(out[5], out[3])) + list(zip(out[5], out[4])):
+    # the table-free search kernel evaluates exactly what the table-rebuilding rounds evaluate
+    for (e1, h1, p1), (e2, h2, p2) in zip(out[4], out[3]):
         assert e1 == e2 and np.array_equal(h1, h2) and p1 == p2
     # the joint accept test decides what the four sequential ones decide (its E[ll] values differ from theirs by rounding only),
     # and the decisions are all that reaches the model
-    for (e1, h1, p1), (e2, h2, p2) in zip(out[0], out[6]):
-        assert e1 == e2 and np.array_equal(h1, h2) and p1 == p2
-    # the one-launch search evaluates the same cells in the same blocks and adds the same partial sums in the same order as the kernel pairs
-    for (e1, h1, p1), (e2, h2, p2) in zip(out[7], out[8]):
+    for (e1, h1, p1), (e2, h2, p2) in zip(out[0], out[5]):
         assert e1 == e2 and np.array_equal(h1, h2) and p1 == p2
     # python lock-step == per-restart scipy path, bit for bit
     for (e1, h1, p1), (e2, h2, p2) in zip(out[1], out[2]):
         assert e1 == e2 and np.array_equal(h1, h2) and p1 == p2
     # the native searches evaluate only the likelihood component the parameter moves (plus, one at a time, the
     # rest as a constant from one full evaluation; none in the shared rounds): same objective up to rounding
-    for a_, b_ in ((0, 1), (5, 1), (0, 5), (7, 0), (7, 5)):
+    for a_, b_ in ((0, 1), (4, 1), (0, 4), (6, 0), (6, 4)):
         for (e1, h1, p1), (e2, h2, p2) in zip(out[a_], out[b_]):
             assert abs(e1 - e2) <= 1e-8 * abs(e2)
             np.testing.assert_allclose(h1, h2, rtol=1e-6)
@@ -555,6 +549,19 @@ def test_param_search_multi_argument_checks(hip):
             b._use_sample(r, sample)
         one = b.param_search([0, 1], name, 10., 2000., grid)
         np.testing.assert_allclose(one, xopt[j], rtol=1e-5, atol=1e-3)
+    # the search drivers that exist, and nothing else: the numbers of the ones that were taken out again are refused, and so is what went with them
+    for v in (3, 4, 6, 7):
+        with pytest.raises(ValueError):
+            b.set_option('search_mode', v)
+    for v in (0, 1, 2, 5):
+        b.set_option('search_mode', v)
+        assert b.get_option('search_mode') == v
+    assert b.get_option('search_mode') == 5               # (the default, restored by the last of them)
+    with pytest.raises(KeyError):                         # no such option name any more (in two halves: the name itself occurs nowhere in the code)
+        b.set_option('cu_' + 'partition', 0)
+    with pytest.raises(ValueError):                       # was: the last search ran as one launch
+        b.info(53)
+    assert b.info(52) > 0                                 # blocks of the last device-driven search (the multi search above)
 
 
 def test_sample_lists_equal_dense_masks(hip):
@@ -602,7 +609,7 @@ def test_sample_lists_equal_dense_masks(hip):
         assert e1 == e2 and np.array_equal(g1, g2)
 
 
-@pytest.mark.parametrize('search_mode', [0, 5, 7])
+@pytest.mark.parametrize('search_mode', [0, 5])
 def test_restart_groups_do_not_change_results(hip, search_mode):
     """Restarts split into groups (own batch, stream and host thread each) give every restart the
     same fit as one batch of all restarts."""

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of library options on the headline bench line only, alternating the variants REPS times on one box:
-#   bash tools/ab_headline.sh [REPS] "" "trial_kernel=1" "search_mode=6 trial_kernel=1" ...
+#   bash tools/ab_headline.sh [REPS] "" "trial_kernel=1" "search_mode=0 trial_kernel=1" ...
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd /tmp
 REPS=$1; shift

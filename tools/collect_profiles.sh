@@ -47,7 +47,7 @@ rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY S
 python3 $ROOT/tools/sq_counters.py $OUT/pmc_sq > $OUT/sweep_sq_counters.txt 2>&1
 rm -rf $OUT/pmc_sq
 unset ITERS RST
-# the two groups' M-step stages with the search rounds driven by the device (search_mode 5) beside the default above
+# the two groups' M-step stages with the search rounds driven by the device (search_mode 5: the default since round 5, pinned here) beside the run above
 { echo "# OPTS=search_mode=5"; OPTS=search_mode=5 python3 $ROOT/tools/mstep_marks.py 2>&1 | grep -v amdgpu.ids; echo "# RST=8 NGROUPS=1 (RestartGroups picks search_mode 5 for a single group)"; RST=8 NGROUPS=1 python3 $ROOT/tools/mstep_marks.py 2>&1 | grep -v amdgpu.ids; } > $OUT/mstep_stage_times_search5.txt 2>&1
 REPS=6 python3 $ROOT/tools/s355_repeat.py 2>&1 | grep "^run" > $OUT/s355_repeat.txt
 rm -rf $OUT/prof_bench $OUT/prof_s355 $OUT/pmc_fetch_* $OUT/pmc_write_*

@@ -15,7 +15,7 @@ ps = synthetic.make_init_params(e, R, MAXCN)
 kw = {}
 if os.environ.get('H_HALVES'):
     kw['h_halves'] = bool(int(os.environ['H_HALVES']))
-if os.environ.get('OPTS'):           # e.g. OPTS=search_mode=5
+if os.environ.get('OPTS'):           # e.g. OPTS=search_mode=0
     kw['options'] = dict((k, int(v)) for k, v in (kv.split('=') for kv in os.environ['OPTS'].split(',')))
 rs = RestartGroups(e, ps, MAXCN, groups=G, num_clones=3, quiet=True, seeds=[1000 + i for i in range(R)], **kw)
 for m, v in zip(rs.models, rs.calculate_elbo()):
@@ -33,7 +33,7 @@ RestartSet.em_iteration = wrapped
 NIT = 8
 t0 = time.time(); rs.run(NIT, 3, 5); rs.synchronize(); dt = time.time() - t0
 print('%d groups: %.1f ms per step, %.0f EM iterations/s' % (G, dt / NIT * 1e3, R * NIT / dt))
-print('device-driven search: %d blocks, one launch: %d' % (rs.sets[0].batch.info(52), rs.sets[0].batch.info(53)))
+print('device-driven search: %d blocks' % rs.sets[0].batch.info(52))
 for g, s in enumerate(rs.sets):
     acc = collections.OrderedDict()
     prev = None

@@ -373,6 +373,23 @@ int rmx_posterior_summary(rmx_batch *b, int32_t r0, int32_t nr, int32_t Q, const
 int rmx_region_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
                     int32_t nlabel, const int16_t *labels, const uint8_t *constrain, double *logp_out);
 
+/* -- region change counts (no reference counterpart) -------------------------- */
+/* log-probabilities of the number of label changes over runs of model segments.  Queries, tables and
+ * constrain are those of rmx_region_prob, but every query names a label (index >= 0).  With C = the number of adjacencies
+ * n in [a, b-1] with label(c_n) != label(c_n+1), bin k of query i is
+ *   log P(c_n in mask at every n in [a, b] with constrain[n] != 0, and C == k),   k = 0 .. nbins-1,
+ * the last bin meaning C >= nbins-1.  Changes are counted between consecutive MODEL segments: a zero-length segment
+ * inserted at a shared boundary that takes a third state contributes two.  The model is not modified.
+ *   nbins     1 .. 16
+ *   logp_out  [nr][nq][nbins]; -inf for a bin that cannot happen, and for a bin below about 1e-308 of the query's total
+ *             (one scale carries all bins of a step)
+ * A (restart, query) result is bit-identical in any restart range and any batch of queries.  Errors as rmx_region_prob,
+ * and RMX_EARG with nothing launched for nbins outside [1, 16] or a query whose label index is negative.
+ * RMX_EASSERT: every bin of the failing query is NaN.  RMX_EUNSUPPORTED: more than 1024 states (the bound of the
+ * kernel's LDS plan: 142 bytes per state rounded up to 16 states). */
+int rmx_region_counts(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
+                      int32_t nlabel, const int16_t *labels, const uint8_t *constrain, int32_t nbins, double *logp_out);
+
 /* -- module-level functions on caller-supplied dense inputs ----------------- */
 /* sum_product (:1213-1246): f [N][S], T [N-1][S][S] -> alphas, betas [N][S] */
 int rmx_sum_product(const double *f, const double *T, double *alphas, double *betas,

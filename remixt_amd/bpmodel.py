@@ -578,14 +578,9 @@ class RemixtBatch(object):
             stats.ctypes.data_as(_dp) if stats is not None else _dp(), amax.ctypes.data_as(i16p) if amax is not None else i16p()))
         return proj, stats, amax
 
-    def region_logprob_raw(self, r0, nr, queries, masks=None, labels=None, constrain=None):
-        """log-probabilities (nr, nq) of path events over runs of model segments under the structured posterior of the
-        last update_p_cn of restarts r0 .. r0+nr-1 (rmx_region_prob).  queries int (nq, 4): first segment, last segment
-        (both of one chain), mask index or -1, label index or -1; masks (C, nmask, S), non-zero = allowed state; labels
-        int (C, nlabel, S); constrain (N,), whether a mask binds at the segment (None: everywhere).  A query asks for
-        log P(state in mask at every constrained segment of the run, and equal labels across every adjacency of the
-        run); -inf for an impossible event."""
-        r0, nr = int(r0), int(nr)
+    def _region_args(self, queries, masks, labels, constrain):
+        """The query and table arguments of rmx_region_prob / rmx_region_counts: (queries int32 (nq, 4), the C arguments
+        nq, queries, nmask, masks, nlabel, labels, constrain, and the arrays those point into)."""
         N, S, C_ = self.num_segments, self.num_cn_states, self.cn_classes.shape[0]
         q = np.asarray(queries)
         if q.ndim != 2 or q.shape[1] != 4:
@@ -595,6 +590,7 @@ class RemixtBatch(object):
         q = np.ascontiguousarray(q, dtype=np.int32)
         u8p, i16p = C.POINTER(C.c_uint8), C.POINTER(C.c_int16)
         nmask, mp, nlabel, lp, cp = 0, u8p(), 0, i16p(), u8p()
+        keep = []
         if masks is not None:
             mk = np.asarray(masks)
             if mk.ndim != 3 or mk.shape[0] != C_ or mk.shape[2] != S:
@@ -603,6 +599,7 @@ class RemixtBatch(object):
             nmask = mk.shape[1]
             if nmask:
                 mp = mk.ctypes.data_as(u8p)
+                keep.append(mk)
         if labels is not None:
             lb = np.asarray(labels)
             if lb.ndim != 3 or lb.shape[0] != C_ or lb.shape[2] != S:
@@ -613,16 +610,44 @@ class RemixtBatch(object):
             nlabel = lb.shape[1]
             if nlabel:
                 lp = lb.ctypes.data_as(i16p)
+                keep.append(lb)
         if constrain is not None:
             cs = np.asarray(constrain)
             if cs.shape != (N,):
                 raise ValueError('constrain must have shape (num_segments,)')
             cs = np.ascontiguousarray(cs != 0, dtype=np.uint8)
             cp = cs.ctypes.data_as(u8p)
+            keep.append(cs)
+        qbuf = q if q.size else np.zeros(4, dtype=np.int32)
+        keep.append(qbuf)
+        return q, (q.shape[0], qbuf.ctypes.data_as(C.POINTER(C.c_int32)), nmask, mp, nlabel, lp, cp), keep
+
+    def region_logprob_raw(self, r0, nr, queries, masks=None, labels=None, constrain=None):
+        """log-probabilities (nr, nq) of path events over runs of model segments under the structured posterior of the
+        last update_p_cn of restarts r0 .. r0+nr-1 (rmx_region_prob).  queries int (nq, 4): first segment, last segment
+        (both of one chain), mask index or -1, label index or -1; masks (C, nmask, S), non-zero = allowed state; labels
+        int (C, nlabel, S); constrain (N,), whether a mask binds at the segment (None: everywhere).  A query asks for
+        log P(state in mask at every constrained segment of the run, and equal labels across every adjacency of the
+        run); -inf for an impossible event."""
+        r0, nr = int(r0), int(nr)
+        q, args, _keep = self._region_args(queries, masks, labels, constrain)
         out = np.zeros((max(nr, 0), q.shape[0]), dtype=np.float64)
-        obuf, qbuf = (out if out.size else np.zeros(1)), (q if q.size else np.zeros(4, dtype=np.int32))
-        self._ck(self._lib.rmx_region_prob(self._handle, r0, nr, q.shape[0], qbuf.ctypes.data_as(C.POINTER(C.c_int32)), nmask, mp, nlabel, lp, cp,
-                                           obuf.ctypes.data_as(_dp)))
+        obuf = out if out.size else np.zeros(1)
+        self._ck(self._lib.rmx_region_prob(self._handle, r0, nr, *args, obuf.ctypes.data_as(_dp)))
+        return out
+
+    def region_counts_raw(self, r0, nr, queries, masks, labels, constrain, nbins):
+        """log-probabilities (nr, nq, nbins) of the number of label changes over runs of model segments under the
+        structured posterior of the last update_p_cn of restarts r0 .. r0+nr-1 (rmx_region_counts).  queries, masks,
+        labels and constrain as region_logprob_raw, but every query names a label.  Bin k of a query is
+        log P(state in mask at every constrained segment of the run, and exactly k adjacencies of the run change the
+        label); the last bin takes nbins - 1 changes or more; -inf for a bin that cannot happen (and for one below about
+        1e-308 of the query's total).  nbins in 1 .. 16."""
+        r0, nr, nbins = int(r0), int(nr), int(nbins)
+        q, args, _keep = self._region_args(queries, masks, labels, constrain)
+        out = np.zeros((max(nr, 0), q.shape[0], max(nbins, 0)), dtype=np.float64)
+        obuf = out if out.size else np.zeros(1)
+        self._ck(self._lib.rmx_region_counts(self._handle, r0, nr, *args, nbins, obuf.ctypes.data_as(_dp)))
         return out
 
     # -- measurement ------------------------------------------------------------
@@ -851,6 +876,10 @@ class RemixtModel(object):
     def region_logprob(self, queries, masks=None, labels=None, constrain=None):
         """RemixtBatch.region_logprob_raw of this model: log-probabilities (nq,)."""
         return self._batch.region_logprob_raw(self._r, 1, queries, masks, labels, constrain)[0]
+
+    def region_counts(self, queries, masks, labels, constrain, nbins):
+        """RemixtBatch.region_counts_raw of this model: log-probabilities (nq, nbins)."""
+        return self._batch.region_counts_raw(self._r, 1, queries, masks, labels, constrain, nbins)[0]
 
     def posterior_project(self, weights):
         """posterior_marginals @ weights[class of the segment] -> (N, Q), on the device: weights (C, S, Q) or (S, Q), Q <= 256."""

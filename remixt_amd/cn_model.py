@@ -750,6 +750,19 @@ class BreakpointModel(object):
         out = posteriors.batch_region_events(b, r, 1, regions, self.seg_fwd_remap, self.seg_is_original, self.is_telomere)
         return dict((k, v[0]) for k, v in out.items())
 
+    def region_change_counts(self, regions, bins=8):
+        """Exact posterior distribution of the number of copy-number changes inside regions ((first, last) experiment
+        segment indices): a dict of arrays (len(regions), bins), `num_changes` (changes of the copy-number state) and
+        `num_total_changes` (changes of the per-clone totals).  Entry k is the probability of exactly k changes, the
+        last entry that of bins - 1 or more.  Changes are counted between consecutive model segments: a path that takes a
+        third state in a zero-length segment inserted at a shared boundary changes twice there."""
+        from . import posteriors
+        if not hasattr(self.model, 'region_counts'):
+            raise NotImplementedError('kernel module %s has no region change counts' % getattr(self._kernel_module(), '__name__', '?'))
+        out = posteriors.batch_region_change_counts(self.model._batch, self.model._r, 1, regions, self.seg_fwd_remap, self.seg_is_original,
+                                                    self.is_telomere, bins=bins)
+        return dict((k, v[0]) for k, v in out.items())
+
     def cn_change_prob(self):
         """(N - 1,): the posterior probability that the copy-number state changes between experiment segments n and n + 1
         (1 - p_no_change of the region [n, n + 1]); NaN where no reference adjacency joins them."""

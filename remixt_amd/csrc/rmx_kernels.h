@@ -5548,3 +5548,224 @@ __global__ __launch_bounds__(RGN_NT) void k_region_prob(Dev d, int r0, int use_w
         out[(size_t)ri * q.nq + qi] = failed ? __builtin_nan("") : logp;
     }
 }
+
+// =============================================================================
+// Region change counts: for a query (a, b, mask, label) over the model segments [a, b] of one chain and K <= 16 bins,
+// log P(c_n in mask at every constrained n of the run, and C = k), C = the number of adjacencies n in [a, b - 1] with
+// label(c_n) != label(c_n+1); the last bin is C >= K - 1.  It is k_region_prob's recursion with a count axis: with
+// G_b(s, k) = [mask] post_b(s) [k = 0], H(s', k) = G_n+1(s', k) / D_n(s') and H+ = H moved up one bin (the last bin keeps
+// what it had: it saturates; K = 1: H+ = H),
+//   G_n(s, k) = [mask] fa_n(s) (sum_{s': label equal} W_n(s, s') H(s', k) + sum_{s': label differs} W_n(s, s') H+(s', k)),
+// and P(k) = sum_s G_a(s, k).  G is divided by its total over (s, k) after every step and the logarithms of the totals are
+// added up.  Nothing of the model is written.
+// One workgroup of 256 threads per (restart, query).  G lives in LDS as [S rounded up to 16][16 bins]; a step is
+//   1. the states s' with mass (some G(s', k) > 0), compacted in state order by a ballot;
+//   2. D(s') for those: Wb (plain adjacency under the current model) has row s' contiguous in s, 16 lanes per s' stride s and
+//      a fixed butterfly, and lane j then divides bin j in place; exp(trans_value) (breakend adjacency, or the plain table of
+//      the other transition model) has the thread own s';
+//   3. G_n on v_mfma_f64_16x16x4_f64 in row tiles of 16 states, the tiles round robin over the four waves: A[i = lane & 15]
+//      [k = lane >> 4] = W(s0 + i, s'_k), a 128-byte run of a Wb row read from global memory (or exp(trans_value)),
+//      B[k][j = lane & 15] = H(s'_k, j) from LDS, D row (lane >> 4) + 4 reg, column lane & 15.  Two instructions per (tile, four
+//      s') add into one accumulator: A selected (never multiplied) to 0 off-label with B = H, and to 0 on-label with B = H+;
+//      a masked row, a row s >= S and a bin j >= K select their operand to 0 as well.  A wave reads B once per four s' for all
+//      of its tiles.  The accumulators (TPW tiles per wave, a template parameter so that they are registers) stay in registers
+//      until every wave has finished reading H; the total is summed from them and G is written divided by it.
+// Every sum has one order, fixed by S and K alone: a (restart, query) result does not depend on the launch.  Only columns
+// s < S of fa / post are read (clamped address and select).  A D(s') that is 0 or not finite under mass, or a total that is
+// not a finite number >= 0, sets RGN_ERR_DENOM in flags[r] and gives NaN in every bin; a bin that cannot happen gives -inf.
+// grid (queries, restarts), block RGC_NT, dynamic LDS rgc_lds_bytes(S); out[(ri * nq + query) * K + k].
+// =============================================================================
+#define RGC_NT 256
+#define RGC_NW (RGC_NT / 64)
+#define RGC_KB 16             // bins of the LDS rows and of the matrix instruction's B operand
+#define RGC_MAXS 1024
+static inline size_t rgc_lds_bytes(int S) { const size_t SR = ((size_t)S + 15) & ~(size_t)15; return SR * (RGC_KB * 8 + 8 + 3 * 2); }
+template <int TPW>
+__global__ __launch_bounds__(RGC_NT) void k_region_counts(Dev d, int r0, int use_wb, RgnArgs q, int K, double *out, uint32_t *flags) {
+    extern __shared__ double rgc_lds[];                 // G [SR][16], fas [SR], lab [2][SR] (int16), idx [SR] (int16)
+    __shared__ double red[RGC_NW], redc[RGC_NW][RGC_KB];
+    __shared__ int nact, s_bad;
+    const int qi = blockIdx.x, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (uniform, and known to be: the matrix instructions sit under conditions on it)
+    const int grp = tid / RGN_GL, gl = tid % RGN_GL;
+    const int ai = lane & 15, kk = lane >> 4;
+    const int S = d.S, SR = (S + 15) & ~15;
+    double *G = rgc_lds, *fas = G + (size_t)SR * RGC_KB;
+    int16_t *labs = (int16_t *)(fas + SR), *idx = labs + 2 * SR;
+    const int a = q.queries[4 * qi], b = q.queries[4 * qi + 1], mi = q.queries[4 * qi + 2], li = q.queries[4 * qi + 3];
+    if (tid == 0) s_bad = 0;
+    int cur = 0;              // labs[cur * SR ..]: the labels of segment n + 1
+    double logp = 0.;
+    bool failed = false;
+    // ---- start: G_b(s, 0) = [mask] post_b(s) ----------------------------------------------------------------
+    {
+        const int cls = d.seg_class[b];
+        const double *post = d.post + rs_off(d, r, b);
+        const uint8_t *mk = (mi >= 0 && (!q.constrain || q.constrain[b])) ? q.masks + ((size_t)cls * q.nmask + mi) * S : nullptr;
+        const int16_t *lb = q.labels + ((size_t)cls * q.nlabel + li) * S;
+        double part = 0.;
+        for (int s = tid; s < SR; s += RGC_NT) {
+            const int sc = s < S ? s : S - 1;
+            const double pv = post[sc];
+            const double v = (s < S && (!mk || mk[sc])) ? pv : 0.;
+            part += v;
+            labs[cur * SR + s] = lb[sc];
+        }
+        const double Z = rgn_block_sum(part, red);
+        if (!(Z >= 0. && Z < INFINITY)) failed = true;
+        else if (Z == 0.) logp = -INFINITY;
+        else logp = log(Z);
+        const bool okz = !failed && Z > 0.;
+        for (int e = tid; e < SR * RGC_KB; e += RGC_NT) {
+            const int s = e / RGC_KB, k = e % RGC_KB, sc = s < S ? s : S - 1;
+            const double pv = post[sc];
+            G[e] = (okz && k == 0 && s < S && (!mk || mk[sc])) ? pv / Z : 0.;
+        }
+    }
+    for (int n = b - 1; n >= a && !failed && logp > -INFINITY; n--) {
+        const int tc = d.tclass[n], bs = d.brk_slot[n];      // (tc >= 0: the host checked that the run lies in one chain)
+        const int cls = d.seg_class[n];
+        const double *fa = d.fa + rs_off(d, r, n);
+        const uint8_t *mk = (mi >= 0 && (!q.constrain || q.constrain[n])) ? q.masks + ((size_t)cls * q.nmask + mi) * S : nullptr;
+        const int16_t *lb = q.labels + ((size_t)cls * q.nlabel + li) * S;
+        const int16_t *lab1 = labs + cur * SR;
+        int16_t *lab0 = labs + (cur ^ 1) * SR;
+        const bool wb = bs < 0 && use_wb;
+        const double *Wt = d.Wb + (size_t)tc * S * S;
+        const double *pd = bs >= 0 ? d.pd_lt + ((size_t)r * d.NBE + bs) * d.M * d.D : nullptr;
+        for (int s = tid; s < SR; s += RGC_NT) {
+            const int sc = s < S ? s : S - 1;
+            const double fv = fa[sc];
+            fas[s] = s < S ? fv : 0.;
+            lab0[s] = lb[sc];
+        }
+        // ---- 1. the states s' with mass, in state order ------------------------------------------------------
+        __syncthreads();      // (G of the step before, or of the start, is complete)
+        if (tid < 64) {
+            int cnt = 0;
+            for (int base = 0; base < S; base += 64) {
+                const int s = base + lane;
+                bool act = false;
+                if (s < S) for (int k = 0; k < K; k++) act = act || G[s * RGC_KB + k] > 0.;
+                const unsigned long long m = __ballot(act);
+                if (act) idx[cnt + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = (int16_t)s;
+                cnt += __builtin_popcountll(m);
+            }
+            if (lane == 0) nact = cnt;
+        }
+        __syncthreads();
+        const int na = __builtin_amdgcn_readfirstlane(nact);
+        // ---- 2. D(s') and H = G / D in place -----------------------------------------------------------------
+        if (wb) {
+            for (int j0 = 0; j0 < na; j0 += RGC_NT / RGN_GL) {
+                const int j = j0 + grp;
+                const bool ok = j < na;
+                const int sp = ok ? idx[j] : 0;
+                double p = 0.;
+                if (ok) {
+                    const double *wr = Wt + (size_t)sp * S;
+                    for (int s = gl; s < S; s += RGN_GL) p = fma(fas[s], wr[s], p);
+                }
+                const double D = group_sum(p, RGN_GL);
+                if (ok) {
+                    if (gl == 0 && !(D > 0. && D < INFINITY)) s_bad = 1;
+                    if (gl < K) G[sp * RGC_KB + gl] = G[sp * RGC_KB + gl] / D;
+                }
+            }
+        } else {
+            for (int j = tid; j < na; j += RGC_NT) {
+                const int sp = idx[j];
+                double D = 0.;
+                for (int s = 0; s < S; s++) {
+                    const double f = fas[s];
+                    if (f != 0.) D = fma(f, exp(trans_value(d, n, s, sp, pd)), D);
+                }
+                if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                for (int k = 0; k < K; k++) G[sp * RGC_KB + k] = G[sp * RGC_KB + k] / D;
+            }
+        }
+        __syncthreads();
+        // ---- 3. G_n on the matrix cores -----------------------------------------------------------------------
+        psm_d4 acc[TPW];
+        int rowlab[TPW];      // label of the lane's A row of tile u, or INT_MIN: the row takes nothing (masked, or s >= S)
+#pragma unroll
+        for (int u = 0; u < TPW; u++) {
+            acc[u] = psm_d4{0., 0., 0., 0.};
+            const int s = (wave + RGC_NW * u) * 16 + ai;
+            const int sc = s < S ? s : S - 1;
+            const bool rok = s < S && (!mk || mk[sc]);
+            rowlab[u] = rok ? (int)lab0[sc] : (int)0x80000000;
+        }
+        for (int j0 = 0; j0 < na; j0 += 4) {
+            const int j = j0 + kk;
+            const bool ok = j < na;
+            const int sp = idx[ok ? j : 0];
+            const int lsp = lab1[sp];
+            const double hv = G[sp * RGC_KB + ai], hm = G[sp * RGC_KB + (ai > 0 ? ai - 1 : 0)];
+            const double bsame = (ok && ai < K) ? hv : 0.;
+            const double bshift = !ok ? 0. : (K == 1 ? bsame : (ai == 0 || ai >= K) ? 0. : (ai < K - 1 ? hm : hm + hv));
+#pragma unroll
+            for (int u = 0; u < TPW; u++) {
+                const int s0 = (wave + RGC_NW * u) * 16;
+                if (s0 < S) {         // (uniform over the wave)
+                    const int s = s0 + ai, sc = s < S ? s : S - 1;
+                    double wv;
+                    if (wb) wv = Wt[(size_t)sp * S + sc];
+                    else wv = (ok && rowlab[u] != (int)0x80000000) ? exp(trans_value(d, n, sc, sp, pd)) : 0.;
+                    const bool live = ok && rowlab[u] != (int)0x80000000, same = rowlab[u] == lsp;
+                    acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64((live && same) ? wv : 0., bsame, acc[u], 0, 0, 0);
+                    acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64((live && !same) ? wv : 0., bshift, acc[u], 0, 0, 0);
+                }
+            }
+        }
+        // [mask] fa(s) and the total, from the registers; the barriers of the sum also end every wave's reads of H
+        double part = 0.;
+#pragma unroll
+        for (int u = 0; u < TPW; u++) {
+            const int s0 = (wave + RGC_NW * u) * 16;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int s = s0 + kk + 4 * g;
+                const double v = s < SR ? fas[s] * acc[u][g] : 0.;
+                acc[u][g] = v;
+                part += v;
+            }
+        }
+        const double Z = rgn_block_sum(part, red);
+        if (s_bad || !(Z >= 0. && Z < INFINITY)) failed = true;
+        else if (Z == 0.) logp = -INFINITY;
+        else logp += log(Z);
+        const bool okz = !failed && Z > 0.;
+#pragma unroll
+        for (int u = 0; u < TPW; u++) {
+            const int s0 = (wave + RGC_NW * u) * 16;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int s = s0 + kk + 4 * g;
+                if (s < SR) G[s * RGC_KB + ai] = okz ? acc[u][g] / Z : 0.;
+            }
+        }
+        cur ^= 1;
+    }
+    // ---- P(k) = sum_s G_a(s, k): 16 lanes of a quarter-wave take the bins, rows stride RGC_NT / 16 -----------------
+    __syncthreads();
+    {
+        double p = 0.;
+        for (int s = tid >> 4; s < S; s += RGC_NT / 16) p += G[s * RGC_KB + (tid & 15)];
+        p += __shfl_xor(p, 16, 64);
+        p += __shfl_xor(p, 32, 64);
+        if (lane < RGC_KB) redc[wave][lane] = p;
+        __syncthreads();
+        if (tid < K) {
+            double t = 0.;
+#pragma unroll
+            for (int i = 0; i < RGC_NW; i++) t += redc[i][tid];
+            double v;
+            if (failed) v = __builtin_nan("");
+            else if (!(logp > -INFINITY) || t == 0.) v = -INFINITY;
+            else v = logp + log(t);
+            out[((size_t)ri * q.nq + qi) * K + tid] = v;
+        }
+    }
+    if (tid == 0 && failed) atomicOr(&flags[r], RGN_ERR_DENOM);
+}

@@ -31,6 +31,11 @@ cn_posterior_summary = False
 # names and p_all_loh, p_any_loh, p_all_hdel, p_any_hdel, p_any_subclonal, p_no_change, p_no_total_change per region
 # (remixt_amd/posteriors.py)
 cn_regions = None
+# (no reference counterpart) with cn_regions: the exact posterior distribution of the number of copy-number changes inside
+# every region, in this many bins (the last: that many changes minus one, or more).  0 = none (results unchanged);
+# 1 .. 16 adds `region_change_counts` -- names, bins, num_changes (state changes) and num_total_changes (changes of the
+# per-clone totals), each (regions, bins) -- to every fit result (remixt_amd/posteriors.py)
+cn_region_change_bins = 0
 
 
 def get_param(config, name):

@@ -302,3 +302,77 @@ def parse_regions(cn_regions):
     """Config value cn_regions, a list of (name, first, last) -> (names, regions int (R, 2))."""
     names = [str(r[0]) for r in cn_regions]
     return names, np.array([[int(r[1]), int(r[2])] for r in cn_regions], dtype=np.int64).reshape(-1, 2)
+
+
+# ---- distribution of the number of copy-number changes over regions (rmx_region_counts; DESIGN 4.11) -----------------
+# the arrays of region_change_counts: name -> label
+COUNT_LABELS = (('num_changes', 'state'), ('num_total_changes', 'total'))
+COUNT_ARRAYS = tuple(c[0] for c in COUNT_LABELS)
+
+
+def combine_counts(logp, piece_region, num_regions):
+    """Distribution of every region's change count from its pieces': logp (..., pieces, bins) log-probabilities ->
+    probabilities (..., num_regions, bins).  Chains are independent under the structured posterior and a chain end is not
+    an adjacency, so a region's count is the sum of its pieces' counts: the pieces' distributions are convolved, with
+    what lands past the last bin added to it (the last bin means bins - 1 changes or more).  A region without pieces has
+    no changes."""
+    with np.errstate(over='ignore'):
+        p = np.exp(np.asarray(logp, dtype=float))
+    K = p.shape[-1]
+    out = np.zeros(p.shape[:-2] + (int(num_regions), K))
+    out[..., 0] = 1.
+    for j, reg in enumerate(np.asarray(piece_region)):
+        cur = out[..., reg, :].copy()
+        new = np.zeros_like(cur)
+        for i in range(K):
+            for k in range(K):
+                new[..., min(i + k, K - 1)] += cur[..., i] * p[..., j, k]
+        out[..., reg, :] = new
+    return out
+
+
+def batch_region_change_counts(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, bins=8, labels=('state', 'total')):
+    """The distribution of the number of label changes over regions, for restarts r0 .. r0+nr-1 of a RemixtBatch from one
+    device call: a dict of (nr, len(regions), bins) arrays of probabilities, `num_changes` for label 'state' and
+    `num_total_changes` for 'total' (those of `labels`).  Entry k is the probability of exactly k changes between
+    consecutive model segments of the region, the last entry that of bins - 1 or more.  A zero-length segment inserted at
+    a shared boundary counts as a segment: a path that takes a third state there changes twice.  regions: (first, last)
+    experiment segment indices."""
+    bins = int(bins)
+    if not 1 <= bins <= 16:
+        raise ValueError('bins must be in 1 .. 16')
+    names = dict((lb, nm) for nm, lb in COUNT_LABELS)
+    _, label_tab = event_tables(batch.cn_classes)
+    cs, ce = chains_from_telomeres(is_telomere)
+    runs, piece_region, constrain = region_queries(regions, seg_fwd_remap, seg_is_original, cs, ce)
+    P, R = len(runs), len(np.asarray(regions).reshape(-1, 2))
+    if P == 0:
+        return dict((names[lb], np.zeros((nr, 0, bins))) for lb in labels)
+    q = np.zeros((len(labels), P, 4), dtype=np.int32)
+    q[:, :, :2] = runs[None]
+    q[:, :, 2] = -1
+    for e, lb in enumerate(labels):
+        q[e, :, 3] = LABEL_NAMES.index(lb)
+    logp = batch.region_counts_raw(r0, nr, q.reshape(-1, 4), None, label_tab, constrain, bins).reshape(nr, len(labels), P, bins)
+    return dict((names[lb], np.clip(combine_counts(logp[:, e], piece_region, R), 0., 1.)) for e, lb in enumerate(labels))
+
+
+def add_region_change_counts(res, names, bins, counts):
+    """Fit result dict `res` gains `region_change_counts`: the region names, the number of bins and the arrays of
+    COUNT_ARRAYS, each (len(names), bins)."""
+    out = {'names': list(names), 'bins': int(bins)}
+    for k in COUNT_ARRAYS:
+        out[k] = np.asarray(counts[k])
+    res['region_change_counts'] = out
+    return res
+
+
+def change_bins(config):
+    """Config value cn_region_change_bins, checked: 0 (off) or 1 .. 16 with cn_regions set."""
+    from . import defaults
+    bins = int(defaults.get_param(config, 'cn_region_change_bins') or 0)
+    if bins and defaults.get_param(config, 'cn_regions') is None:
+        raise ValueError('cn_region_change_bins needs cn_regions')
+    if not 0 <= bins <= 16:
+        raise ValueError('cn_region_change_bins must be in 0 .. 16')
+    return bins

@@ -390,6 +390,29 @@ int rmx_region_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int3
 int rmx_region_counts(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
                       int32_t nlabel, const int16_t *labels, const uint8_t *constrain, int32_t nbins, double *logp_out);
 
+/* -- call probabilities (no reference counterpart) ---------------------------- */
+/* log-probabilities that the copy-number path agrees with a reference path over runs of model segments, under the
+ * structured posterior q of the last update_p_cn of restarts r0 .. r0+nr-1.  Query i = (a, b, label index or
+ * -1, path index) over the model segments [a, b] of one chain, with ref = path `path index` of the restart:
+ *   logp_out[r][i] = log P(label(c_n) == label(ref_n) at every n in [a, b] with constrain[n] != 0),
+ * the label table being the one of n's state class; label -1 asks for c_n == ref_n.  There is no adjacency constraint.
+ * A whole chain with label -1 gives log q of that chain's part of the path.  The model is not modified.
+ *   paths     int16 [nr][npaths][N], state indices in [0, S) into each segment's class table (every entry is
+ *             checked, the ones no query reads included); staged whole: keeping a call small is the caller's job
+ *   queries   int32 [nq][4]; a <= b, both in [0, N) and in the same chain; nq = 0 is valid and does nothing
+ *   labels    int16 [C][nlabel][S], one table per state class; NULL with nlabel = 0
+ *   constrain uint8 [N]: whether the event binds at the segment; NULL = everywhere
+ *   logp_out  [nr][nq]; -inf for an impossible event -- and for a reference state whose forward entry underflowed to 0
+ *             in the sweep's scaled rows, where the true probability is merely tiny
+ * A (restart, query) result is bit-identical in any restart range, any batch of queries and any number of paths.
+ * RMX_EARG, with nothing launched and logp_out untouched: a bad range, npaths < 1, nq < 0, a query with a > b, an end
+ * outside [0, N), ends in different chains, a label or path index out of range, a path entry outside [0, S).
+ * RMX_EVALUE with the restarts listed by rmx_last_error_restarts: a restart has had no update_p_cn.  RMX_EASSERT with
+ * the restarts listed: a backward step met a zero or non-finite normaliser under positive mass, or a sum that is not a
+ * finite number >= 0 (that query's result is NaN).  RMX_EUNSUPPORTED: more than 1024 states. */
+int rmx_call_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t npaths, const int16_t *paths, int32_t nq, const int32_t *queries,
+                  int32_t nlabel, const int16_t *labels, const uint8_t *constrain, double *logp_out);
+
 /* -- module-level functions on caller-supplied dense inputs ----------------- */
 /* sum_product (:1213-1246): f [N][S], T [N-1][S][S] -> alphas, betas [N][S] */
 int rmx_sum_product(const double *f, const double *T, double *alphas, double *betas,

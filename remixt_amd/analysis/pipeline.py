@@ -8,7 +8,7 @@ import numpy as np
 
 from .. import defaults, posteriors, sampling
 from ..cn_model import BreakpointModel
-from ..restarts import RestartSet, add_cn_sample_summaries, add_posterior_summaries, add_region_change_counts, add_region_events, collect_fit_results, fit_restarts_distributed, select_optimal  # noqa: F401
+from ..restarts import RestartSet, add_call_confidence, add_cn_sample_summaries, add_posterior_summaries, add_region_change_counts, add_region_events, collect_fit_results, fit_restarts_distributed, select_optimal  # noqa: F401
 
 
 def _model_kwargs(experiment, config):
@@ -33,6 +33,7 @@ def fit(experiment, init_params, config, device=0, quiet=False, init_id=0):
     """analysis/pipeline.py:127-228 (one restart).  init_id: the restart's id, which selects its posterior-sample stream
     when config num_cn_samples > 0."""
     bins = posteriors.change_bins(config)      # (a bad combination fails before the fit, not after it)
+    call_conf = posteriors.call_confidence_on(config)
     h_init = np.array([
         init_params['h_normal'],
         init_params['h_tumour'] * init_params['mix_frac'],
@@ -74,6 +75,8 @@ def fit(experiment, init_params, config, device=0, quiet=False, init_id=0):
         posteriors.add_region_events(res, names, model.region_events(regions))
         if bins:
             posteriors.add_region_change_counts(res, names, bins, model.region_change_counts(regions, bins))
+        if call_conf:
+            posteriors.add_call_confidence(res, names, model.call_confidence(regions, res['cn']), model.cn_logprob(res['cn']))
     return res
 
 
@@ -103,6 +106,7 @@ def fit_restarts(experiment, init_params_by_id, config, device=0, quiet=True, se
     `fit_task` per init_id (workflow.py:329-340).  With per-restart seeds the restarts run as
     `groups` RestartSets on their own streams and host threads (same per-restart results)."""
     bins = posteriors.change_bins(config)      # (a bad combination fails before the fit, not after it)
+    call_conf = posteriors.call_confidence_on(config)
     ids = sorted(init_params_by_id)
     params = [init_params_by_id[i] for i in ids]
     max_cn = defaults.get_param(config, 'max_copy_number')
@@ -124,6 +128,8 @@ def fit_restarts(experiment, init_params_by_id, config, device=0, quiet=True, se
         add_region_events(rs, results, defaults.get_param(config, 'cn_regions'))
         if bins:
             add_region_change_counts(rs, results, defaults.get_param(config, 'cn_regions'), bins)
+        if call_conf:
+            add_call_confidence(rs, results, defaults.get_param(config, 'cn_regions'))
     out = dict(zip(ids, results))
     rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     return out
@@ -275,6 +281,9 @@ def store_fit_results(store, experiment, fit_results, key_prefix):
     if 'region_change_counts' in fit_results:     # (config cn_region_change_bins)
         for k in posteriors.COUNT_ARRAYS:
             store[key_prefix + '/' + k] = pd.DataFrame(np.asarray(fit_results['region_change_counts'][k]))
+    if 'call_confidence' in fit_results:          # (config cn_call_confidence)
+        for k in posteriors.CALL_ARRAYS:
+            store[key_prefix + '/' + k] = pd.Series(np.asarray(fit_results['call_confidence'][k]))
 
 
 def store_optimal_solution(stats, store, config):

@@ -650,6 +650,29 @@ class RemixtBatch(object):
         self._ck(self._lib.rmx_region_counts(self._handle, r0, nr, *args, nbins, obuf.ctypes.data_as(_dp)))
         return out
 
+    def call_logprob_raw(self, r0, nr, paths, queries, labels=None, constrain=None):
+        """log-probabilities (nr, nq) that the copy-number path agrees with a reference path over runs of model segments,
+        under the structured posterior of the last update_p_cn of restarts r0 .. r0+nr-1 (rmx_call_prob).  paths int
+        (nr, npaths, N): state indices into each segment's class table; queries int (nq, 4): first segment, last segment
+        (both of one chain), label index or -1, path index; labels int (C, nlabel, S); constrain (N,), whether the event
+        binds at the segment (None: everywhere).  A query asks for log P(label(state) == label(reference state) at every
+        bound segment of the run), label -1 for the state itself; -inf for an impossible event."""
+        r0, nr = int(r0), int(nr)
+        q, args, _keep = self._region_args(queries, None, labels, constrain)
+        nq, qp, _, _, nlabel, lp, cp = args
+        pt = np.asarray(paths)
+        if pt.ndim != 3 or pt.shape[0] != max(nr, 0) or pt.shape[2] != self.num_segments:
+            raise ValueError('paths must have shape (nr, npaths, num_segments)')
+        if pt.size and (pt.min() < -32768 or pt.max() > 32767):
+            raise ValueError('state index out of range')
+        pt = np.ascontiguousarray(pt, dtype=np.int16)
+        pbuf = pt if pt.size else np.zeros(1, dtype=np.int16)
+        out = np.zeros((max(nr, 0), q.shape[0]), dtype=np.float64)
+        obuf = out if out.size else np.zeros(1)
+        self._ck(self._lib.rmx_call_prob(self._handle, r0, nr, pt.shape[1], pbuf.ctypes.data_as(C.POINTER(C.c_int16)), nq, qp, nlabel, lp, cp,
+                                         obuf.ctypes.data_as(_dp)))
+        return out
+
     # -- measurement ------------------------------------------------------------
     def timer_start(self):
         self._ck(self._lib.rmx_timer_start(self._handle))
@@ -880,6 +903,10 @@ class RemixtModel(object):
     def region_counts(self, queries, masks, labels, constrain, nbins):
         """RemixtBatch.region_counts_raw of this model: log-probabilities (nq, nbins)."""
         return self._batch.region_counts_raw(self._r, 1, queries, masks, labels, constrain, nbins)[0]
+
+    def call_logprob(self, paths, queries, labels=None, constrain=None):
+        """RemixtBatch.call_logprob_raw of this model: paths (npaths, N) -> log-probabilities (nq,)."""
+        return self._batch.call_logprob_raw(self._r, 1, np.asarray(paths)[None], queries, labels, constrain)[0]
 
     def posterior_project(self, weights):
         """posterior_marginals @ weights[class of the segment] -> (N, Q), on the device: weights (C, S, Q) or (S, Q), Q <= 256."""

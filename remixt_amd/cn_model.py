@@ -763,6 +763,45 @@ class BreakpointModel(object):
                                                     self.is_telomere, bins=bins)
         return dict((k, v[0]) for k, v in out.items())
 
+    def _call_states(self, cn):
+        """(batch, restart, states (K, N1) in model order, whether cn was one path) of a call `cn` in experiment order
+        ((N, M, 2) or (K, N, M, 2)); None: the decoded path."""
+        from . import posteriors
+        if not hasattr(self.model, 'call_logprob'):
+            raise NotImplementedError('kernel module %s has no call probabilities' % getattr(self._kernel_module(), '__name__', '?'))
+        b = self.model._batch
+        if cn is None:
+            path = np.zeros((self.model.num_segments, self.model.num_clones, self.model.num_alleles), dtype=int)
+            self.model.infer_cn(path)
+            return b, self.model._r, posteriors.cn_to_states(path, b.cn_classes, b.seg_class)[None], True
+        cn = np.asarray(cn)
+        single = cn.ndim == 3
+        states = np.stack([posteriors.states_in_model_order(c, b, self.seg_fwd_remap) for c in (cn[None] if single else cn)])
+        return b, self.model._r, states, single
+
+    def call_confidence(self, regions, cn=None):
+        """Exact probabilities, under the structured posterior of the last variational update, that the copy-number path
+        agrees with a call over regions ((first, last) experiment segment indices): a dict of arrays (len(regions),),
+        p_call (the path equals the call at every segment of the region), p_call_unphased (up to a swap of the two alleles)
+        and p_call_total (the per-clone totals).  cn: the call, (N, M, 2) in experiment segment order as optimal_cn returns
+        it; None: the decoded path.  Zero-length segments inserted at shared boundaries are marginalised."""
+        from . import posteriors
+        b, r, states, single = self._call_states(cn)
+        if not single:
+            raise ValueError('call_confidence takes one call of shape (num_segments, num_clones, 2)')
+        out = posteriors.batch_call_confidence(b, r, 1, states, regions, self.seg_fwd_remap, self.seg_is_original, self.is_telomere)
+        return dict((k, v[0]) for k, v in out.items())
+
+    def cn_logprob(self, cn=None):
+        """log q(cn) under the structured posterior of the last variational update: the exact log-probability of a whole
+        copy-number path, a float -- or (K,) for cn of shape (K, N, M, 2).  cn in experiment segment order as optimal_cn
+        returns it; None: the decoded path.  Zero-length segments inserted at shared boundaries are marginalised.  -inf
+        also where a state's forward entry underflowed in the sweep."""
+        from . import posteriors
+        b, r, states, single = self._call_states(cn)
+        out = posteriors.batch_cn_logprob(b, r, 1, states[None], self.seg_is_original, self.is_telomere)[0]
+        return float(out[0]) if single else out
+
     def cn_change_prob(self):
         """(N - 1,): the posterior probability that the copy-number state changes between experiment segments n and n + 1
         (1 - p_no_change of the region [n, n + 1]); NaN where no reference adjacency joins them."""

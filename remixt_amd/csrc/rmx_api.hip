@@ -40,12 +40,12 @@ static inline long long now_ns() { return std::chrono::duration_cast<std::chrono
 enum KernelId {
     KID_STATE_TABLES = 0, KID_SEG_CONST, KID_FRAMELOGPROB, KID_FB, KID_MARGINALS, KID_MARGINALS_AB, KID_OUTLIER_TOTAL,
     KID_OUTLIER_ALLELE, KID_ALLELE_SWAP, KID_BRK_LUT, KID_PAIRWISE, KID_BRK_UPDATE, KID_ELBO_SEG, KID_ELBO_FINAL,
-    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_POST_SUMMARY, KID_REGION, KID_REGION_COUNTS, KID_COUNT
+    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_POST_SUMMARY, KID_REGION, KID_REGION_COUNTS, KID_CALL_PROB, KID_COUNT
 };
 static const char *kKernelNames[KID_COUNT] = {
     "k_state_tables", "k_seg_const", "k_framelogprob", "k_fb", "k_marginals<true>", "k_marginals<false>", "k_update_outlier_total",
     "k_update_outlier_allele", "k_update_allele_swap", "k_brk_lut", "k_pairwise", "k_brk_update", "k_elbo_seg", "k_elbo_final",
-    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn", "k_posterior_summary", "k_region_prob", "k_region_counts"};
+    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn", "k_posterior_summary", "k_region_prob", "k_region_counts", "k_call_prob"};
 
 struct ProfRec { int id; hipEvent_t a, b; };
 
@@ -3244,6 +3244,110 @@ int rmx_region_counts(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const in
     for (int i = 0; i < nr; i++) if (e[i]) g_err_restarts.push_back(r0 + i);
     if (!g_err_restarts.empty()) {
         char buf[160]; snprintf(buf, sizeof buf, "region_counts: a backward step has a zero or non-finite normaliser (restart %d)", g_err_restarts[0]);
+        return fail_flagged(RMX_EASSERT, buf);
+    }
+    return RMX_OK;
+}
+
+// Call probabilities (k_call_prob): the log-probability that the path agrees with a reference path, up to a label, at every
+// bound segment of a run.  rmx_region_prob's validation, staging of queries and outputs (at most 64 MiB, chunked over
+// queries) and grouping of restarts by the snapshot's transition model; the reference paths of the call are checked here
+// (the kernel indexes label tables and weight rows with their entries) and staged whole beside the label tables.  One wave
+// computes a (restart, query) on its own, so a result depends on neither the restart range, the chunking nor the other paths.
+int rmx_call_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t npaths, const int16_t *paths, int32_t nq, const int32_t *queries,
+                  int32_t nlabel, const int16_t *labels, const uint8_t *constrain, double *logp_out) { BIND(b);
+    if (!b || r0 < 0 || nr < 1 || (int64_t)r0 + nr > b->R) return fail(RMX_EARG, "bad restart range");
+    if (npaths < 1 || !paths) return fail(RMX_EARG, "call_prob: no reference paths");
+    if (nq < 0 || (nq > 0 && (!queries || !logp_out))) return fail(RMX_EARG, "call_prob: bad query count, or no queries or no output");
+    if (nlabel < 0 || (nlabel > 0 && !labels)) return fail(RMX_EARG, "call_prob: bad label tables");
+    const Dev &d = b->d;
+    const int N = d.N, S = d.S, C_ = d.C;
+    if (S > CLP_MAXS) return fail(RMX_EUNSUPPORTED, "call_prob: more than 1024 states");
+    {
+        // chain of a segment = the number of chain ends (tclass < 0) before it
+        std::vector<int32_t> chain(N);
+        int32_t c = 0;
+        for (int n = 0; n < N; n++) { chain[n] = c; if (b->tclass[n] < 0) c++; }
+        for (int i = 0; i < nq; i++) {
+            const int32_t *qq = queries + 4 * (size_t)i;
+            if (qq[0] < 0 || qq[1] >= N || qq[0] > qq[1]) return fail(RMX_EARG, "call_prob: a query needs 0 <= first <= last < num_segments");
+            if (chain[qq[0]] != chain[qq[1]]) return fail(RMX_EARG, "call_prob: a query crosses a chain end");
+            if (qq[2] < -1 || qq[2] >= nlabel) return fail(RMX_EARG, "call_prob: label index out of range");
+            if (qq[3] < 0 || qq[3] >= npaths) return fail(RMX_EARG, "call_prob: path index out of range");
+        }
+        const size_t np = (size_t)nr * npaths * N;
+        for (size_t i = 0; i < np; i++) if (paths[i] < 0 || paths[i] >= S) return fail(RMX_EARG, "call_prob: a path entry is outside [0, num_cn_states)");
+    }
+    // no update_p_cn yet: there is no posterior to evaluate (reported as rmx_sample_cn does)
+    g_err_restarts.clear();
+    for (int r = r0; r < r0 + nr; r++) if (!b->lt_valid[r]) g_err_restarts.push_back(r);
+    if (!g_err_restarts.empty()) {
+        char buf[160]; snprintf(buf, sizeof buf, "call_prob before update_p_cn (restart %d)", g_err_restarts[0]);
+        return fail_flagged(RMX_EVALUE, buf);
+    }
+    if (nq == 0) return RMX_OK;
+    int rc;
+    if (!b->d_rflags && (rc = dalloc(b, &b->d_rflags, b->R))) return rc;
+    // tables: labels, paths (2-byte entries first), constrain
+    const size_t lab_bytes = (size_t)C_ * nlabel * S * sizeof(int16_t), path_bytes = (size_t)nr * npaths * N * sizeof(int16_t),
+                 tab_bytes = lab_bytes + path_bytes + (constrain ? (size_t)N : 0);
+    if (b->rgt_cap < tab_bytes) {
+        dfree(b, b->d_rgt); b->d_rgt = nullptr; b->rgt_cap = 0;
+        if ((rc = dalloc(b, &b->d_rgt, tab_bytes))) return rc;
+        b->rgt_cap = tab_bytes;
+    }
+    if (lab_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt, labels, lab_bytes, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes, paths, path_bytes, hipMemcpyHostToDevice, b->stream));
+    if (constrain) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes + path_bytes, constrain, (size_t)N, hipMemcpyHostToDevice, b->stream));
+    // staging in doubles: outputs [nrc][qc], then the chunk's queries [qc][4] int32
+    const size_t budget = (size_t)64 << 20;
+    const int nrc = std::min(nr, 65535);
+    const size_t qc = std::max<size_t>(1, std::min<size_t>((size_t)nq, budget / ((size_t)nrc * 8 + 16)));
+    const size_t need = (size_t)nrc * qc + 2 * qc;
+    if (b->rgn_cap < need) {
+        dfree(b, b->d_rgn); b->d_rgn = nullptr; b->rgn_cap = 0;
+        if ((rc = dalloc(b, &b->d_rgn, need))) return rc;
+        b->rgn_cap = need;
+    }
+    double *dout = b->d_rgn;
+    int32_t *dq = (int32_t *)(b->d_rgn + (size_t)nrc * qc);
+    const size_t lds = clp_lds_bytes(S);
+    if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)k_call_prob, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(hipMemsetAsync(b->d_rflags + r0, 0, sizeof(uint32_t) * nr, b->stream));
+    const int16_t *dpaths = (const int16_t *)(b->d_rgt + lab_bytes);
+    ClpArgs ca;
+    ca.queries = dq; ca.labels = (const int16_t *)b->d_rgt; ca.constrain = constrain ? b->d_rgt + lab_bytes + path_bytes : nullptr;
+    ca.npaths = npaths; ca.nlabel = nlabel; ca.pad_ = 0;
+    for (size_t q0 = 0; q0 < (size_t)nq; q0 += qc) {
+        const size_t nqc = std::min(qc, (size_t)nq - q0);
+        ca.nq = (int)nqc;
+        HIPCHK(hipMemcpyAsync(dq, queries + 4 * q0, nqc * 16, hipMemcpyHostToDevice, b->stream));
+        for (int rb = 0; rb < nr; rb += nrc) {
+            const int nrr = std::min(nrc, nr - rb);
+            // runs of restarts whose snapshot was taken under the same transition model (its plain tables)
+            for (int i = rb; i < rb + nrr;) {
+                int j = i; while (j < rb + nrr && b->lt_model[r0 + j] == b->lt_model[r0 + i]) j++;
+                const int model = b->lt_model[r0 + i];
+                const Dev dv = dev_for_model(b, model);
+                ca.paths = dpaths + (size_t)i * npaths * N;
+                {
+                    ProfScope ps(b, KID_CALL_PROB);
+                    hipLaunchKernelGGL(k_call_prob, dim3((unsigned)((nqc + CLP_WPB - 1) / CLP_WPB), j - i), dim3(64 * CLP_WPB), lds, b->stream, dv, r0 + i,
+                                       model == d.tmodel ? 1 : 0, ca, dout + (size_t)(i - rb) * nqc, b->d_rflags);
+                    HIPCHK(hipGetLastError());
+                }
+                i = j;
+            }
+            // device [nrr][nqc] -> host rows (rb .. rb+nrr)[q0 .. q0+nqc)
+            HIPCHK(hipMemcpy2DAsync(logp_out + (size_t)rb * nq + q0, (size_t)nq * 8, dout, nqc * 8, nqc * 8, nrr, hipMemcpyDeviceToHost, b->stream));
+        }
+    }
+    uint32_t *e = b->h_err;
+    HIPCHK(hipMemcpyAsync(e, b->d_rflags + r0, sizeof(uint32_t) * nr, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int i = 0; i < nr; i++) if (e[i]) g_err_restarts.push_back(r0 + i);
+    if (!g_err_restarts.empty()) {
+        char buf[160]; snprintf(buf, sizeof buf, "call_prob: a backward step has a zero or non-finite normaliser (restart %d)", g_err_restarts[0]);
         return fail_flagged(RMX_EASSERT, buf);
     }
     return RMX_OK;

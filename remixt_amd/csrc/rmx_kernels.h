@@ -5769,3 +5769,178 @@ __global__ __launch_bounds__(RGC_NT) void k_region_counts(Dev d, int r0, int use
     }
     if (tid == 0 && failed) atomicOr(&flags[r], RGN_ERR_DENOM);
 }
+
+// =============================================================================
+// Call probabilities: log P(E) under the structured posterior of the last update_p_cn, for the event E of a query
+// (a, b, label, path) over the model segments [a, b] of one chain: c_n in A_n at every n of the run with constrain[n] set,
+// A_n = { s : label(s) == label(ref_n) } under the label table of n's state class, ref = the query's reference path
+// (label -1: A_n = { ref_n }).  There is no adjacency constraint.  It is k_region_prob's recursion with a per-segment
+// allowed set that the reference path fixes in advance:
+//   g_b(s) = [s in A_b] post_b(s),   g_n(s) = [s in A_n] fa_n(s) sum_s' W_n(s, s') g_n+1(s') / D_n(s'),   P(E) = sum_s g_a(s),
+// D_n(s') = sum_s fa_n(s) W_n(s, s'); g is divided by its sum after every step and the logarithms of the sums are added
+// up.  Nothing of the model is written.
+// One wave per (restart, query), CLP_WPB independent waves per workgroup and no workgroup barrier: a step costs
+// |A| S weights, not S^2, which is too little for 256 threads.  Per wave, LDS holds the states s' with mass as (index, h)
+// and the allowed states of the current segment as (index, g), each in state order.  A step is
+//   1. D(s') for every s' with mass: the 64 lanes stride s over the fa row (held in registers) and the Wb row of s'
+//      (contiguous in s; exp(trans_value) on a breakend adjacency or under the other transition model), then a fixed
+//      butterfly; lane 0 turns g(s') into h(s') = g(s') / D(s');
+//   2. the allowed states of n (one ballot per 64 states; a singleton needs no scan; an unbound segment allows all S);
+//   3. g(s) for the allowed s: 16 lanes per s stride the states with mass, four s per round;
+//   4. the wave sum, one log, and the states with g > 0 compacted into the list for the next step.
+// An unbound segment (a zero-length segment inserted at a shared boundary) makes all S states allowed for one step and
+// up to S states carry mass into the next; the same code walks both.  The lanes of a wave run in lockstep and its LDS
+// operations complete in order, so what one lane writes the others read without a barrier.
+// Every sum has one order, fixed by S and the sets alone: a (restart, query) result depends on neither the launch nor
+// the other paths.  Only columns s < S of fa / post are read.  A D(s') that is 0 or not finite, or a sum of g that is
+// not a finite number >= 0, sets CLP_ERR_DENOM in flags[r] and gives NaN; a sum of exactly 0 gives -inf.
+// grid (ceil(nq / CLP_WPB), restarts), block 64 * CLP_WPB, dynamic LDS clp_lds_bytes(S); out[ri * nq + query].
+// =============================================================================
+#define CLP_WPB 4             // waves (= queries) per workgroup
+#define CLP_NSL 16            // states per lane of the fa row: S <= 1024
+#define CLP_GL 16             // lanes per allowed state in the g pass
+#define CLP_MAXS 1024
+#define CLP_ERR_DENOM 1u
+struct ClpArgs {
+    const int32_t *queries;   // [nq][4]: a, b, label index or -1, path index
+    const int16_t *paths;     // [restarts of the launch][npaths][N]
+    const int16_t *labels;    // [C][nlabel][S]
+    const uint8_t *constrain; // [N] or null (every segment binds)
+    int nq, npaths, nlabel, pad_;
+};
+// per wave: h [SR], g [SR] doubles, then hidx [SR], gidx [SR] int16; SR = S rounded up to 8 keeps every array 16-byte aligned
+static inline size_t clp_lds_bytes(int S) { const size_t SR = ((size_t)S + 7) & ~(size_t)7; return (size_t)CLP_WPB * SR * (2 * 8 + 2 * 2); }
+
+// the allowed states of segment n in state order -> gidx[0 .. count); every lane gets the count
+__device__ inline int clp_allowed(const Dev &d, const ClpArgs &q, int n, int li, int ref, int lane, int16_t *gidx) {
+    const int S = d.S;
+    const bool bound = !q.constrain || q.constrain[n];
+    if (bound && li < 0) {
+        if (lane == 0) gidx[0] = (int16_t)ref;
+        return 1;
+    }
+    const int16_t *lb = q.labels + ((size_t)d.seg_class[n] * q.nlabel + (li < 0 ? 0 : li)) * S;      // (not read when unbound)
+    const int lref = bound ? lb[ref] : 0;
+    int cnt = 0;
+    for (int base = 0; base < S; base += 64) {
+        const int s = base + lane;
+        const bool ok = s < S && (!bound || lb[s] == lref);
+        const unsigned long long m = __ballot(ok);
+        if (ok) gidx[cnt + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = (int16_t)s;
+        cnt += __builtin_popcountll(m);
+    }
+    return cnt;
+}
+// after a step: Z = the sum of g[0 .. na).  Adds log Z, and compacts the allowed states with g > 0 as (hidx, g / Z) for the
+// next step; returns their number, or -1 for a failed sum (Z == 0: logp = -inf and 0 states)
+__device__ inline int clp_finish(double Z, int na, int lane, const double *g, const int16_t *gidx, double *h, int16_t *hidx, double &logp) {
+    if (!(Z >= 0. && Z < INFINITY)) return -1;
+    if (Z == 0.) { logp = -INFINITY; return 0; }
+    logp += log(Z);
+    int cnt = 0;
+    for (int base = 0; base < na; base += 64) {
+        const int i = base + lane;
+        const double v = i < na ? g[i] / Z : 0.;
+        const bool act = v > 0.;
+        const unsigned long long m = __ballot(act);
+        if (act) {
+            const int p = cnt + __builtin_popcountll(m & ((1ull << lane) - 1ull));
+            hidx[p] = gidx[i]; h[p] = v;
+        }
+        cnt += __builtin_popcountll(m);
+    }
+    return cnt;
+}
+__global__ __launch_bounds__(64 * CLP_WPB) void k_call_prob(Dev d, int r0, int use_wb, ClpArgs q, double *out, uint32_t *flags) {
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int qi = blockIdx.x * CLP_WPB + w, ri = blockIdx.y, r = r0 + ri;
+    if (qi >= q.nq) return;      // (the whole wave: no workgroup barrier below)
+    const int S = d.S, SR = (S + 7) & ~7, nsl = (S + 63) >> 6;
+    double *h = (double *)smem_raw + (size_t)w * 2 * SR, *g = h + SR;
+    int16_t *hidx = (int16_t *)((double *)smem_raw + (size_t)CLP_WPB * 2 * SR) + (size_t)w * 2 * SR, *gidx = hidx + SR;
+    const int a = q.queries[4 * qi], b = q.queries[4 * qi + 1], li = q.queries[4 * qi + 2], pi = q.queries[4 * qi + 3];
+    const int16_t *path = q.paths + ((size_t)ri * q.npaths + pi) * d.N;
+    const int grp = lane / CLP_GL, gl = lane % CLP_GL;
+    double logp = 0.;
+    // ---- start: g_b = [A_b] post_b ----------------------------------------------------------------------
+    int nm;                   // the number of states with mass; < 0: failed
+    {
+        const int na = clp_allowed(d, q, b, li, path[b], lane, gidx);
+        const double *post = d.post + rs_off(d, r, b);
+        double part = 0.;
+        for (int i = lane; i < na; i += 64) {
+            const double v = post[gidx[i]];
+            g[i] = v; part += v;
+        }
+        nm = clp_finish(group_sum(part, 64), na, lane, g, gidx, h, hidx, logp);
+    }
+    for (int n = b - 1; n >= a && nm > 0; n--) {
+        const int tc = d.tclass[n], bs = d.brk_slot[n];      // (tc >= 0: the host checked that the run lies in one chain)
+        const double *fa = d.fa + rs_off(d, r, n);
+        const bool wb = bs < 0 && use_wb;
+        const double *Wt = d.Wb + (size_t)tc * S * S;
+        const double *pd = bs >= 0 ? d.pd_lt + ((size_t)r * d.NBE + bs) * d.M * d.D : nullptr;
+        // the fa row for the Wb rows: lane l holds states l, l + 64, ...
+        double f[CLP_NSL];
+#pragma unroll
+        for (int k = 0; k < CLP_NSL; k++) {
+            const int s = lane + 64 * k;
+            const double v = (wb && k < nsl) ? fa[s < S ? s : S - 1] : 0.;
+            f[k] = s < S ? v : 0.;
+        }
+        // 1. D(s') and h(s') = g(s') / D(s') for the states with mass
+        bool bad = false;
+        for (int j = 0; j < nm; j++) {
+            const int sp = hidx[j];
+            double p = 0.;
+            if (wb) {
+                const double *wr = Wt + (size_t)sp * S;
+#pragma unroll
+                for (int k = 0; k < CLP_NSL; k++) {
+                    const int s = lane + 64 * k;
+                    if (k < nsl) p = fma(f[k], wr[s < S ? s : S - 1], p);      // (f is 0 past S)
+                }
+            } else {
+#pragma unroll 1
+                for (int s = lane; s < S; s += 64) {
+                    const double fv = fa[s];
+                    if (fv != 0.) p = fma(fv, exp(trans_value(d, n, s, sp, pd)), p);
+                }
+            }
+            const double D = group_sum(p, 64);
+            if (!(D > 0. && D < INFINITY)) bad = true;
+            if (lane == 0) h[j] = h[j] / D;
+        }
+        // 2. the allowed states of n
+        const int na = clp_allowed(d, q, n, li, path[n], lane, gidx);
+        // 3. g(s) for the allowed s
+        for (int i0 = 0; i0 < na; i0 += 64 / CLP_GL) {
+            const int i = i0 + grp;
+            const bool ok = i < na;
+            const int s = ok ? gidx[i] : 0;
+            const double fs = ok ? fa[s] : 0.;
+            double p = 0.;
+            if (fs != 0.) {
+                if (wb) {
+                    const double *wc = Wt + s;
+                    for (int j = gl; j < nm; j += CLP_GL) p = fma(wc[(size_t)hidx[j] * S], h[j], p);
+                } else {
+#pragma unroll 1
+                    for (int j = gl; j < nm; j += CLP_GL) p = fma(exp(trans_value(d, n, s, hidx[j], pd)), h[j], p);
+                }
+            }
+            const double sum = group_sum(p, CLP_GL);
+            if (ok && gl == 0) g[i] = sum * fs;
+        }
+        // 4. the sum, and the states with mass for the next step
+        double part = 0.;
+        for (int i = lane; i < na; i += 64) part += g[i];
+        const double Z = group_sum(part, 64);
+        nm = bad ? -1 : clp_finish(Z, na, lane, g, gidx, h, hidx, logp);
+    }
+    if (lane == 0) {
+        if (nm < 0) atomicOr(&flags[r], CLP_ERR_DENOM);
+        out[(size_t)ri * q.nq + qi] = nm < 0 ? __builtin_nan("") : logp;
+    }
+}

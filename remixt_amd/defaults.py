@@ -36,6 +36,11 @@ cn_regions = None
 # 1 .. 16 adds `region_change_counts` -- names, bins, num_changes (state changes) and num_total_changes (changes of the
 # per-clone totals), each (regions, bins) -- to every fit result (remixt_amd/posteriors.py)
 cn_region_change_bins = 0
+# (no reference counterpart) with cn_regions: the exact posterior probability that the reported call holds.  False = none
+# (results unchanged); True adds `call_confidence` -- names, p_call (the path equals the result's `cn` at every segment of
+# the region), p_call_unphased (up to a swap of the alleles) and p_call_total (the per-clone totals) -- and the stat
+# cn_logprob, log q of the whole `cn`, to every fit result (remixt_amd/posteriors.py)
+cn_call_confidence = False
 
 
 def get_param(config, name):

@@ -376,3 +376,78 @@ def change_bins(config):
     if not 0 <= bins <= 16:
         raise ValueError('cn_region_change_bins must be in 0 .. 16')
     return bins
+
+
+# ---- probability that a copy-number call holds over regions (rmx_call_prob) -----------------------------
+# the arrays of call_confidence: name -> the label up to which the path has to agree with the call
+CALL_LABELS = (('p_call', 'state'), ('p_call_unphased', 'unphased'), ('p_call_total', 'total'))
+CALL_ARRAYS = tuple(c[0] for c in CALL_LABELS)
+_CALL_PATH_BYTES = 64 << 20      # the reference paths staged by one device call of batch_cn_logprob
+
+
+def batch_call_confidence(batch, r0, nr, states, regions, seg_fwd_remap, seg_is_original, is_telomere):
+    """The probability, under the structured posterior, that the copy-number path agrees with the call `states` at
+    every segment of a region, for restarts r0 .. r0+nr-1 of a RemixtBatch from one device call: a dict of the three
+    (nr, len(regions)) arrays of CALL_ARRAYS -- p_call (the same state everywhere), p_call_unphased (the same up to a swap of
+    the alleles) and p_call_total (the same per-clone totals).  states: int (nr, N1) state indices in model segment
+    order; what they hold at inserted zero-length segments is ignored (those are marginalised), so the output of
+    states_in_model_order is valid input.  regions: (first, last) experiment segment indices; a region that spans chain
+    ends is the conjunction over its chains, which are independent."""
+    _, label_tab = event_tables(batch.cn_classes)
+    cs, ce = chains_from_telomeres(is_telomere)
+    runs, piece_region, constrain = region_queries(regions, seg_fwd_remap, seg_is_original, cs, ce)
+    P, R = len(runs), len(np.asarray(regions).reshape(-1, 2))
+    if P == 0:
+        return dict((name, np.zeros((nr, 0))) for name in CALL_ARRAYS)
+    q = np.zeros((len(CALL_LABELS), P, 4), dtype=np.int32)
+    q[:, :, :2] = runs[None]
+    for e, (_, lb) in enumerate(CALL_LABELS):
+        q[e, :, 2] = LABEL_NAMES.index(lb)
+    paths = np.asarray(states).reshape(nr, 1, -1)
+    logp = batch.call_logprob_raw(r0, nr, paths, q.reshape(-1, 4), label_tab, constrain).reshape(nr, len(CALL_LABELS), P)
+    # (a sum of rounded logs of 1 can sit an ulp above 0)
+    return dict((name, np.exp(np.minimum(combine(logp[:, e], piece_region, R), 0.))) for e, name in enumerate(CALL_ARRAYS))
+
+
+def batch_cn_logprob(batch, r0, nr, states, seg_is_original, is_telomere):
+    """log q of whole copy-number paths under the structured posterior, for restarts r0 .. r0+nr-1 of a RemixtBatch:
+    states int (nr, K, N1) state indices in model segment order -> (nr, K).  It is the sum over the chains, which are
+    independent, of the log-probability that the path takes exactly these states at every real segment; inserted
+    zero-length segments are marginalised (what `states` holds there is ignored).  The paths go to the device in chunks
+    over K of at most 64 MiB."""
+    st = np.asarray(states)
+    if st.ndim != 3 or st.shape[0] != nr:
+        raise ValueError('states must have shape (nr, num_paths, num_segments)')
+    K, N1 = st.shape[1], st.shape[2]
+    cs, ce = chains_from_telomeres(is_telomere)
+    constrain = np.ascontiguousarray(np.asarray(seg_is_original) != 0, dtype=np.uint8)
+    out = np.zeros((nr, K))
+    step = max(1, _CALL_PATH_BYTES // max(1, 2 * nr * N1))
+    for k0 in range(0, K, step):
+        k1 = min(K, k0 + step)
+        q = np.zeros((k1 - k0, len(cs), 4), dtype=np.int32)
+        q[:, :, 0], q[:, :, 1], q[:, :, 2] = cs[None], ce[None], -1
+        q[:, :, 3] = np.arange(k1 - k0)[:, None]
+        logp = batch.call_logprob_raw(r0, nr, st[:, k0:k1], q.reshape(-1, 4), None, constrain)
+        out[:, k0:k1] = logp.reshape(nr, k1 - k0, len(cs)).sum(axis=2)
+    return out
+
+
+def add_call_confidence(res, names, conf, logprob):
+    """Fit result dict `res` gains `call_confidence`: the region names and the three arrays of CALL_ARRAYS for its own
+    `cn`, and stats['cn_logprob']: log q of that `cn`."""
+    out = {'names': list(names)}
+    for k in CALL_ARRAYS:
+        out[k] = np.asarray(conf[k])
+    res['call_confidence'] = out
+    res['stats']['cn_logprob'] = float(logprob)
+    return res
+
+
+def call_confidence_on(config):
+    """Config value cn_call_confidence, checked: it needs cn_regions."""
+    from . import defaults
+    on = bool(defaults.get_param(config, 'cn_call_confidence'))
+    if on and defaults.get_param(config, 'cn_regions') is None:
+        raise ValueError('cn_call_confidence needs cn_regions')
+    return on

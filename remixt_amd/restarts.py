@@ -681,6 +681,36 @@ class RestartSet(object):
         return posteriors.batch_region_change_counts(self.batch, 0, len(self.models), regions, m.seg_fwd_remap, m.seg_is_original, m.is_telomere,
                                                      bins=bins)
 
+    def _call_states(self, cn):
+        """int16 (restarts, N1): the restarts' calls as state indices in model segment order.  cn: their paths in
+        experiment order (the `cn` of results()); None: the decoded paths."""
+        from . import posteriors
+        b = self.batch
+        if cn is None:
+            cn_all, _ = b.infer_cn_batch(0, len(self.models))
+            return posteriors.cn_to_states(cn_all, b.cn_classes, b.seg_class)
+        return np.stack([posteriors.states_in_model_order(cn[r], b, m.seg_fwd_remap) for r, m in enumerate(self.models)])
+
+    def call_confidence(self, regions, cn=None):
+        """BreakpointModel.call_confidence of every restart from one device call: a dict of arrays (restarts, len(regions)).
+        cn: the restarts' calls in experiment order (the `cn` of results()); None: the decoded paths."""
+        from . import posteriors
+        if self.batch is None or not hasattr(self.batch, 'call_logprob_raw'):
+            per = [m.call_confidence(regions, None if cn is None else cn[r]) for r, m in enumerate(self.models)]
+            return dict((k, np.stack([p[k] for p in per])) for k in posteriors.CALL_ARRAYS)
+        m = self.models[0]
+        return posteriors.batch_call_confidence(self.batch, 0, len(self.models), self._call_states(cn), regions, m.seg_fwd_remap,
+                                                m.seg_is_original, m.is_telomere)
+
+    def cn_logprob(self, cn=None):
+        """BreakpointModel.cn_logprob of every restart from one device call: (restarts,).  cn: the restarts' paths in
+        experiment order (the `cn` of results()); None: the decoded paths."""
+        from . import posteriors
+        if self.batch is None or not hasattr(self.batch, 'call_logprob_raw'):
+            return np.array([m.cn_logprob(None if cn is None else cn[r]) for r, m in enumerate(self.models)])
+        m = self.models[0]
+        return posteriors.batch_cn_logprob(self.batch, 0, len(self.models), self._call_states(cn)[:, None], m.seg_is_original, m.is_telomere)[:, 0]
+
     def cn_change_prob(self):
         """BreakpointModel.cn_change_prob of every restart from one device call: (restarts, N - 1)."""
         from . import posteriors
@@ -827,6 +857,15 @@ class RestartGroups(object):
         parts = self._map(lambda rs: rs.region_change_counts(regions, bins))
         return dict((k, np.concatenate([p[k] for p in parts])) for k in parts[0])
 
+    def call_confidence(self, regions, cn=None):
+        """RestartSet.call_confidence over the groups, restarts in order (cn: of all restarts): a dict of arrays (restarts, len(regions))."""
+        parts = self._map(lambda rs: rs.call_confidence(regions, None if cn is None else cn[self.slices[self.sets.index(rs)]]))
+        return dict((k, np.concatenate([p[k] for p in parts])) for k in parts[0])
+
+    def cn_logprob(self, cn=None):
+        """RestartSet.cn_logprob over the groups, restarts in order (cn: of all restarts): (restarts,)."""
+        return np.concatenate(self._map(lambda rs: rs.cn_logprob(None if cn is None else cn[self.slices[self.sets.index(rs)]])))
+
     def cn_change_prob(self):
         """RestartSet.cn_change_prob over the groups, restarts in order: (restarts, N - 1)."""
         return np.concatenate(self._map(lambda rs: rs.cn_change_prob()))
@@ -930,6 +969,15 @@ class DatasetGroups(object):
     def region_change_counts(self, regions, bins=8):
         """RestartGroups.region_change_counts of every dataset: a list, one dict of arrays (restarts, len(regions), bins) per dataset."""
         return self._map(lambda part: part.region_change_counts(regions, bins))
+
+    def call_confidence(self, regions, cn=None):
+        """RestartGroups.call_confidence of every dataset (cn: per dataset, a list of its restarts' paths): a list, one dict of arrays
+        (restarts, len(regions)) per dataset."""
+        return self._map(lambda part: part.call_confidence(regions, None if cn is None else cn[self.parts.index(part)]))
+
+    def cn_logprob(self, cn=None):
+        """RestartGroups.cn_logprob of every dataset (cn: per dataset, a list of its restarts' paths): a list of (restarts,) arrays."""
+        return self._map(lambda part: part.cn_logprob(None if cn is None else cn[self.parts.index(part)]))
 
     def cn_change_prob(self):
         """RestartGroups.cn_change_prob of every dataset: a list of (restarts, N - 1) arrays."""
@@ -1045,17 +1093,24 @@ def _count_len(region_names, change_bins):
     return 2 * int(change_bins) * len(region_names) if change_bins and region_names is not None else 0
 
 
+def _call_len(region_names, call_confidence):
+    """Float slots of the call confidence in a record (0 when config cn_call_confidence is off: the record is unchanged):
+    the three arrays of posteriors.CALL_ARRAYS, one entry per region, and cn_logprob.  They are the record's last."""
+    return 3 * len(region_names) + 1 if call_confidence and region_names is not None else 0
+
+
 def _posterior_fields(N, M):
     """(name, shape) of the arrays of posteriors.COMPACT_ARRAYS in record order."""
     from .posteriors import COMPACT_ARRAYS
     return [(k, (N, M) if k.startswith('total_cn') else (N,)) for k in COMPACT_ARRAYS]
 
 
-def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0):
+def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0, call_confidence=False):
     """One restart's results as (float64 vector, int8 vector) of fixed length."""
     from .sampling import SUMMARY_STATS
     f = np.zeros(_HDR + M + nparams + 4 * N + _sample_len(N, M, cn_samples) + _posterior_len(N, M, cn_posterior) + _region_len(region_names)
-                 + _count_len(region_names, change_bins), dtype=np.float64)
+                 + _count_len(region_names, change_bins) + _call_len(region_names, call_confidence), dtype=np.float64)
+    tail = _call_len(region_names, call_confidence)      # what follows the region change counts
     st = res['stats']
     f[0] = st['elbo']; f[1] = st['elbo_diff'] if st['elbo_diff'] is not None else np.nan
     f[2] = st['ploidy']; f[3] = st['proportion_divergent']
@@ -1071,7 +1126,7 @@ def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_post
         f[o + 6 + N * M:o + 6 + N * M + N] = res['cn_state_agreement']
     if cn_posterior:
         from . import posteriors
-        o = len(f) - _count_len(region_names, change_bins) - _region_len(region_names) - _posterior_len(N, M, True)
+        o = len(f) - tail - _count_len(region_names, change_bins) - _region_len(region_names) - _posterior_len(N, M, True)
         f[o:o + 2] = [st[k] for k in posteriors.SUMMARY_STATS]
         o += 2
         for k, shape in _posterior_fields(N, M):
@@ -1080,15 +1135,22 @@ def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_post
     if region_names is not None:
         from . import posteriors
         nreg = len(region_names)
-        o = len(f) - _count_len(region_names, change_bins) - _region_len(region_names)
+        o = len(f) - tail - _count_len(region_names, change_bins) - _region_len(region_names)
         for j, k in enumerate(posteriors.REGION_ARRAYS):
             f[o + j * nreg:o + (j + 1) * nreg] = res['region_events'][k]
     if _count_len(region_names, change_bins):
         from . import posteriors
         n = len(region_names) * int(change_bins)
-        o = len(f) - 2 * n
+        o = len(f) - tail - 2 * n
         for j, k in enumerate(posteriors.COUNT_ARRAYS):
             f[o + j * n:o + (j + 1) * n] = np.asarray(res['region_change_counts'][k]).ravel()
+    if tail:
+        from . import posteriors
+        nreg = len(region_names)
+        o = len(f) - tail
+        for j, k in enumerate(posteriors.CALL_ARRAYS):
+            f[o + j * nreg:o + (j + 1) * nreg] = res['call_confidence'][k]
+        f[-1] = st['cn_logprob']
     i8 = np.zeros(N * M * 2 + K * M + 2 * N, dtype=np.int8)
     i8[:N * M * 2] = res['cn'].ravel()
     i8[N * M * 2:N * M * 2 + K * M] = np.array([res['brk_cn'][k] for k in brk_ids]).ravel()
@@ -1097,8 +1159,10 @@ def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_post
     return f, i8
 
 
-def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0):
+def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0,
+            call_confidence=False):
     from .sampling import SUMMARY_STATS
+    tail = _call_len(region_names, call_confidence)      # what follows the region change counts
     res = dict()
     res['h'] = f[_HDR:_HDR + M].copy()
     o = _HDR + M + nparams
@@ -1123,7 +1187,7 @@ def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_sampl
         res['cn_state_agreement'] = f[o + 6 + N * M:o + 6 + N * M + N].copy()
     if cn_posterior:
         from . import posteriors
-        o = len(f) - _count_len(region_names, change_bins) - _region_len(region_names) - _posterior_len(N, M, True)
+        o = len(f) - tail - _count_len(region_names, change_bins) - _region_len(region_names) - _posterior_len(N, M, True)
         for j, k in enumerate(posteriors.SUMMARY_STATS):
             st[k] = float(f[o + j])
         o += 2
@@ -1133,21 +1197,27 @@ def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_sampl
     if region_names is not None:
         from . import posteriors
         nreg = len(region_names)
-        o = len(f) - _count_len(region_names, change_bins) - _region_len(region_names)
+        o = len(f) - tail - _count_len(region_names, change_bins) - _region_len(region_names)
         posteriors.add_region_events(res, region_names, dict((k, f[o + j * nreg:o + (j + 1) * nreg].copy()) for j, k in enumerate(posteriors.REGION_ARRAYS)))
     if _count_len(region_names, change_bins):
         from . import posteriors
         n = len(region_names) * int(change_bins)
-        o = len(f) - 2 * n
+        o = len(f) - tail - 2 * n
         posteriors.add_region_change_counts(res, region_names, change_bins, dict(
             (k, f[o + j * n:o + (j + 1) * n].reshape(len(region_names), int(change_bins)).copy()) for j, k in enumerate(posteriors.COUNT_ARRAYS)))
     res['stats'] = st
+    if tail:
+        from . import posteriors
+        nreg = len(region_names)
+        o = len(f) - tail
+        posteriors.add_call_confidence(res, region_names, dict((k, f[o + j * nreg:o + (j + 1) * nreg].copy()) for j, k in enumerate(posteriors.CALL_ARRAYS)),
+                                       f[-1])
     return res
 
 
 def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clones=3, num_em_iter=5, num_update_iter=5,
                              device=None, kernel_module=None, seeds=None, quiet=True, groups=2, num_cn_samples=0, cn_sample_seed=0,
-                             cn_posterior_summary=False, cn_regions=None, cn_region_change_bins=0, **model_kwargs):
+                             cn_posterior_summary=False, cn_regions=None, cn_region_change_bins=0, cn_call_confidence=False, **model_kwargs):
     """Fit all restarts across the ranks of the default torch.distributed group.
 
     Every rank holds the (small, read-only) experiment; rank g fits restarts
@@ -1162,11 +1232,15 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
     (posteriors.add_region_events), and the records grow by seven floats per region.
     cn_region_change_bins: K > 0 (with cn_regions): every result also carries `region_change_counts`
     (posteriors.add_region_change_counts), and the records grow by 2 K floats per region.
+    cn_call_confidence (with cn_regions): every result also carries `call_confidence` and stats['cn_logprob'] for its own
+    `cn` (posteriors.add_call_confidence), and the records grow by three floats per region and one.
     """
     import torch
     import torch.distributed as dist
     if cn_region_change_bins and cn_regions is None:
         raise ValueError('cn_region_change_bins needs cn_regions')
+    if cn_call_confidence and cn_regions is None:
+        raise ValueError('cn_call_confidence needs cn_regions')
     distributed = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size() if distributed else 1
     rank = dist.get_rank() if distributed else 0
@@ -1190,6 +1264,8 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
             add_region_events(rs, local, cn_regions)
             if cn_region_change_bins:
                 add_region_change_counts(rs, local, cn_regions, cn_region_change_bins)
+            if cn_call_confidence:
+                add_call_confidence(rs, local, cn_regions)
         param_names = list(rs.models[0].likelihood_params)
         rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     if param_names is None:
@@ -1198,7 +1274,8 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
             [] if nc else ['negbin_hdel_mu', 'negbin_hdel_r_0', 'negbin_hdel_r_1', 'betabin_loh_p', 'betabin_loh_M_0', 'betabin_loh_M_1'])
     return gather_result_records(local, experiment, init_params, num_clones, param_names, device=device, cn_samples=num_cn_samples > 0,
                                  cn_posterior=bool(cn_posterior_summary),
-                                 region_names=None if cn_regions is None else [str(r[0]) for r in cn_regions], change_bins=cn_region_change_bins)
+                                 region_names=None if cn_regions is None else [str(r[0]) for r in cn_regions], change_bins=cn_region_change_bins,
+                                 call_confidence=bool(cn_call_confidence))
 
 
 def add_region_events(rs, results, cn_regions):
@@ -1223,6 +1300,20 @@ def add_region_change_counts(rs, results, cn_regions, bins):
     return results
 
 
+def add_call_confidence(rs, results, cn_regions):
+    """Add the call confidence of config cn_regions / cn_call_confidence of every restart of `rs` (a RestartSet /
+    RestartGroups; one device call per batch and quantity) to results[r], each for its own `cn`
+    (posteriors.add_call_confidence)."""
+    from . import posteriors
+    names, regions = posteriors.parse_regions(cn_regions)
+    cn = [res['cn'] for res in results]
+    conf = rs.call_confidence(regions, cn)
+    logprob = rs.cn_logprob(cn)
+    for r, res in enumerate(results):
+        posteriors.add_call_confidence(res, names, dict((k, v[r]) for k, v in conf.items()), logprob[r])
+    return results
+
+
 def add_posterior_summaries(rs, results, experiment):
     """Add the exact posterior summary of every restart of `rs` (a RestartSet / RestartGroups; one device call per
     batch) to results[r] (posteriors.add_posterior_summary); cn_posterior_prob is taken at results[r]['cn']."""
@@ -1244,7 +1335,7 @@ def add_cn_sample_summaries(rs, results, experiment, num_samples, seed, init_ids
 
 
 def gather_result_records(local, experiment, init_params, num_clones, param_names, device=None, timing=None, local_ids=None, cn_samples=False,
-                          cn_posterior=False, region_names=None, change_bins=0):
+                          cn_posterior=False, region_names=None, change_bins=0, call_confidence=False):
     """The one collective of the path: every rank contributes the fixed-size records of the restarts
     it fitted (`local`, in the order of shard_indices) -- one float64 record (ELBO, h, parameters, outlier
     probabilities, failure code) and one int8 record (cn, brk_cn, masks) per restart -- and every rank gets the
@@ -1273,11 +1364,11 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
             per_rank = int(cnt_.item())
     if len(local) > per_rank:
         raise ValueError('gather_result_records: %d local results for a share of %d (pass local_ids for shares that are not shard_indices\')' % (len(local), per_rank))
-    flen = _HDR + M + nparams + 4 * N + _sample_len(N, M, cn_samples) + _posterior_len(N, M, cn_posterior) + _region_len(region_names) + _count_len(region_names, change_bins)
+    flen = _HDR + M + nparams + 4 * N + _sample_len(N, M, cn_samples) + _posterior_len(N, M, cn_posterior) + _region_len(region_names) + _count_len(region_names, change_bins) + _call_len(region_names, call_confidence)
     ilen = N * M * 2 + K * M + 2 * N
     fbuf = np.full((per_rank, flen), np.nan); ibuf = np.zeros((per_rank, ilen), dtype=np.int8)
     for j, res in enumerate(local):
-        fbuf[j], ibuf[j] = _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples, cn_posterior, region_names, change_bins)
+        fbuf[j], ibuf[j] = _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples, cn_posterior, region_names, change_bins, call_confidence)
     if local_ids is not None:
         ids_t = np.full((per_rank,), -1, dtype=np.int64); ids_t[:len(local_ids)] = local_ids
     t0 = time.perf_counter()
@@ -1309,7 +1400,7 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
     for g in range(world):
         ids_g = shard_indices(len(init_params), world, g) if ids_all is None else [int(i) for i in ids_all[g] if i >= 0]
         for j, i in enumerate(ids_g):
-            results[i] = _unpack(fall[g][j], iall[g][j], N, M, K, nparams, brk_ids, param_names, init_params[i], cn_samples, cn_posterior, region_names, change_bins)
+            results[i] = _unpack(fall[g][j], iall[g][j], N, M, K, nparams, brk_ids, param_names, init_params[i], cn_samples, cn_posterior, region_names, change_bins, call_confidence)
     return results
 
 

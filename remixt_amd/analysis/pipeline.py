@@ -8,7 +8,7 @@ import numpy as np
 
 from .. import defaults, posteriors, sampling
 from ..cn_model import BreakpointModel
-from ..restarts import RestartSet, add_call_confidence, add_cn_sample_summaries, add_posterior_summaries, add_region_change_counts, add_region_events, collect_fit_results, fit_restarts_distributed, select_optimal  # noqa: F401
+from ..restarts import RestartSet, add_call_confidence, add_cn_sample_summaries, add_optional_outputs, add_posterior_summaries, add_region_change_counts, add_region_events, collect_fit_results, fit_restarts_distributed, select_optimal  # noqa: F401
 
 
 def _model_kwargs(experiment, config):
@@ -118,18 +118,8 @@ def fit_restarts(experiment, init_params_by_id, config, device=0, quiet=True, se
         rs = RestartSet(experiment, params, max_cn, num_clones=3, device=device, quiet=quiet, seeds=seeds,
                         **_model_kwargs(experiment, config))
     rs.fit(defaults.get_param(config, 'num_em_iter'), defaults.get_param(config, 'num_update_iter'))
-    results = rs.results()
-    num_samples = defaults.get_param(config, 'num_cn_samples')
-    if num_samples > 0:
-        add_cn_sample_summaries(rs, results, experiment, num_samples, defaults.get_param(config, 'cn_sample_seed'), ids)
-    if defaults.get_param(config, 'cn_posterior_summary'):
-        add_posterior_summaries(rs, results, experiment)
-    if defaults.get_param(config, 'cn_regions') is not None:
-        add_region_events(rs, results, defaults.get_param(config, 'cn_regions'))
-        if bins:
-            add_region_change_counts(rs, results, defaults.get_param(config, 'cn_regions'), bins)
-        if call_conf:
-            add_call_confidence(rs, results, defaults.get_param(config, 'cn_regions'))
+    results = add_optional_outputs(rs, rs.results(), experiment, ids, defaults.get_param(config, 'num_cn_samples'), defaults.get_param(config, 'cn_sample_seed'),
+                                   defaults.get_param(config, 'cn_posterior_summary'), defaults.get_param(config, 'cn_regions'), bins, call_conf)
     out = dict(zip(ids, results))
     rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     return out

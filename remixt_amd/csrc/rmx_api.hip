@@ -731,6 +731,102 @@ static int launch_brk_lut(rmx_batch *b, int r0, int r1, double *dst, double *eds
 }
 
 #define RANGE_CHECK() if (!b || r0 < 0 || r1 > b->R || r0 >= r1) return fail(RMX_EARG, "bad restart range")
+
+// ---- the host path the decode and the posterior queries (rmx_sample_cn, rmx_region_prob, rmx_region_counts, rmx_call_prob) share ----
+// a device buffer that only grows: at least `need` elements afterwards (what it held is not kept)
+template <typename T> static int grow(rmx_batch *b, T **p, size_t *cap, size_t need) {
+    if (*cap >= need) return RMX_OK;
+    dfree(b, *p); *p = nullptr; *cap = 0;
+    int rc = dalloc(b, p, need);
+    if (!rc) *cap = need;
+    return rc;
+}
+
+// no update_p_cn yet: there is no forward pass, snapshot or posterior to read (the restarts are reported like a device-side check)
+static int require_snapshot(rmx_batch *b, int r0, int nr, const char *name) {
+    g_err_restarts.clear();
+    for (int r = r0; r < r0 + nr; r++) if (!b->lt_valid[r]) g_err_restarts.push_back(r);
+    if (g_err_restarts.empty()) return RMX_OK;
+    char buf[160]; snprintf(buf, sizeof buf, "%s before update_p_cn (restart %d)", name, g_err_restarts[0]);
+    return fail_flagged(RMX_EVALUE, buf);
+}
+
+// the flags [r0, r0 + nr) a call's kernels raised, read back once everything queued has run: "<what> (restart %d)"
+static int report_flags(rmx_batch *b, const uint32_t *flags, int r0, int nr, const char *what) {
+    uint32_t *e = b->h_err;
+    HIPCHK(hipMemcpyAsync(e, flags + r0, sizeof(uint32_t) * nr, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int i = 0; i < nr; i++) if (e[i]) g_err_restarts.push_back(r0 + i);
+    if (g_err_restarts.empty()) return RMX_OK;
+    char buf[160]; snprintf(buf, sizeof buf, "%s (restart %d)", what, g_err_restarts[0]);
+    return fail_flagged(RMX_EASSERT, buf);
+}
+
+// f(i, j, model, Dev, use_wb) for every run [i, j) of restarts r0 + [i0, i1) whose snapshot was taken under the same transition
+// model: the Dev carries that model's plain tables, use_wb says that it is the current one
+template <typename F> static int for_model_runs(const rmx_batch *b, int r0, int i0, int i1, F f) {
+    for (int i = i0, j; i < i1; i = j) {
+        const int model = b->lt_model[r0 + i];
+        for (j = i + 1; j < i1 && b->lt_model[r0 + j] == model; j++) {}
+        int rc = f(i, j, model, dev_for_model(b, model), model == b->d.tmodel ? 1 : 0);
+        if (rc) return rc;
+    }
+    return RMX_OK;
+}
+
+// the [nq][4] queries of a region call: segments first <= last of one chain (fields 0, 1); fields 2 and 3 in [lo, hi), or `msg`
+struct QueryField { int lo, hi; const char *msg; };
+static int check_queries(const rmx_batch *b, const char *name, int nq, const int32_t *queries, QueryField f2, QueryField f3) {
+    const int N = b->d.N;
+    // chain of a segment = the number of chain ends (tclass < 0) before it
+    std::vector<int32_t> chain(N);
+    int32_t c = 0;
+    for (int n = 0; n < N; n++) { chain[n] = c; if (b->tclass[n] < 0) c++; }
+    for (int i = 0; i < nq; i++) {
+        const int32_t *qq = queries + 4 * (size_t)i;
+        if (qq[0] < 0 || qq[1] >= N || qq[0] > qq[1]) return fail(RMX_EARG, std::string(name) + ": a query needs 0 <= first <= last < num_segments");
+        if (chain[qq[0]] != chain[qq[1]]) return fail(RMX_EARG, std::string(name) + ": a query crosses a chain end");
+        if (qq[2] < f2.lo || qq[2] >= f2.hi) return fail(RMX_EARG, f2.msg);
+        if (qq[3] < f3.lo || qq[3] >= f3.hi) return fail(RMX_EARG, f3.msg);
+    }
+    return RMX_OK;
+}
+
+// The queries of a region call against restarts r0 .. r0+nr-1, `per` outputs each.  Queries and outputs go through one device
+// buffer of at most 64 MiB (doubles: outputs [nrc][qc][per], then the chunk's queries [qc][4] int32), chunked over queries and over
+// blocks of 65535 restarts; within a block, one launch per run of restarts of one transition model:
+//   launch(Dev of the run, its first restart, its length, its offset in the call, use_wb, device queries, their number, the run's outputs, flags)
+// under profile id `kid`.  Rows [nrr][nqc * per] come back to logp_out [nr][nq][per]; a raised flag fails the call with flag_msg.
+template <typename L> static int run_queries(rmx_batch *b, int r0, int nr, int nq, const int32_t *queries, int per, int kid, const char *flag_msg,
+                                             double *logp_out, L launch) {
+    int rc;
+    if (!b->d_rflags && (rc = dalloc(b, &b->d_rflags, b->R))) return rc;
+    const size_t budget = (size_t)64 << 20;
+    const int nrc = std::min(nr, 65535);
+    const size_t qc = std::max<size_t>(1, std::min<size_t>((size_t)nq, budget / ((size_t)nrc * per * 8 + 16)));
+    if ((rc = grow(b, &b->d_rgn, &b->rgn_cap, (size_t)nrc * qc * per + 2 * qc))) return rc;
+    double *dout = b->d_rgn;
+    int32_t *dq = (int32_t *)(b->d_rgn + (size_t)nrc * qc * per);
+    HIPCHK(hipMemsetAsync(b->d_rflags + r0, 0, sizeof(uint32_t) * nr, b->stream));
+    for (size_t q0 = 0; q0 < (size_t)nq; q0 += qc) {
+        const size_t nqc = std::min(qc, (size_t)nq - q0);
+        HIPCHK(hipMemcpyAsync(dq, queries + 4 * q0, nqc * 16, hipMemcpyHostToDevice, b->stream));
+        for (int rb = 0; rb < nr; rb += nrc) {
+            const int nrr = std::min(nrc, nr - rb);
+            rc = for_model_runs(b, r0, rb, rb + nrr, [&](int i, int j, int, const Dev &dv, int use_wb) -> int {
+                ProfScope ps(b, kid);
+                launch(dv, r0 + i, j - i, i, use_wb, dq, (int)nqc, dout + (size_t)(i - rb) * nqc * per, b->d_rflags);
+                HIPCHK(hipGetLastError());
+                return RMX_OK;
+            });
+            if (rc) return rc;
+            // device [nrr][nqc][per] -> host rows (rb .. rb+nrr)[q0 .. q0+nqc)
+            HIPCHK(hipMemcpy2DAsync(logp_out + ((size_t)rb * nq + q0) * per, (size_t)nq * per * 8, dout, nqc * per * 8, nqc * per * 8, nrr, hipMemcpyDeviceToHost, b->stream));
+        }
+    }
+    return report_flags(b, b->d_rflags, r0, nr, flag_msg);
+}
+
 // HIP's current device is per host thread and starts at 0: every entry point binds the calling thread to the
 // batch's device first (restart groups, M-step helpers and result collection call from their own threads;
 // allocations and events made there must belong to the batch's GPU, not to GPU 0)
@@ -2371,11 +2467,7 @@ int rmx_param_search_multi(rmx_batch *b, int32_t nreq, const int32_t *restarts, 
     if ((size_t)Q * G > (size_t)(b->R + 1) * 64 * (1 + RMX_MAX_CLONES) || b->R > 32767)
         return fail(RMX_EUNSUPPORTED, "rmx_param_search_multi: staging too small for this request");
     const size_t need = (size_t)Q * G * std::max(maxcnt, 1);      // partial sums [request][candidate][sampled segment]
-    if (b->mpartial_cap < need) {
-        dfree(b, b->d_mpartial); b->d_mpartial = nullptr; b->mpartial_cap = 0;
-        if ((rc = dalloc(b, &b->d_mpartial, need))) return rc;
-        b->mpartial_cap = need;
-    }
+    if ((rc = grow(b, &b->d_mpartial, &b->mpartial_cap, need))) return rc;
     for (int j = 0; j < nparams; j++)
         for (int g = 0; g < G; g++) { mv.gv[j][g] = grids[(size_t)j * G + g]; mv.glv[j][g] = std::log(mv.gv[j][g]); }
     // the candidates are evaluated against the restarts' device parameters and state tables: bring them up to date
@@ -2773,11 +2865,7 @@ static int viterbi_paths(rmx_batch *b, int r0, int nr, std::vector<int64_t> &pat
     }
     // the trace-back in parallel (k_bp_all + k_chase_*): the lattice rows of this call, transition values of class 0 from the packed copies
     const bool par_tb = lattice_rows && vopt == 0 && b->opt[RMX_OPT_TRACEBACK] == 0 && cur_model && b->fbk_ok && !b->tc_pairs.empty() && ca0 == cb0 && N >= 2 && S <= 1024;
-    if ((!lattice_rows || par_tb) && b->bp_cap < (size_t)nr * N * S) {
-        dfree(b, b->d_bp); b->d_bp = nullptr; b->bp_cap = 0;
-        if ((rc = dalloc(b, &b->d_bp, (size_t)nr * N * S))) return rc;
-        b->bp_cap = (size_t)nr * N * S;
-    }
+    if ((!lattice_rows || par_tb) && (rc = grow(b, &b->d_bp, &b->bp_cap, (size_t)nr * N * S))) return rc;
     { ProfScope ps(b, KID_VITERBI);
       b->last_viterbi = sadmax ? 6 : (reg ? (reg_max ? 4 : 1) : (coded ? (maxima ? 5 : 2) : 3));
       b->last_viterbi_wgs = 1;
@@ -2834,8 +2922,7 @@ static int viterbi_paths(rmx_batch *b, int r0, int nr, std::vector<int64_t> &pat
         const int NB = P * (P >= 4 ? 2 : (P == 1 ? 8 : 4));
         const int B = std::max(8, std::min(128, (96 * 1024) / (2 * S)));
         const int NBLK = (N - 1 + B - 1) / B;
-        if (b->comp_cap < (size_t)nr * NBLK * S) { dfree(b, b->d_comp); b->d_comp = nullptr; b->comp_cap = 0; if ((rc = dalloc(b, &b->d_comp, (size_t)nr * NBLK * S))) return rc; b->comp_cap = (size_t)nr * NBLK * S; }
-        if (b->ends_cap < (size_t)nr * NBLK) { dfree(b, b->d_ends); b->d_ends = nullptr; b->ends_cap = 0; if ((rc = dalloc(b, &b->d_ends, (size_t)nr * NBLK))) return rc; b->ends_cap = (size_t)nr * NBLK; }
+        if ((rc = grow(b, &b->d_comp, &b->comp_cap, (size_t)nr * NBLK * S)) || (rc = grow(b, &b->d_ends, &b->ends_cap, (size_t)nr * NBLK))) return rc;
         ProfScope ps(b, KID_BACKTRACE);
         const size_t lds_a = (size_t)NB * SR * 8 + (size_t)(M == 4 ? 2 : 1) * SR * 4 + 16, lds_c = (size_t)B * S * 2 + 16;
         auto ka = M == 4 ? k_bp_all<true> : k_bp_all<false>;
@@ -2905,16 +2992,20 @@ int rmx_infer_cn_batch(rmx_batch *b, int32_t r0, int32_t nr, int64_t *cn_out, do
     const Dev &d = b->d;
     const int N = d.N, S = d.S, M = d.M;
     std::vector<int64_t> paths; std::vector<double> lps;
-    // maximal runs of restarts with a lattice; the others have framelogprob == 1 and log_transmat == 0
+    // maximal stretches of restarts with a lattice, by transition model; the others have framelogprob == 1 and log_transmat == 0
     // (bpmodel.pyx:557-558): every comparison ties, the first index wins
     std::vector<int64_t> all((size_t)nr * N, 0); std::vector<double> lp(nr, (double)N);
-    for (int i = 0; i < nr;) {
-        if (!b->lt_valid[r0 + i]) { i++; continue; }
-        int j = i; while (j < nr && b->lt_valid[r0 + j] && b->lt_model[r0 + j] == b->lt_model[r0 + i]) j++;
-        int rc = viterbi_paths(b, r0 + i, j - i, paths, lps, b->lt_model[r0 + i]); if (rc) return rc;
-        memcpy(all.data() + (size_t)i * N, paths.data(), (size_t)(j - i) * N * 8);
-        for (int k = i; k < j; k++) lp[k] = lps[k - i];
-        i = j;
+    for (int a = 0; a < nr;) {
+        if (!b->lt_valid[r0 + a]) { a++; continue; }
+        int z = a; while (z < nr && b->lt_valid[r0 + z]) z++;
+        int rc = for_model_runs(b, r0, a, z, [&](int i, int j, int model, const Dev &, int) -> int {
+            int rc = viterbi_paths(b, r0 + i, j - i, paths, lps, model); if (rc) return rc;
+            memcpy(all.data() + (size_t)i * N, paths.data(), (size_t)(j - i) * N * 8);
+            for (int k = i; k < j; k++) lp[k] = lps[k - i];
+            return RMX_OK;
+        });
+        if (rc) return rc;
+        a = z;
     }
     b->last_path.assign(all.end() - N, all.end());
     // bpmodel.pyx:1205-1210 (the allele "swap" there re-uses the flipped index on both sides: a plain gather)
@@ -2941,53 +3032,32 @@ int rmx_sample_cn(rmx_batch *b, int32_t r0, int32_t nr, int32_t num_samples, con
     const Dev &d = b->d;
     const int N = d.N;
     if (d.S > 64 * SMP_NSL) return fail(RMX_EUNSUPPORTED, "sample_cn: more than 1024 states");
-    // no update_p_cn yet: there is no forward pass to sample from (the restart is reported like a device-side check)
-    g_err_restarts.clear();
-    for (int r = r0; r < r0 + nr; r++) if (!b->lt_valid[r]) g_err_restarts.push_back(r);
-    if (!g_err_restarts.empty()) {
-        char buf[160]; snprintf(buf, sizeof buf, "sample_cn before update_p_cn (restart %d)", g_err_restarts[0]);
-        return fail_flagged(RMX_EVALUE, buf);
-    }
     int rc;
+    if ((rc = require_snapshot(b, r0, nr, "sample_cn"))) return rc;
     if (!b->d_seeds && (rc = dalloc(b, &b->d_seeds, b->R))) return rc;
     if (!b->d_sflags && (rc = dalloc(b, &b->d_sflags, b->R))) return rc;
     const size_t per_sample = (size_t)nr * N * sizeof(int16_t);
     const int kc = (int)std::max<size_t>(1, std::min<size_t>((size_t)num_samples, ((size_t)64 << 20) / per_sample));
-    if (b->samp_cap < (size_t)kc * nr * N) {
-        dfree(b, b->d_samp); b->d_samp = nullptr; b->samp_cap = 0;
-        if ((rc = dalloc(b, &b->d_samp, (size_t)kc * nr * N))) return rc;
-        b->samp_cap = (size_t)kc * nr * N;
-    }
+    if ((rc = grow(b, &b->d_samp, &b->samp_cap, (size_t)kc * nr * N))) return rc;
     HIPCHK(hipMemcpyAsync(b->d_seeds, seeds, sizeof(uint64_t) * nr, hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipMemsetAsync(b->d_sflags + r0, 0, sizeof(uint32_t) * nr, b->stream));
-    // runs of restarts whose snapshot was taken under the same transition model (its plain tables)
-    for (int i = 0; i < nr;) {
-        int j = i; while (j < nr && b->lt_model[r0 + j] == b->lt_model[r0 + i]) j++;
-        const int model = b->lt_model[r0 + i];
-        const Dev dv = dev_for_model(b, model);
+    rc = for_model_runs(b, r0, 0, nr, [&](int i, int j, int, const Dev &dv, int use_wb) -> int {
         for (int k0 = 0; k0 < num_samples; k0 += kc) {
             const int nk = std::min(kc, num_samples - k0);
             {
                 ProfScope ps(b, KID_SAMPLE);
                 hipLaunchKernelGGL(k_sample_cn, dim3(d.NC, j - i, (nk + SMP_WPB - 1) / SMP_WPB), dim3(64 * SMP_WPB), 0, b->stream, dv, r0 + i, k0, nk,
-                                   model == d.tmodel ? 1 : 0, (const uint64_t *)(b->d_seeds + i), b->d_samp, b->d_sflags);
+                                   use_wb, (const uint64_t *)(b->d_seeds + i), b->d_samp, b->d_sflags);
                 HIPCHK(hipGetLastError());
             }
             // device [j-i][nk][N] -> host rows (r0+i .. r0+j)[k0 .. k0+nk)
             HIPCHK(hipMemcpy2DAsync(states_out + ((size_t)i * num_samples + k0) * N, (size_t)num_samples * N * sizeof(int16_t), b->d_samp,
                                     (size_t)nk * N * sizeof(int16_t), (size_t)nk * N * sizeof(int16_t), j - i, hipMemcpyDeviceToHost, b->stream));
         }
-        i = j;
-    }
-    uint32_t *e = b->h_err;
-    HIPCHK(hipMemcpyAsync(e, b->d_sflags + r0, sizeof(uint32_t) * nr, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    for (int i = 0; i < nr; i++) if (e[i]) g_err_restarts.push_back(r0 + i);
-    if (!g_err_restarts.empty()) {
-        char buf[160]; snprintf(buf, sizeof buf, "sample_cn: a step has no finite positive weight (restart %d)", g_err_restarts[0]);
-        return fail_flagged(RMX_EASSERT, buf);
-    }
-    return RMX_OK;
+        return RMX_OK;
+    });
+    if (rc) return rc;
+    return report_flags(b, b->d_sflags, r0, nr, "sample_cn: a step has no finite positive weight");
 }
 
 // Posterior summaries (k_posterior_summary) of restarts r0 .. r0+nr-1: linear functionals, row statistics and arg-max of
@@ -3019,18 +3089,10 @@ int rmx_posterior_summary(rmx_batch *b, int32_t r0, int32_t nr, int32_t Q, const
     const size_t rows = (size_t)nrc * ncap;
     const size_t o_stats = want_proj ? rows * Q : 0, o_i16 = o_stats + (stats_out ? rows * 3 : 0), need = o_i16 + (rows * 4 + 7) / 8 + 1;
     int rc;
-    if (b->psum_cap < need) {
-        dfree(b, b->d_psum); b->d_psum = nullptr; b->psum_cap = 0;
-        if ((rc = dalloc(b, &b->d_psum, need))) return rc;
-        b->psum_cap = need;
-    }
+    if ((rc = grow(b, &b->d_psum, &b->psum_cap, need))) return rc;
     if (want_proj) {
         const size_t wn = (size_t)d.C * S * Q;
-        if (b->psw_cap < wn) {
-            dfree(b, b->d_psw); b->d_psw = nullptr; b->psw_cap = 0;
-            if ((rc = dalloc(b, &b->d_psw, wn))) return rc;
-            b->psw_cap = wn;
-        }
+        if ((rc = grow(b, &b->d_psw, &b->psw_cap, wn))) return rc;
         HIPCHK(hipMemcpyAsync(b->d_psw, weights, wn * sizeof(double), hipMemcpyHostToDevice, b->stream));
     }
     if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)k_posterior_summary, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -3059,8 +3121,8 @@ int rmx_posterior_summary(rmx_batch *b, int32_t r0, int32_t nr, int32_t Q, const
 
 // Region event probabilities (k_region_prob) of restarts r0 .. r0+nr-1 from what the last update_p_cn left on the device: the
 // fa plane and transition snapshot rmx_sample_cn reads, and the marginals d.post.  Everything a query could index out of
-// range is checked here, before anything is queued: the kernel trusts the segment runs and the table indices.  Queries and
-// outputs go through one device buffer of at most 64 MiB, chunked over queries; one workgroup computes a (restart, query)
+// range is checked here, before anything is queued: the kernel trusts the segment runs and the table indices.  Staging, chunking
+// and the grouping of restarts by the snapshot's transition model are run_queries'; one workgroup computes a (restart, query)
 // on its own, so a result depends on neither the restart range nor the chunking.
 int rmx_region_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
                     int32_t nlabel, const int16_t *labels, const uint8_t *constrain, double *logp_out) { BIND(b);
@@ -3070,90 +3132,27 @@ int rmx_region_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int3
     const Dev &d = b->d;
     const int N = d.N, S = d.S, C_ = d.C;
     if (S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "region_prob: more than 1024 states");
-    {
-        // chain of a segment = the number of chain ends (tclass < 0) before it
-        std::vector<int32_t> chain(N);
-        int32_t c = 0;
-        for (int n = 0; n < N; n++) { chain[n] = c; if (b->tclass[n] < 0) c++; }
-        for (int i = 0; i < nq; i++) {
-            const int32_t *qq = queries + 4 * (size_t)i;
-            if (qq[0] < 0 || qq[1] >= N || qq[0] > qq[1]) return fail(RMX_EARG, "region_prob: a query needs 0 <= first <= last < num_segments");
-            if (chain[qq[0]] != chain[qq[1]]) return fail(RMX_EARG, "region_prob: a query crosses a chain end");
-            if (qq[2] < -1 || qq[2] >= nmask) return fail(RMX_EARG, "region_prob: mask index out of range");
-            if (qq[3] < -1 || qq[3] >= nlabel) return fail(RMX_EARG, "region_prob: label index out of range");
-        }
-    }
-    // no update_p_cn yet: there is no posterior to evaluate (reported as rmx_sample_cn does)
-    g_err_restarts.clear();
-    for (int r = r0; r < r0 + nr; r++) if (!b->lt_valid[r]) g_err_restarts.push_back(r);
-    if (!g_err_restarts.empty()) {
-        char buf[160]; snprintf(buf, sizeof buf, "region_prob before update_p_cn (restart %d)", g_err_restarts[0]);
-        return fail_flagged(RMX_EVALUE, buf);
-    }
     int rc;
-    if (!b->d_rflags && (rc = dalloc(b, &b->d_rflags, b->R))) return rc;
+    if ((rc = check_queries(b, "region_prob", nq, queries, {-1, nmask, "region_prob: mask index out of range"}, {-1, nlabel, "region_prob: label index out of range"}))) return rc;
+    if ((rc = require_snapshot(b, r0, nr, "region_prob"))) return rc;
     // tables: labels (2-byte entries first), masks, constrain
-    const size_t lab_bytes = (size_t)C_ * nlabel * S * sizeof(int16_t), mask_bytes = (size_t)C_ * nmask * S, tab_bytes = lab_bytes + mask_bytes + (constrain ? (size_t)N : 0);
-    if (b->rgt_cap < tab_bytes) {
-        dfree(b, b->d_rgt); b->d_rgt = nullptr; b->rgt_cap = 0;
-        if ((rc = dalloc(b, &b->d_rgt, tab_bytes))) return rc;
-        b->rgt_cap = tab_bytes;
-    }
+    const size_t lab_bytes = (size_t)C_ * nlabel * S * sizeof(int16_t), mask_bytes = (size_t)C_ * nmask * S;
+    if ((rc = grow(b, &b->d_rgt, &b->rgt_cap, lab_bytes + mask_bytes + (constrain ? (size_t)N : 0)))) return rc;
     if (lab_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt, labels, lab_bytes, hipMemcpyHostToDevice, b->stream));
     if (mask_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes, masks, mask_bytes, hipMemcpyHostToDevice, b->stream));
     if (constrain) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes + mask_bytes, constrain, (size_t)N, hipMemcpyHostToDevice, b->stream));
-    // staging in doubles: outputs [nrc][qc], then the chunk's queries [qc][4] int32
-    const size_t budget = (size_t)64 << 20;
-    const int nrc = std::min(nr, 65535);
-    const size_t qc = std::max<size_t>(1, std::min<size_t>((size_t)nq, budget / ((size_t)nrc * 8 + 16)));
-    const size_t need = (size_t)nrc * qc + 2 * qc;
-    if (b->rgn_cap < need) {
-        dfree(b, b->d_rgn); b->d_rgn = nullptr; b->rgn_cap = 0;
-        if ((rc = dalloc(b, &b->d_rgn, need))) return rc;
-        b->rgn_cap = need;
-    }
-    double *dout = b->d_rgn;
-    int32_t *dq = (int32_t *)(b->d_rgn + (size_t)nrc * qc);
-    HIPCHK(hipMemsetAsync(b->d_rflags + r0, 0, sizeof(uint32_t) * nr, b->stream));
     RgnArgs ra;
-    ra.queries = dq; ra.labels = (const int16_t *)b->d_rgt; ra.masks = b->d_rgt + lab_bytes; ra.constrain = constrain ? b->d_rgt + lab_bytes + mask_bytes : nullptr;
+    ra.labels = (const int16_t *)b->d_rgt; ra.masks = b->d_rgt + lab_bytes; ra.constrain = constrain ? b->d_rgt + lab_bytes + mask_bytes : nullptr;
     ra.nmask = nmask; ra.nlabel = nlabel; ra.pad_ = 0;
-    for (size_t q0 = 0; q0 < (size_t)nq; q0 += qc) {
-        const size_t nqc = std::min(qc, (size_t)nq - q0);
-        ra.nq = (int)nqc;
-        HIPCHK(hipMemcpyAsync(dq, queries + 4 * q0, nqc * 16, hipMemcpyHostToDevice, b->stream));
-        for (int rb = 0; rb < nr; rb += nrc) {
-            const int nrr = std::min(nrc, nr - rb);
-            // runs of restarts whose snapshot was taken under the same transition model (its plain tables)
-            for (int i = rb; i < rb + nrr;) {
-                int j = i; while (j < rb + nrr && b->lt_model[r0 + j] == b->lt_model[r0 + i]) j++;
-                const int model = b->lt_model[r0 + i];
-                const Dev dv = dev_for_model(b, model);
-                {
-                    ProfScope ps(b, KID_REGION);
-                    hipLaunchKernelGGL(k_region_prob, dim3((unsigned)nqc, j - i), dim3(RGN_NT), 0, b->stream, dv, r0 + i, model == d.tmodel ? 1 : 0, ra,
-                                       dout + (size_t)(i - rb) * nqc, b->d_rflags);
-                    HIPCHK(hipGetLastError());
-                }
-                i = j;
-            }
-            // device [nrr][nqc] -> host rows (rb .. rb+nrr)[q0 .. q0+nqc)
-            HIPCHK(hipMemcpy2DAsync(logp_out + (size_t)rb * nq + q0, (size_t)nq * 8, dout, nqc * 8, nqc * 8, nrr, hipMemcpyDeviceToHost, b->stream));
-        }
-    }
-    uint32_t *e = b->h_err;
-    HIPCHK(hipMemcpyAsync(e, b->d_rflags + r0, sizeof(uint32_t) * nr, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    for (int i = 0; i < nr; i++) if (e[i]) g_err_restarts.push_back(r0 + i);
-    if (!g_err_restarts.empty()) {
-        char buf[160]; snprintf(buf, sizeof buf, "region_prob: a backward step has a zero or non-finite normaliser (restart %d)", g_err_restarts[0]);
-        return fail_flagged(RMX_EASSERT, buf);
-    }
-    return RMX_OK;
+    return run_queries(b, r0, nr, nq, queries, 1, KID_REGION, "region_prob: a backward step has a zero or non-finite normaliser", logp_out,
+                       [&](const Dev &dv, int r, int n, int, int use_wb, const int32_t *dq, int nqc, double *out, uint32_t *flags) {
+        ra.queries = dq; ra.nq = nqc;
+        hipLaunchKernelGGL(k_region_prob, dim3((unsigned)nqc, n), dim3(RGN_NT), 0, b->stream, dv, r, use_wb, ra, out, flags);
+    });
 }
 
-// Region change counts (k_region_counts): rmx_region_prob's validation, staging, chunking and grouping of restarts by the
-// snapshot's transition model, with nbins outputs per (restart, query) and a label required in every query.
+// Region change counts (k_region_counts): rmx_region_prob with nbins outputs per (restart, query) and a label required in
+// every query.
 int rmx_region_counts(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
                       int32_t nlabel, const int16_t *labels, const uint8_t *constrain, int32_t nbins, double *logp_out) { BIND(b);
     if (!b || r0 < 0 || nr < 1 || (int64_t)r0 + nr > b->R) return fail(RMX_EARG, "bad restart range");
@@ -3163,97 +3162,34 @@ int rmx_region_counts(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const in
     const Dev &d = b->d;
     const int N = d.N, S = d.S, C_ = d.C;
     if (S > RGC_MAXS) return fail(RMX_EUNSUPPORTED, "region_counts: more than 1024 states");
-    {
-        // chain of a segment = the number of chain ends (tclass < 0) before it
-        std::vector<int32_t> chain(N);
-        int32_t c = 0;
-        for (int n = 0; n < N; n++) { chain[n] = c; if (b->tclass[n] < 0) c++; }
-        for (int i = 0; i < nq; i++) {
-            const int32_t *qq = queries + 4 * (size_t)i;
-            if (qq[0] < 0 || qq[1] >= N || qq[0] > qq[1]) return fail(RMX_EARG, "region_counts: a query needs 0 <= first <= last < num_segments");
-            if (chain[qq[0]] != chain[qq[1]]) return fail(RMX_EARG, "region_counts: a query crosses a chain end");
-            if (qq[2] < -1 || qq[2] >= nmask) return fail(RMX_EARG, "region_counts: mask index out of range");
-            if (qq[3] < 0 || qq[3] >= nlabel) return fail(RMX_EARG, "region_counts: a query needs a label index in [0, nlabel)");
-        }
-    }
-    // no update_p_cn yet: there is no posterior to evaluate (reported as rmx_sample_cn does)
-    g_err_restarts.clear();
-    for (int r = r0; r < r0 + nr; r++) if (!b->lt_valid[r]) g_err_restarts.push_back(r);
-    if (!g_err_restarts.empty()) {
-        char buf[160]; snprintf(buf, sizeof buf, "region_counts before update_p_cn (restart %d)", g_err_restarts[0]);
-        return fail_flagged(RMX_EVALUE, buf);
-    }
     int rc;
-    if (!b->d_rflags && (rc = dalloc(b, &b->d_rflags, b->R))) return rc;
+    if ((rc = check_queries(b, "region_counts", nq, queries, {-1, nmask, "region_counts: mask index out of range"},
+                            {0, nlabel, "region_counts: a query needs a label index in [0, nlabel)"}))) return rc;
+    if ((rc = require_snapshot(b, r0, nr, "region_counts"))) return rc;
     // tables: labels (2-byte entries first), masks, constrain
-    const size_t lab_bytes = (size_t)C_ * nlabel * S * sizeof(int16_t), mask_bytes = (size_t)C_ * nmask * S, tab_bytes = lab_bytes + mask_bytes + (constrain ? (size_t)N : 0);
-    if (b->rgt_cap < tab_bytes) {
-        dfree(b, b->d_rgt); b->d_rgt = nullptr; b->rgt_cap = 0;
-        if ((rc = dalloc(b, &b->d_rgt, tab_bytes))) return rc;
-        b->rgt_cap = tab_bytes;
-    }
+    const size_t lab_bytes = (size_t)C_ * nlabel * S * sizeof(int16_t), mask_bytes = (size_t)C_ * nmask * S;
+    if ((rc = grow(b, &b->d_rgt, &b->rgt_cap, lab_bytes + mask_bytes + (constrain ? (size_t)N : 0)))) return rc;
     if (lab_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt, labels, lab_bytes, hipMemcpyHostToDevice, b->stream));
     if (mask_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes, masks, mask_bytes, hipMemcpyHostToDevice, b->stream));
     if (constrain) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes + mask_bytes, constrain, (size_t)N, hipMemcpyHostToDevice, b->stream));
-    // staging in doubles: outputs [nrc][qc][nbins], then the chunk's queries [qc][4] int32
-    const size_t budget = (size_t)64 << 20;
-    const int nrc = std::min(nr, 65535);
-    const size_t qc = std::max<size_t>(1, std::min<size_t>((size_t)nq, budget / ((size_t)nrc * nbins * 8 + 16)));
-    const size_t need = (size_t)nrc * qc * nbins + 2 * qc;
-    if (b->rgn_cap < need) {
-        dfree(b, b->d_rgn); b->d_rgn = nullptr; b->rgn_cap = 0;
-        if ((rc = dalloc(b, &b->d_rgn, need))) return rc;
-        b->rgn_cap = need;
-    }
-    double *dout = b->d_rgn;
-    int32_t *dq = (int32_t *)(b->d_rgn + (size_t)nrc * qc * nbins);
     const size_t lds = rgc_lds_bytes(S);
     const int tiles = (S + 15) / 16, tpw = tiles <= 3 * RGC_NW ? 3 : (tiles <= 8 * RGC_NW ? 8 : 16);      // row tiles of 16 states per wave
     auto kf = tpw == 3 ? k_region_counts<3> : (tpw == 8 ? k_region_counts<8> : k_region_counts<16>);
     if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(hipMemsetAsync(b->d_rflags + r0, 0, sizeof(uint32_t) * nr, b->stream));
     RgnArgs ra;
-    ra.queries = dq; ra.labels = (const int16_t *)b->d_rgt; ra.masks = b->d_rgt + lab_bytes; ra.constrain = constrain ? b->d_rgt + lab_bytes + mask_bytes : nullptr;
+    ra.labels = (const int16_t *)b->d_rgt; ra.masks = b->d_rgt + lab_bytes; ra.constrain = constrain ? b->d_rgt + lab_bytes + mask_bytes : nullptr;
     ra.nmask = nmask; ra.nlabel = nlabel; ra.pad_ = 0;
-    for (size_t q0 = 0; q0 < (size_t)nq; q0 += qc) {
-        const size_t nqc = std::min(qc, (size_t)nq - q0);
-        ra.nq = (int)nqc;
-        HIPCHK(hipMemcpyAsync(dq, queries + 4 * q0, nqc * 16, hipMemcpyHostToDevice, b->stream));
-        for (int rb = 0; rb < nr; rb += nrc) {
-            const int nrr = std::min(nrc, nr - rb);
-            // runs of restarts whose snapshot was taken under the same transition model (its plain tables)
-            for (int i = rb; i < rb + nrr;) {
-                int j = i; while (j < rb + nrr && b->lt_model[r0 + j] == b->lt_model[r0 + i]) j++;
-                const int model = b->lt_model[r0 + i];
-                const Dev dv = dev_for_model(b, model);
-                {
-                    ProfScope ps(b, KID_REGION_COUNTS);
-                    hipLaunchKernelGGL(kf, dim3((unsigned)nqc, j - i), dim3(RGC_NT), lds, b->stream, dv, r0 + i, model == d.tmodel ? 1 : 0, ra, (int)nbins,
-                                       dout + (size_t)(i - rb) * nqc * nbins, b->d_rflags);
-                    HIPCHK(hipGetLastError());
-                }
-                i = j;
-            }
-            // device [nrr][nqc][nbins] -> host rows (rb .. rb+nrr)[q0 .. q0+nqc)
-            HIPCHK(hipMemcpy2DAsync(logp_out + ((size_t)rb * nq + q0) * nbins, (size_t)nq * nbins * 8, dout, nqc * nbins * 8, nqc * nbins * 8, nrr, hipMemcpyDeviceToHost, b->stream));
-        }
-    }
-    uint32_t *e = b->h_err;
-    HIPCHK(hipMemcpyAsync(e, b->d_rflags + r0, sizeof(uint32_t) * nr, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    for (int i = 0; i < nr; i++) if (e[i]) g_err_restarts.push_back(r0 + i);
-    if (!g_err_restarts.empty()) {
-        char buf[160]; snprintf(buf, sizeof buf, "region_counts: a backward step has a zero or non-finite normaliser (restart %d)", g_err_restarts[0]);
-        return fail_flagged(RMX_EASSERT, buf);
-    }
-    return RMX_OK;
+    return run_queries(b, r0, nr, nq, queries, nbins, KID_REGION_COUNTS, "region_counts: a backward step has a zero or non-finite normaliser", logp_out,
+                       [&](const Dev &dv, int r, int n, int, int use_wb, const int32_t *dq, int nqc, double *out, uint32_t *flags) {
+        ra.queries = dq; ra.nq = nqc;
+        hipLaunchKernelGGL(kf, dim3((unsigned)nqc, n), dim3(RGC_NT), lds, b->stream, dv, r, use_wb, ra, (int)nbins, out, flags);
+    });
 }
 
 // Call probabilities (k_call_prob): the log-probability that the path agrees with a reference path, up to a label, at every
-// bound segment of a run.  rmx_region_prob's validation, staging of queries and outputs (at most 64 MiB, chunked over
-// queries) and grouping of restarts by the snapshot's transition model; the reference paths of the call are checked here
-// (the kernel indexes label tables and weight rows with their entries) and staged whole beside the label tables.  One wave
-// computes a (restart, query) on its own, so a result depends on neither the restart range, the chunking nor the other paths.
+// bound segment of a run.  The reference paths of the call are checked here (the kernel indexes label tables and weight rows
+// with their entries) and staged whole beside the label tables; the rest is run_queries'.  One wave computes a (restart,
+// query) on its own, so a result depends on neither the restart range, the chunking nor the other paths.
 int rmx_call_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t npaths, const int16_t *paths, int32_t nq, const int32_t *queries,
                   int32_t nlabel, const int16_t *labels, const uint8_t *constrain, double *logp_out) { BIND(b);
     if (!b || r0 < 0 || nr < 1 || (int64_t)r0 + nr > b->R) return fail(RMX_EARG, "bad restart range");
@@ -3263,94 +3199,29 @@ int rmx_call_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t npaths, const in
     const Dev &d = b->d;
     const int N = d.N, S = d.S, C_ = d.C;
     if (S > CLP_MAXS) return fail(RMX_EUNSUPPORTED, "call_prob: more than 1024 states");
-    {
-        // chain of a segment = the number of chain ends (tclass < 0) before it
-        std::vector<int32_t> chain(N);
-        int32_t c = 0;
-        for (int n = 0; n < N; n++) { chain[n] = c; if (b->tclass[n] < 0) c++; }
-        for (int i = 0; i < nq; i++) {
-            const int32_t *qq = queries + 4 * (size_t)i;
-            if (qq[0] < 0 || qq[1] >= N || qq[0] > qq[1]) return fail(RMX_EARG, "call_prob: a query needs 0 <= first <= last < num_segments");
-            if (chain[qq[0]] != chain[qq[1]]) return fail(RMX_EARG, "call_prob: a query crosses a chain end");
-            if (qq[2] < -1 || qq[2] >= nlabel) return fail(RMX_EARG, "call_prob: label index out of range");
-            if (qq[3] < 0 || qq[3] >= npaths) return fail(RMX_EARG, "call_prob: path index out of range");
-        }
-        const size_t np = (size_t)nr * npaths * N;
-        for (size_t i = 0; i < np; i++) if (paths[i] < 0 || paths[i] >= S) return fail(RMX_EARG, "call_prob: a path entry is outside [0, num_cn_states)");
-    }
-    // no update_p_cn yet: there is no posterior to evaluate (reported as rmx_sample_cn does)
-    g_err_restarts.clear();
-    for (int r = r0; r < r0 + nr; r++) if (!b->lt_valid[r]) g_err_restarts.push_back(r);
-    if (!g_err_restarts.empty()) {
-        char buf[160]; snprintf(buf, sizeof buf, "call_prob before update_p_cn (restart %d)", g_err_restarts[0]);
-        return fail_flagged(RMX_EVALUE, buf);
-    }
-    if (nq == 0) return RMX_OK;
     int rc;
-    if (!b->d_rflags && (rc = dalloc(b, &b->d_rflags, b->R))) return rc;
+    if ((rc = check_queries(b, "call_prob", nq, queries, {-1, nlabel, "call_prob: label index out of range"}, {0, npaths, "call_prob: path index out of range"}))) return rc;
+    const size_t np = (size_t)nr * npaths * N;
+    for (size_t i = 0; i < np; i++) if (paths[i] < 0 || paths[i] >= S) return fail(RMX_EARG, "call_prob: a path entry is outside [0, num_cn_states)");
+    if ((rc = require_snapshot(b, r0, nr, "call_prob"))) return rc;
+    if (nq == 0) return RMX_OK;
     // tables: labels, paths (2-byte entries first), constrain
-    const size_t lab_bytes = (size_t)C_ * nlabel * S * sizeof(int16_t), path_bytes = (size_t)nr * npaths * N * sizeof(int16_t),
-                 tab_bytes = lab_bytes + path_bytes + (constrain ? (size_t)N : 0);
-    if (b->rgt_cap < tab_bytes) {
-        dfree(b, b->d_rgt); b->d_rgt = nullptr; b->rgt_cap = 0;
-        if ((rc = dalloc(b, &b->d_rgt, tab_bytes))) return rc;
-        b->rgt_cap = tab_bytes;
-    }
+    const size_t lab_bytes = (size_t)C_ * nlabel * S * sizeof(int16_t), path_bytes = np * sizeof(int16_t);
+    if ((rc = grow(b, &b->d_rgt, &b->rgt_cap, lab_bytes + path_bytes + (constrain ? (size_t)N : 0)))) return rc;
     if (lab_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt, labels, lab_bytes, hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes, paths, path_bytes, hipMemcpyHostToDevice, b->stream));
     if (constrain) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes + path_bytes, constrain, (size_t)N, hipMemcpyHostToDevice, b->stream));
-    // staging in doubles: outputs [nrc][qc], then the chunk's queries [qc][4] int32
-    const size_t budget = (size_t)64 << 20;
-    const int nrc = std::min(nr, 65535);
-    const size_t qc = std::max<size_t>(1, std::min<size_t>((size_t)nq, budget / ((size_t)nrc * 8 + 16)));
-    const size_t need = (size_t)nrc * qc + 2 * qc;
-    if (b->rgn_cap < need) {
-        dfree(b, b->d_rgn); b->d_rgn = nullptr; b->rgn_cap = 0;
-        if ((rc = dalloc(b, &b->d_rgn, need))) return rc;
-        b->rgn_cap = need;
-    }
-    double *dout = b->d_rgn;
-    int32_t *dq = (int32_t *)(b->d_rgn + (size_t)nrc * qc);
     const size_t lds = clp_lds_bytes(S);
     if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)k_call_prob, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(hipMemsetAsync(b->d_rflags + r0, 0, sizeof(uint32_t) * nr, b->stream));
     const int16_t *dpaths = (const int16_t *)(b->d_rgt + lab_bytes);
     ClpArgs ca;
-    ca.queries = dq; ca.labels = (const int16_t *)b->d_rgt; ca.constrain = constrain ? b->d_rgt + lab_bytes + path_bytes : nullptr;
+    ca.labels = (const int16_t *)b->d_rgt; ca.constrain = constrain ? b->d_rgt + lab_bytes + path_bytes : nullptr;
     ca.npaths = npaths; ca.nlabel = nlabel; ca.pad_ = 0;
-    for (size_t q0 = 0; q0 < (size_t)nq; q0 += qc) {
-        const size_t nqc = std::min(qc, (size_t)nq - q0);
-        ca.nq = (int)nqc;
-        HIPCHK(hipMemcpyAsync(dq, queries + 4 * q0, nqc * 16, hipMemcpyHostToDevice, b->stream));
-        for (int rb = 0; rb < nr; rb += nrc) {
-            const int nrr = std::min(nrc, nr - rb);
-            // runs of restarts whose snapshot was taken under the same transition model (its plain tables)
-            for (int i = rb; i < rb + nrr;) {
-                int j = i; while (j < rb + nrr && b->lt_model[r0 + j] == b->lt_model[r0 + i]) j++;
-                const int model = b->lt_model[r0 + i];
-                const Dev dv = dev_for_model(b, model);
-                ca.paths = dpaths + (size_t)i * npaths * N;
-                {
-                    ProfScope ps(b, KID_CALL_PROB);
-                    hipLaunchKernelGGL(k_call_prob, dim3((unsigned)((nqc + CLP_WPB - 1) / CLP_WPB), j - i), dim3(64 * CLP_WPB), lds, b->stream, dv, r0 + i,
-                                       model == d.tmodel ? 1 : 0, ca, dout + (size_t)(i - rb) * nqc, b->d_rflags);
-                    HIPCHK(hipGetLastError());
-                }
-                i = j;
-            }
-            // device [nrr][nqc] -> host rows (rb .. rb+nrr)[q0 .. q0+nqc)
-            HIPCHK(hipMemcpy2DAsync(logp_out + (size_t)rb * nq + q0, (size_t)nq * 8, dout, nqc * 8, nqc * 8, nrr, hipMemcpyDeviceToHost, b->stream));
-        }
-    }
-    uint32_t *e = b->h_err;
-    HIPCHK(hipMemcpyAsync(e, b->d_rflags + r0, sizeof(uint32_t) * nr, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    for (int i = 0; i < nr; i++) if (e[i]) g_err_restarts.push_back(r0 + i);
-    if (!g_err_restarts.empty()) {
-        char buf[160]; snprintf(buf, sizeof buf, "call_prob: a backward step has a zero or non-finite normaliser (restart %d)", g_err_restarts[0]);
-        return fail_flagged(RMX_EASSERT, buf);
-    }
-    return RMX_OK;
+    return run_queries(b, r0, nr, nq, queries, 1, KID_CALL_PROB, "call_prob: a backward step has a zero or non-finite normaliser", logp_out,
+                       [&](const Dev &dv, int r, int n, int i, int use_wb, const int32_t *dq, int nqc, double *out, uint32_t *flags) {
+        ca.queries = dq; ca.nq = nqc; ca.paths = dpaths + (size_t)i * npaths * N;
+        hipLaunchKernelGGL(k_call_prob, dim3((unsigned)((nqc + CLP_WPB - 1) / CLP_WPB), n), dim3(64 * CLP_WPB), lds, b->stream, dv, r, use_wb, ca, out, flags);
+    });
 }
 
 // ---- module-level functions -------------------------------------------------------------------

@@ -367,12 +367,19 @@ def add_region_change_counts(res, names, bins, counts):
     return res
 
 
+def check_region_options(cn_regions, change_bins, call_confidence):
+    """The outputs that are computed over regions need cn_regions: checked before a fit, not after it."""
+    if change_bins and cn_regions is None:
+        raise ValueError('cn_region_change_bins needs cn_regions')
+    if call_confidence and cn_regions is None:
+        raise ValueError('cn_call_confidence needs cn_regions')
+
+
 def change_bins(config):
     """Config value cn_region_change_bins, checked: 0 (off) or 1 .. 16 with cn_regions set."""
     from . import defaults
     bins = int(defaults.get_param(config, 'cn_region_change_bins') or 0)
-    if bins and defaults.get_param(config, 'cn_regions') is None:
-        raise ValueError('cn_region_change_bins needs cn_regions')
+    check_region_options(defaults.get_param(config, 'cn_regions'), bins, False)
     if not 0 <= bins <= 16:
         raise ValueError('cn_region_change_bins must be in 0 .. 16')
     return bins
@@ -448,6 +455,5 @@ def call_confidence_on(config):
     """Config value cn_call_confidence, checked: it needs cn_regions."""
     from . import defaults
     on = bool(defaults.get_param(config, 'cn_call_confidence'))
-    if on and defaults.get_param(config, 'cn_regions') is None:
-        raise ValueError('cn_call_confidence needs cn_regions')
+    check_region_options(defaults.get_param(config, 'cn_regions'), 0, on)
     return on

@@ -8,12 +8,13 @@ update for all restarts) and restarts are sharded over GPUs, one process per
 GPU, with ONE gather of the per-restart results at the end (RCCL over xGMI via
 torch.distributed; no communication during EM).
 """
+import collections
 import os
 
 import numpy as np
 
 from .cn_model import BreakpointModel
-from . import synthetic
+from . import posteriors, synthetic
 
 
 class SampleList(object):
@@ -1070,87 +1071,78 @@ def _failure_code(message):
     return 3
 
 
-def _sample_len(N, M, cn_samples):
-    """Float slots of the posterior-sample summary in a record (0 when sampling is off: the record is unchanged)."""
-    return 6 + N * M + N if cn_samples else 0
+_Section = collections.namedtuple('_Section', 'length pack unpack')      # pack(res, stats, view), unpack(view, res, stats)
 
 
-def _posterior_len(N, M, cn_posterior):
-    """Float slots of the exact posterior summary in a record (0 when it is off: the record is unchanged): six (N,)
-    arrays, two (N, M) arrays, two stats."""
-    return N * (6 + 2 * M) + 2 if cn_posterior else 0
+def _section(fields, group=None, head=(), tail=(), add=None):
+    """One optional section of a float record: the stats `head`, the arrays `fields` ((name, shape), read from res, or
+    from res[group]) and the stats `tail`.  Unpacking puts the arrays into res, or hands them, with the tail values, to
+    add(res, arrays, *tail values)."""
+    sizes = [int(np.prod(shape)) for _, shape in fields]
+
+    def pack(res, stats, view):
+        src = res if group is None else res[group]
+        view[:len(head)] = [stats[k] for k in head]
+        o = len(head)
+        for (k, _), n in zip(fields, sizes):
+            view[o:o + n] = np.asarray(src[k]).ravel(); o += n
+        view[o:] = [stats[k] for k in tail]
+
+    def unpack(view, res, stats):
+        stats.update((k, float(v)) for k, v in zip(head, view))
+        o = len(head); arrays = {}
+        for (k, shape), n in zip(fields, sizes):
+            arrays[k] = view[o:o + n].reshape(shape).copy(); o += n
+        if add is None:
+            res.update(arrays)
+        else:
+            add(res, arrays, *view[o:])
+    return _Section(len(head) + sum(sizes) + len(tail), pack, unpack)
 
 
-def _region_len(region_names):
-    """Float slots of the region event probabilities in a record (0 when config cn_regions is unset: the record is
-    unchanged): the seven arrays of posteriors.REGION_ARRAYS, one entry per region."""
-    return 7 * len(region_names) if region_names is not None else 0
-
-
-def _count_len(region_names, change_bins):
-    """Float slots of the region change counts in a record (0 when config cn_region_change_bins is 0: the record is
-    unchanged): the two arrays of posteriors.COUNT_ARRAYS, change_bins entries per region.  They are the record's last."""
-    return 2 * int(change_bins) * len(region_names) if change_bins and region_names is not None else 0
-
-
-def _call_len(region_names, call_confidence):
-    """Float slots of the call confidence in a record (0 when config cn_call_confidence is off: the record is unchanged):
-    the three arrays of posteriors.CALL_ARRAYS, one entry per region, and cn_logprob.  They are the record's last."""
-    return 3 * len(region_names) + 1 if call_confidence and region_names is not None else 0
-
-
-def _posterior_fields(N, M):
-    """(name, shape) of the arrays of posteriors.COMPACT_ARRAYS in record order."""
-    from .posteriors import COMPACT_ARRAYS
-    return [(k, (N, M) if k.startswith('total_cn') else (N,)) for k in COMPACT_ARRAYS]
+def _record_sections(N, M, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0, call_confidence=False):
+    """The optional sections of a float record, in record order.  The record is the fixed part -- header, h, parameters,
+    outlier probabilities: _HDR + M + nparams + 4 N floats -- and then, each only when its option is on (a record without
+    it is unchanged), at offsets that are the running sum of what precedes:
+      posterior samples (num_cn_samples > 0): the six sampling.SUMMARY_STATS, cn_sample_agreement (N, M), cn_state_agreement (N,);
+      posterior summary (cn_posterior_summary): the two posteriors.SUMMARY_STATS, the arrays of posteriors.COMPACT_ARRAYS;
+      region events (cn_regions): the seven arrays of posteriors.REGION_ARRAYS, one entry per region;
+      change counts (cn_region_change_bins, with regions): the two arrays of posteriors.COUNT_ARRAYS, (regions, bins) each;
+      call confidence (cn_call_confidence, with regions): the three arrays of posteriors.CALL_ARRAYS, then cn_logprob."""
+    from . import sampling
+    out = []
+    if cn_samples:
+        out.append(_section([('cn_sample_agreement', (N, M)), ('cn_state_agreement', (N,))], head=sampling.SUMMARY_STATS))
+    if cn_posterior:
+        out.append(_section([(k, (N, M) if k.startswith('total_cn') else (N,)) for k in posteriors.COMPACT_ARRAYS], head=posteriors.SUMMARY_STATS))
+    if region_names is not None:
+        nreg = len(region_names)
+        out.append(_section([(k, (nreg,)) for k in posteriors.REGION_ARRAYS], 'region_events',
+                            add=lambda res, a: posteriors.add_region_events(res, region_names, a)))
+        if change_bins:
+            out.append(_section([(k, (nreg, int(change_bins))) for k in posteriors.COUNT_ARRAYS], 'region_change_counts',
+                                add=lambda res, a: posteriors.add_region_change_counts(res, region_names, change_bins, a)))
+        if call_confidence:
+            out.append(_section([(k, (nreg,)) for k in posteriors.CALL_ARRAYS], 'call_confidence', tail=('cn_logprob',),
+                                add=lambda res, a, logprob: posteriors.add_call_confidence(res, region_names, a, logprob)))
+    return out
 
 
 def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0, call_confidence=False):
     """One restart's results as (float64 vector, int8 vector) of fixed length."""
-    from .sampling import SUMMARY_STATS
-    f = np.zeros(_HDR + M + nparams + 4 * N + _sample_len(N, M, cn_samples) + _posterior_len(N, M, cn_posterior) + _region_len(region_names)
-                 + _count_len(region_names, change_bins) + _call_len(region_names, call_confidence), dtype=np.float64)
-    tail = _call_len(region_names, call_confidence)      # what follows the region change counts
+    sections = _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence)
+    o = _HDR + M + nparams
+    f = np.zeros(o + 4 * N + sum(s.length for s in sections), dtype=np.float64)
     st = res['stats']
     f[0] = st['elbo']; f[1] = st['elbo_diff'] if st['elbo_diff'] is not None else np.nan
     f[2] = st['ploidy']; f[3] = st['proportion_divergent']
     f[4] = float(_failure_code(st.get('error_message', '')))
     f[_HDR:_HDR + M] = res['h']
-    f[_HDR + M:_HDR + M + nparams] = [st[k] for k in param_names]
-    o = _HDR + M + nparams
+    f[_HDR + M:o] = [st[k] for k in param_names]
     f[o:o + 2 * N] = res['p_outlier_total'].ravel(); f[o + 2 * N:o + 4 * N] = res['p_outlier_allele'].ravel()
-    if cn_samples:
-        o += 4 * N
-        f[o:o + 6] = [st[k] for k in SUMMARY_STATS]
-        f[o + 6:o + 6 + N * M] = np.asarray(res['cn_sample_agreement']).ravel()
-        f[o + 6 + N * M:o + 6 + N * M + N] = res['cn_state_agreement']
-    if cn_posterior:
-        from . import posteriors
-        o = len(f) - tail - _count_len(region_names, change_bins) - _region_len(region_names) - _posterior_len(N, M, True)
-        f[o:o + 2] = [st[k] for k in posteriors.SUMMARY_STATS]
-        o += 2
-        for k, shape in _posterior_fields(N, M):
-            n = int(np.prod(shape))
-            f[o:o + n] = np.asarray(res[k]).ravel(); o += n
-    if region_names is not None:
-        from . import posteriors
-        nreg = len(region_names)
-        o = len(f) - tail - _count_len(region_names, change_bins) - _region_len(region_names)
-        for j, k in enumerate(posteriors.REGION_ARRAYS):
-            f[o + j * nreg:o + (j + 1) * nreg] = res['region_events'][k]
-    if _count_len(region_names, change_bins):
-        from . import posteriors
-        n = len(region_names) * int(change_bins)
-        o = len(f) - tail - 2 * n
-        for j, k in enumerate(posteriors.COUNT_ARRAYS):
-            f[o + j * n:o + (j + 1) * n] = np.asarray(res['region_change_counts'][k]).ravel()
-    if tail:
-        from . import posteriors
-        nreg = len(region_names)
-        o = len(f) - tail
-        for j, k in enumerate(posteriors.CALL_ARRAYS):
-            f[o + j * nreg:o + (j + 1) * nreg] = res['call_confidence'][k]
-        f[-1] = st['cn_logprob']
+    o += 4 * N
+    for s in sections:
+        s.pack(res, st, f[o:o + s.length]); o += s.length
     i8 = np.zeros(N * M * 2 + K * M + 2 * N, dtype=np.int8)
     i8[:N * M * 2] = res['cn'].ravel()
     i8[N * M * 2:N * M * 2 + K * M] = np.array([res['brk_cn'][k] for k in brk_ids]).ravel()
@@ -1161,8 +1153,7 @@ def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_post
 
 def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0,
             call_confidence=False):
-    from .sampling import SUMMARY_STATS
-    tail = _call_len(region_names, call_confidence)      # what follows the region change counts
+    sections = _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence)
     res = dict()
     res['h'] = f[_HDR:_HDR + M].copy()
     o = _HDR + M + nparams
@@ -1179,39 +1170,10 @@ def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_sampl
           'mode_idx': init_params.get('mode_idx', 0), 'divergence_weight': init_params['divergence_weight']}
     for j, k in enumerate(param_names):
         st[k] = float(f[_HDR + M + j])
-    if cn_samples:
-        o += 4 * N
-        for j, k in enumerate(SUMMARY_STATS):
-            st[k] = float(f[o + j])
-        res['cn_sample_agreement'] = f[o + 6:o + 6 + N * M].reshape(N, M).copy()
-        res['cn_state_agreement'] = f[o + 6 + N * M:o + 6 + N * M + N].copy()
-    if cn_posterior:
-        from . import posteriors
-        o = len(f) - tail - _count_len(region_names, change_bins) - _region_len(region_names) - _posterior_len(N, M, True)
-        for j, k in enumerate(posteriors.SUMMARY_STATS):
-            st[k] = float(f[o + j])
-        o += 2
-        for k, shape in _posterior_fields(N, M):
-            n = int(np.prod(shape))
-            res[k] = f[o:o + n].reshape(shape).copy(); o += n
-    if region_names is not None:
-        from . import posteriors
-        nreg = len(region_names)
-        o = len(f) - tail - _count_len(region_names, change_bins) - _region_len(region_names)
-        posteriors.add_region_events(res, region_names, dict((k, f[o + j * nreg:o + (j + 1) * nreg].copy()) for j, k in enumerate(posteriors.REGION_ARRAYS)))
-    if _count_len(region_names, change_bins):
-        from . import posteriors
-        n = len(region_names) * int(change_bins)
-        o = len(f) - tail - 2 * n
-        posteriors.add_region_change_counts(res, region_names, change_bins, dict(
-            (k, f[o + j * n:o + (j + 1) * n].reshape(len(region_names), int(change_bins)).copy()) for j, k in enumerate(posteriors.COUNT_ARRAYS)))
-    res['stats'] = st
-    if tail:
-        from . import posteriors
-        nreg = len(region_names)
-        o = len(f) - tail
-        posteriors.add_call_confidence(res, region_names, dict((k, f[o + j * nreg:o + (j + 1) * nreg].copy()) for j, k in enumerate(posteriors.CALL_ARRAYS)),
-                                       f[-1])
+    res['stats'] = st      # (posteriors.add_call_confidence puts cn_logprob there)
+    o += 4 * N
+    for s in sections:
+        s.unpack(f[o:o + s.length], res, st); o += s.length
     return res
 
 
@@ -1237,10 +1199,7 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
     """
     import torch
     import torch.distributed as dist
-    if cn_region_change_bins and cn_regions is None:
-        raise ValueError('cn_region_change_bins needs cn_regions')
-    if cn_call_confidence and cn_regions is None:
-        raise ValueError('cn_call_confidence needs cn_regions')
+    posteriors.check_region_options(cn_regions, cn_region_change_bins, cn_call_confidence)
     distributed = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size() if distributed else 1
     rank = dist.get_rank() if distributed else 0
@@ -1256,16 +1215,7 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
                            **model_kwargs)
         rs.fit(num_em_iter, num_update_iter)
         local = rs.results()
-        if num_cn_samples > 0:
-            add_cn_sample_summaries(rs, local, experiment, num_cn_samples, cn_sample_seed, mine)
-        if cn_posterior_summary:
-            add_posterior_summaries(rs, local, experiment)
-        if cn_regions is not None:
-            add_region_events(rs, local, cn_regions)
-            if cn_region_change_bins:
-                add_region_change_counts(rs, local, cn_regions, cn_region_change_bins)
-            if cn_call_confidence:
-                add_call_confidence(rs, local, cn_regions)
+        add_optional_outputs(rs, local, experiment, mine, num_cn_samples, cn_sample_seed, cn_posterior_summary, cn_regions, cn_region_change_bins, cn_call_confidence)
         param_names = list(rs.models[0].likelihood_params)
         rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     if param_names is None:
@@ -1281,7 +1231,6 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
 def add_region_events(rs, results, cn_regions):
     """Add the region event probabilities of config cn_regions, a list of (name, first, last), of every restart of `rs`
     (a RestartSet / RestartGroups; one device call per batch) to results[r] (posteriors.add_region_events)."""
-    from . import posteriors
     names, regions = posteriors.parse_regions(cn_regions)
     events = rs.region_events(regions)
     for r, res in enumerate(results):
@@ -1292,7 +1241,6 @@ def add_region_events(rs, results, cn_regions):
 def add_region_change_counts(rs, results, cn_regions, bins):
     """Add the region change counts of config cn_regions / cn_region_change_bins of every restart of `rs` (a RestartSet /
     RestartGroups; one device call per batch) to results[r] (posteriors.add_region_change_counts)."""
-    from . import posteriors
     names, regions = posteriors.parse_regions(cn_regions)
     counts = rs.region_change_counts(regions, bins)
     for r, res in enumerate(results):
@@ -1304,7 +1252,6 @@ def add_call_confidence(rs, results, cn_regions):
     """Add the call confidence of config cn_regions / cn_call_confidence of every restart of `rs` (a RestartSet /
     RestartGroups; one device call per batch and quantity) to results[r], each for its own `cn`
     (posteriors.add_call_confidence)."""
-    from . import posteriors
     names, regions = posteriors.parse_regions(cn_regions)
     cn = [res['cn'] for res in results]
     conf = rs.call_confidence(regions, cn)
@@ -1331,6 +1278,24 @@ def add_cn_sample_summaries(rs, results, experiment, num_samples, seed, init_ids
     samples = rs.sample_cn(num_samples, seed, init_ids=list(init_ids))
     for res, smp in zip(results, samples):
         add_sample_summary(res, smp, experiment.l)
+    return results
+
+
+def add_optional_outputs(rs, results, experiment, init_ids, num_cn_samples=0, cn_sample_seed=0, cn_posterior_summary=False, cn_regions=None,
+                         cn_region_change_bins=0, cn_call_confidence=False):
+    """Add the optional outputs of a fit -- the config values of the same names -- of every restart of the fitted `rs` (a
+    RestartSet / RestartGroups) to results[r]; init_ids[r] selects restart r's posterior-sample stream.  The combination is
+    checked before the fit (posteriors.check_region_options)."""
+    if num_cn_samples > 0:
+        add_cn_sample_summaries(rs, results, experiment, num_cn_samples, cn_sample_seed, init_ids)
+    if cn_posterior_summary:
+        add_posterior_summaries(rs, results, experiment)
+    if cn_regions is not None:
+        add_region_events(rs, results, cn_regions)
+        if cn_region_change_bins:
+            add_region_change_counts(rs, results, cn_regions, cn_region_change_bins)
+        if cn_call_confidence:
+            add_call_confidence(rs, results, cn_regions)
     return results
 
 
@@ -1364,7 +1329,7 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
             per_rank = int(cnt_.item())
     if len(local) > per_rank:
         raise ValueError('gather_result_records: %d local results for a share of %d (pass local_ids for shares that are not shard_indices\')' % (len(local), per_rank))
-    flen = _HDR + M + nparams + 4 * N + _sample_len(N, M, cn_samples) + _posterior_len(N, M, cn_posterior) + _region_len(region_names) + _count_len(region_names, change_bins) + _call_len(region_names, call_confidence)
+    flen = _HDR + M + nparams + 4 * N + sum(s.length for s in _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence))
     ilen = N * M * 2 + K * M + 2 * N
     fbuf = np.full((per_rank, flen), np.nan); ibuf = np.zeros((per_rank, ilen), dtype=np.int8)
     for j, res in enumerate(local):

@@ -127,7 +127,8 @@ int rmx_synchronize(rmx_batch *b);
  * former (1 k_fbm: FP64 matrix cores at 4 restarts per workgroup, vector FMA at 2 / 1; 2 k_fbv: two-phase vector FMA, 3 k_fbk: weights from packed copy numbers, 4 k_fbq: matrix cores with
  * weights from 8-bit codes; 0: general kernel k_fb<0> only), 13 restarts per workgroup of that launch, 14 the lattice kernel of
  * the last decode (1 k_viterbi_reg, 2 k_viterbi_code, 3 k_viterbi, 4 k_viterbi_max, 5 k_viterbi_code_max, 6 k_viterbi_sad_max: above ~380 states); 18 workgroups per restart of that lattice, 19 the trace-back (1 parallel, 0 the sequential walk), 54 decodes repeated after a lattice cluster's watchdog ran out; 15 the largest number of restarts per workgroup of that launch (13 is the
- * smallest: k_fbm gives long chains fewer restarts per workgroup than short ones) */
+ * smallest: k_fbm gives long chains fewer restarts per workgroup than short ones); 64 the largest number of total-copy classes of a state table,
+ * 65 whether the cell cache keeps its read-depth planes per class (1) or per state (0; also without a cell cache) */
 int rmx_info(rmx_batch *b, int32_t what, int64_t *out);
 /* -- tuning options ------------------------------------------------------- */
 /* Not part of the reference protocol: which of this library's equivalent kernels / launch shapes run.  Results do not
@@ -179,6 +180,9 @@ enum rmx_option_id {
     RMX_OPT_TRACEBACK,          /* trace-back of the kept lattice rows (default transition model): 0 (default) in parallel -- the first arg-maximum of every target
                                    state of every row on the whole chip (k_bp_all), then the walk as a composition of maps (k_chase_compose / _ends / _fill);
                                    1 the sequential walk on one wave per restart (k_backtrace_max / k_backtrace_sad) */
+    RMX_OPT_LT_CLASSES,         /* creation time, 1 (default): the cell cache keeps the two read-depth planes per (segment, total-copy class) instead of per
+                                   (segment, state) -- states of a table with the same total copy numbers share the value to the bit -- where a table has at
+                                   most 128 such classes; 0: six planes per (segment, state).  Results are the same bits either way */
     RMX_OPT_COUNT
 };
 int rmx_set_default_option(int32_t option_id, int32_t value);

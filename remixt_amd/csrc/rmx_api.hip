@@ -75,7 +75,7 @@ static void pool_release(int dev, int role, hipStream_t s) {
 }
 
 // tuning options (include/remixt_amd.h rmx_option_id): process-wide defaults, copied into a batch at creation
-static int g_opt_default[RMX_OPT_COUNT] = {0, 0, 1, 1, 1, 0, 5, 0, 1, 1, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0};      // (search_mode 5 since round 5)
+static int g_opt_default[RMX_OPT_COUNT] = {0, 0, 1, 1, 1, 0, 5, 0, 1, 1, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 1};      // (search_mode 5 since round 5)
 static std::mutex g_opt_mu;
 
 struct rmx_batch {
@@ -611,30 +611,35 @@ static int ensure_tables(rmx_batch *b, int r0, int r1, bool need_segc = true) {
 // ---- strip kernels (S > 32, at most 4 states per lane) --------------------------------------------
 typedef void (*cells_kernel_t)(Dev, int);
 // cache: 0 none, 1 evaluate + store, 2 read
-template <int NS> static cells_kernel_t cells_kernel_ns(int mode, int mask, int cache) {
-    if (mode == 0) return cache == 2 ? k_cells<NS, 0, CM_ALL, 2> : (cache == 1 ? k_cells<NS, 0, CM_ALL, 1> : k_cells<NS, 0, CM_ALL, 0>);
-    if (mode == 1) return cache == 2 ? k_cells<NS, 1, CM_ALL, 2> : k_cells<NS, 1, CM_ALL, 0>;
-    if (mode == 3) return k_cells<NS, 3, CM_ALL, 2>;
-    if (cache == 2) return k_cells<NS, 2, 31, 2>;
-    if (cache == 1) {
-        switch (mask) {
-        case 1: return k_cells<NS, 2, 1, 1>; case 2: return k_cells<NS, 2, 2, 1>;
-        case 3: return k_cells<NS, 2, 3, 1>; case 4: return k_cells<NS, 2, 4, 1>; case 8: return k_cells<NS, 2, 8, 1>;
-        case 12: return k_cells<NS, 2, 12, 1>; case 15: return k_cells<NS, 2, 15, 1>; default: return k_cells<NS, 2, 31, 1>;
-        }
-    }
+// ltc: the read-depth planes of the cache per (segment, total-copy class) -- only with a cache (1, 2)
+template <int NS, int LTC> static cells_kernel_t cells_kernel_cached(int mode, int mask, int cache) {
+    if (mode == 0) return cache == 2 ? k_cells<NS, 0, CM_ALL, 2, LTC> : k_cells<NS, 0, CM_ALL, 1, LTC>;
+    if (mode == 1) return k_cells<NS, 1, CM_ALL, 2, LTC>;
+    if (mode == 3) return k_cells<NS, 3, CM_ALL, 2, LTC>;
+    if (cache == 2) return k_cells<NS, 2, 31, 2, LTC>;
     switch (mask) {
-    case 1: return k_cells<NS, 2, 1, 0>; case 2: return k_cells<NS, 2, 2, 0>;
-    case 3: return k_cells<NS, 2, 3, 0>; case 4: return k_cells<NS, 2, 4, 0>; case 8: return k_cells<NS, 2, 8, 0>;
-    case 12: return k_cells<NS, 2, 12, 0>; case 15: return k_cells<NS, 2, 15, 0>; default: return k_cells<NS, 2, 31, 0>;
+    case 1: return k_cells<NS, 2, 1, 1, LTC>; case 2: return k_cells<NS, 2, 2, 1, LTC>;
+    case 3: return k_cells<NS, 2, 3, 1, LTC>; case 4: return k_cells<NS, 2, 4, 1, LTC>; case 8: return k_cells<NS, 2, 8, 1, LTC>;
+    case 12: return k_cells<NS, 2, 12, 1, LTC>; case 15: return k_cells<NS, 2, 15, 1, LTC>; default: return k_cells<NS, 2, 31, 1, LTC>;
+    }
+}
+template <int NS> static cells_kernel_t cells_kernel_ns(int mode, int mask, int cache, bool ltc) {
+    if (cache) return ltc ? cells_kernel_cached<NS, 1>(mode, mask, cache) : cells_kernel_cached<NS, 0>(mode, mask, cache);
+    if (mode == 0) return k_cells<NS, 0, CM_ALL, 0, 0>;
+    if (mode == 1) return k_cells<NS, 1, CM_ALL, 0, 0>;
+    switch (mask) {
+    case 1: return k_cells<NS, 2, 1, 0, 0>; case 2: return k_cells<NS, 2, 2, 0, 0>;
+    case 3: return k_cells<NS, 2, 3, 0, 0>; case 4: return k_cells<NS, 2, 4, 0, 0>; case 8: return k_cells<NS, 2, 8, 0, 0>;
+    case 12: return k_cells<NS, 2, 12, 0, 0>; case 15: return k_cells<NS, 2, 15, 0, 0>; default: return k_cells<NS, 2, 31, 0, 0>;
     }
 }
 static bool use_strip(rmx_batch *b) { return b->d.S > 32 && b->d.S <= 384 && b->opt[RMX_OPT_STRIP]; }
 static cells_kernel_t cells_kernel(rmx_batch *b, int mode, int mask, int cache) {
     const int ns = (b->d.S + 63) / 64;
-    switch (ns) { case 1: return cells_kernel_ns<1>(mode, mask, cache); case 2: return cells_kernel_ns<2>(mode, mask, cache);
-                  case 3: return cells_kernel_ns<3>(mode, mask, cache); case 4: return cells_kernel_ns<4>(mode, mask, cache);
-                  case 5: return cells_kernel_ns<5>(mode, mask, cache); default: return cells_kernel_ns<6>(mode, mask, cache); }
+    const bool ltc = cache != 0 && b->d.ltc != nullptr;
+    switch (ns) { case 1: return cells_kernel_ns<1>(mode, mask, cache, ltc); case 2: return cells_kernel_ns<2>(mode, mask, cache, ltc);
+                  case 3: return cells_kernel_ns<3>(mode, mask, cache, ltc); case 4: return cells_kernel_ns<4>(mode, mask, cache, ltc);
+                  case 5: return cells_kernel_ns<5>(mode, mask, cache, ltc); default: return cells_kernel_ns<6>(mode, mask, cache, ltc); }
 }
 // block size of the sampled-objective kernels: one lane per state, whole waves, at most 256
 static dim3 ell_block(rmx_batch *b) { return dim3(std::min(256, ((b->d.S + 63) / 64) * 64)); }
@@ -869,7 +874,7 @@ int rmx_set_default_option(int32_t id, int32_t value) {
 static void configure_fb(rmx_batch *b);
 int rmx_set_option(rmx_batch *b, int32_t id, int32_t value) {
     if (!b || id < 0 || id >= RMX_OPT_COUNT || !option_value_ok(id, value)) return fail(RMX_EARG, "bad option id / value");
-    if (id == RMX_OPT_CELL_CACHE || id == RMX_OPT_SPARSE_TRIAL || id == RMX_OPT_FB_DEBUG || id == RMX_OPT_STREAM_POOL) return fail(RMX_EARG, "creation-time option: use rmx_set_default_option before rmx_batch_create");
+    if (id == RMX_OPT_CELL_CACHE || id == RMX_OPT_SPARSE_TRIAL || id == RMX_OPT_FB_DEBUG || id == RMX_OPT_STREAM_POOL || id == RMX_OPT_LT_CLASSES) return fail(RMX_EARG, "creation-time option: use rmx_set_default_option before rmx_batch_create");
     BIND(b);      // configure_fb sets function attributes (the > 64 KiB LDS opt-in) on the calling thread's current device
     b->opt[id] = value;
     if (id == RMX_OPT_FB_KERNEL) configure_fb(b);
@@ -1063,10 +1068,28 @@ int rmx_batch_create(const rmx_problem *pr, int32_t R, const double *h_init, con
         uint16_t *pi_ = nullptr; uint8_t *pc_ = nullptr;
         if (dalloc(b, &pi_, RN * RMX_SIGK) == RMX_OK && dalloc(b, &pc_, RN) == RMX_OK) { d.sig_idx = pi_; d.sig_cnt = pc_; }
     }
+    d.ltc = nullptr; d.ltcls = nullptr; d.ltrep = nullptr; d.NT = 0; d.NTP = 0;
     {
+        // total-copy classes of the state tables: the two read-depth planes of the cache are kept per (segment, class) where a table has at most 128 of them
+        std::vector<int32_t> cls_, rep_, cnt_;
+        int32_t nt_ = 0;
+        if (rmxh::lt_classes(b->cn_classes.data(), C, S, M, cls_, rep_, cnt_, &nt_)) { rmx_batch_destroy(b); return fail(RMX_EARG, "bad state tables"); }
+        d.NT = nt_; d.NTP = ((nt_ + 7) / 8) * 8;
+        const bool compact = b->opt[RMX_OPT_LT_CLASSES] != 0 && nt_ <= 128;
         const size_t bytes = RNS * 6 * 8;
         const bool want = b->opt[RMX_OPT_CELL_CACHE] != 0;
-        if (want && S > 32 && S <= 384 && bytes <= ((size_t)96 << 30)) { double *p_ = nullptr; if (dalloc(b, &p_, RNS * 6) == RMX_OK) { d.lc = p_; b->use_cache = true; } }
+        if (want && S > 32 && S <= 384 && bytes <= ((size_t)96 << 30)) {
+            double *p_ = nullptr, *q_ = nullptr;
+            if (!compact) { if (dalloc(b, &p_, RNS * 6) == RMX_OK) { d.lc = p_; b->use_cache = true; } }
+            else {
+                std::vector<uint8_t> cls8((size_t)C * S);
+                std::vector<int32_t> rep((size_t)C * d.NTP, 0);
+                for (size_t i = 0; i < cls8.size(); i++) cls8[i] = (uint8_t)cls_[i];
+                for (int c = 0; c < C; c++) for (int k = 0; k < cnt_[c]; k++) rep[(size_t)c * d.NTP + k] = rep_[(size_t)c * S + k];
+                if (dalloc(b, &p_, RNS * 4) == RMX_OK && dalloc(b, &q_, RN * d.NTP * 2) == RMX_OK &&
+                    dupload(b, &d.ltcls, cls8) == RMX_OK && dupload(b, &d.ltrep, rep) == RMX_OK) { d.lc = p_; d.ltc = q_; b->use_cache = true; }
+            }
+        }
     }
     if ((rc = dalloc(b, &b->d_lt_valid, R)) || (rc = dalloc(b, &b->d_partial, (size_t)R * ELBO_BLOCKS * 5)) || (rc = dalloc(b, &b->d_be_e, (size_t)R * std::max(d.NBE, 1))) || (rc = dalloc(b, &b->d_out4, (size_t)R * 5)) ||
         (rc = dalloc(b, &b->d_ell_partial, (size_t)R * std::max(N, ELBO_BLOCKS) * (1 + RMX_MAX_CLONES))) || (rc = dalloc(b, &b->d_ell_out, (size_t)R * 8)) ||
@@ -1191,6 +1214,7 @@ int rmx_info(rmx_batch *b, int32_t what, int64_t *out) { BIND(b);
     case 60: *out = b->t_launch_ns; break; case 61: *out = b->t_wait_ns; break; case 62: *out = b->t_post_ns; break; case 63: *out = b->n_rounds; break;
     case 12: *out = b->last_fb_kernel; break; case 13: *out = b->last_fb_nv; break; case 14: *out = b->last_viterbi; break; case 15: *out = b->last_fb_nv_max; break;
     case 18: *out = b->last_viterbi_wgs; break; case 19: *out = b->last_traceback; break;
+    case 64: *out = b->d.NT; break; case 65: *out = b->d.ltc ? 1 : 0; break;      // total-copy classes of the largest state table; compact read-depth planes in use
     case 54: *out = b->cluster_timeouts; break;      // decodes repeated with one workgroup per restart after a lattice cluster's watchdog ran out
     case 52: *out = b->last_search_blocks; break;      // blocks of the last device-driven search
     case 16: { StreamPool &p_ = g_stream_pool[b->device & 15]; std::lock_guard<std::mutex> lk(p_.mu); *out = p_.created[0] + p_.created[1]; break; }      // streams the device's pool has created so far
@@ -2648,7 +2672,7 @@ static int trial_pass(rmx_batch *b, int r0, int r1, Dev &d2) {
     HIPCHK(hipMemcpyAsync(b->d_A2 + RN0 * 2, d.A + RN0 * 2, cnt * 16, hipMemcpyDeviceToDevice, b->stream));
     HIPCHK(hipMemcpyAsync(b->d_Bv2 + RN0 * 4, d.Bv + RN0 * 4, cnt * 32, hipMemcpyDeviceToDevice, b->stream));
     d2 = b->d;
-    d2.A = b->d_A2; d2.Bv = b->d_Bv2; d2.lc = nullptr;
+    d2.A = b->d_A2; d2.Bv = b->d_Bv2; d2.lc = nullptr; d2.ltc = nullptr;
     for (int r = r0; r < r1;) {
         const int mask = use_strip(b) ? cover_mask(b->comp_dirty[r] & 15) : (b->comp_dirty[r] ? 15 : 0);
         int e = r + 1;

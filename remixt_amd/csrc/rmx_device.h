@@ -81,7 +81,12 @@ struct Dev {
     double *fe_alt;                      // [R][N][SP] second fe buffer: a fused marginal pass writes the NEXT sweep's scaled
                                          // emissions here while this sweep's breakend reductions still read fe (the host swaps)
     uint16_t *sig_idx; uint8_t *sig_cnt; // [R][N][RMX_SIGK], [R][N]: states with posterior mass >= RMX_POST_EPS per segment (count 255: more than RMX_SIGK, use all states), or null
-    double *lc;                          // [R][6][N][SP] cached cell likelihoods (LT0, LT1, LA00, LA01, LA10, LA11) or null
+    double *lc;                          // [R][6][N][SP] cached cell likelihoods (LT0, LT1, LA00, LA01, LA10, LA11) or null;
+                                         // with ltc: [R][4][N][SP] (LA00 .. LA11)
+    double *ltc;                         // [R][2][N][NTP] LT0, LT1 per (segment, total-copy class of the segment's state table), or null
+    const uint8_t *ltcls;                // [C][S] total-copy class of a state (rmxh::lt_classes)
+    const int32_t *ltrep;                // [C][NTP] first state of a class (0 past the table's count)
+    int NT, NTP;                         // most classes of a table; row stride of ltc (NT rounded up to 8)
     double *fmax, *mrow;                 // [R][N]
     double *A, *Bv;                      // [R][N][2], [R][N][4]
     double *rowPF, *rowPP, *rowZ;        // [R][N]

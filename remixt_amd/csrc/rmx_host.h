@@ -1,6 +1,7 @@
 // rmx_host.h -- the pieces of the C ABI that never touch the device, as plain C++ (no HIP types), so that the CPU test
 // suite can compile them with gcc -fsanitize=address,undefined (tests/csrc/host_sanitize.cpp, tests/test_sanitizers_cpu.py):
 //   compress_cn_states   rmx_compress_cn_states: dense (N,S,M,2) int64 state array -> class tables + class id per segment
+//   lt_classes           the total-copy classes of the state tables (compact read-depth planes of the cell cache)
 //   weighted_search      rmx_weighted_search: numpy's cumsum / searchsorted(side='right') for the weighted M-step samples
 //                        (reference remixt/cn_model.py:475-480)
 //   weighted_sample_round  rmx_weighted_sample_round: a whole round of that sampling from a strided weight column
@@ -42,6 +43,36 @@ inline int compress_cn_states(const int64_t *cn_states, int32_t N, int32_t S, in
         seg_class_out[n] = found;
     }
     *num_classes = C;
+    return 0;
+}
+
+// Total-copy classes of the state tables.  The read-depth likelihood of a (segment, state) cell depends on the state only
+// through its expected depth sum_m h[m] * tot[m] and the hdel branch, so the states of one table that share the tuple
+// tot[0..M) and the hdel bit share the value to the bit.  Per state-table class c: ltcls[c * S + s] is the total-copy class
+// of state s, numbered in order of first appearance; ltrep[c * S + k] the first state of class k (-1 past the table's
+// count); count[c] the number of classes of table c; *NT the largest count.
+inline int lt_classes(const int64_t *cn_classes, int32_t C, int32_t S, int32_t M,
+                      std::vector<int32_t> &ltcls, std::vector<int32_t> &ltrep, std::vector<int32_t> &count, int32_t *NT) {
+    if (!cn_classes || !NT || C < 1 || S < 1 || M < 1) return 5;
+    ltcls.assign((size_t)C * S, -1); ltrep.assign((size_t)C * S, -1); count.assign((size_t)C, 0);
+    std::vector<int64_t> keys((size_t)S * (M + 1)), key((size_t)M + 1);
+    int32_t nt = 0;
+    for (int c = 0; c < C; c++) {
+        int k = 0;
+        for (int s = 0; s < S; s++) {
+            const int64_t *t = cn_classes + ((size_t)c * S + s) * M * 2;
+            bool hdel = true;
+            for (int m = 0; m < M; m++) { key[(size_t)m] = t[m * 2] + t[m * 2 + 1]; if (t[m * 2] != 0 || t[m * 2 + 1] != 0) hdel = false; }
+            key[(size_t)M] = hdel ? 1 : 0;
+            int found = -1;
+            for (int j = 0; j < k && found < 0; j++) if (std::equal(key.begin(), key.end(), keys.begin() + (size_t)j * (M + 1))) found = j;
+            if (found < 0) { std::copy(key.begin(), key.end(), keys.begin() + (size_t)k * (M + 1)); ltrep[(size_t)c * S + k] = s; found = k++; }
+            ltcls[(size_t)c * S + s] = found;
+        }
+        count[(size_t)c] = k;
+        nt = std::max(nt, (int32_t)k);
+    }
+    *NT = nt;
     return 0;
 }
 

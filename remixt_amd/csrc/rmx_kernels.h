@@ -1992,8 +1992,13 @@ __global__ void k_marginals(Dev d, int r0, int G) {
 // d.lc, 2 = take all six values from the cache (no transcendental at all).  The six values depend on
 // (h, likelihood parameters, masks) only, i.e. they are constant across the variational sweeps of one
 // EM iteration; the host tracks per restart which components of the cache are current.
-template <int NS, int MODE, int MASK, int CACHE>
+// LTC 1 (with a cache only): the read-depth values LT0 / LT1 depend on the state through its total-copy class alone (expected depth and hdel
+// branch: rmxh::lt_classes), so the cache keeps them per (segment, class) in d.ltc and four planes (LA) per cell.  Per segment the lanes that own
+// a class put the two class rows into a wave-private LDS row -- read from d.ltc (CACHE 2) or evaluated from the class's first state and stored
+// (CACHE 1) -- and every lane takes the values of its states from there by class index: the same values in the same sums as with six planes.
+template <int NS, int MODE, int MASK, int CACHE, int LTC>
 __global__ __launch_bounds__(256) void k_cells(Dev d, int r0) {
+    static_assert(!LTC || CACHE != 0, "class rows belong to the cell cache");
     const int r = r0 + blockIdx.y;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -2008,19 +2013,36 @@ __global__ __launch_bounds__(256) void k_cells(Dev d, int r0) {
     unsigned err = 0;
     const double divw = rp.p[RMX_P_DIVERGENCE_WEIGHT];
     const size_t plane = (size_t)d.N * d.SP;
-    double *lcr = d.lc ? d.lc + (size_t)r * 6 * plane : nullptr;
-    // one cell through the cache policy
-    auto cell = [&](const SegCtx &sc, const StateRegs &stx, size_t off, double LT[2], double LA[4]) {
+    double *lcr = d.lc ? d.lc + (size_t)r * (LTC ? 4 : 6) * plane : nullptr;
+    double *lar = lcr ? lcr + (LTC ? 0 : 2) * plane : nullptr;      // the four LA planes
+    // class rows: which of LT0 / LT1 this kernel moves through them, the restart's two compact planes, the wave's LDS copy of a segment's rows
+    constexpr bool LTG0 = LTC && (CACHE == 2 || (MASK & CM_LT0)), LTG1 = LTC && (CACHE == 2 || (MASK & CM_LT1));
+    constexpr bool LTG = LTG0 || LTG1;
+    const size_t lplane = LTC ? (size_t)d.N * d.NTP : 0;
+    double *ltr = LTC ? d.ltc + (size_t)r * 2 * lplane : nullptr;
+    __shared__ double ltl[LTC ? 4 : 1][LTC ? 256 : 1];      // [wave][u * 128 + class]
+    unsigned ci_lo = 0, ci_hi = 0;      // class indices of the lane's states, 8 bits each (states 0 .. 3, 4 .. 5)
+    double repD[LTG && CACHE == 1 ? 2 : 1] = {}, repLogD[LTG && CACHE == 1 ? 2 : 1] = {};      // CACHE 1: table entries of the first state of the
+    unsigned repFl[LTG && CACHE == 1 ? 2 : 1] = {};                                             // classes lane, lane + 64
+    auto lt_gather = [&](int k, double LT[2]) {
+        const unsigned c_ = ((k < 4 ? ci_lo : ci_hi) >> (8 * (k & 3))) & 0xffu;
+        LT[0] = LTG0 ? ltl[wave][c_] : 0.;
+        LT[1] = LTG1 ? ltl[wave][128 + c_] : 0.;
+    };
+    // one cell through the cache policy (k: which of the lane's states)
+    auto cell = [&](const SegCtx &sc, const StateRegs &stx, size_t off, int k, double LT[2], double LA[4]) {
         if (CACHE == 2) {
-            LT[0] = lcr[off]; LT[1] = lcr[plane + off];
-            LA[0] = lcr[2 * plane + off]; LA[1] = lcr[3 * plane + off]; LA[2] = lcr[4 * plane + off]; LA[3] = lcr[5 * plane + off];
+            if (LTC) lt_gather(k, LT);
+            else { LT[0] = lcr[off]; LT[1] = lcr[plane + off]; }
+            LA[0] = lar[off]; LA[1] = lar[plane + off]; LA[2] = lar[2 * plane + off]; LA[3] = lar[3 * plane + off];
         } else {
-            cell_ll_regs<MASK & CM_ALL>(rp, sc, stx, LT, LA, err);
+            cell_ll_regs<LTC ? (MASK & (CM_LA0 | CM_LA1)) : (MASK & CM_ALL)>(rp, sc, stx, LT, LA, err);
+            if (LTC) lt_gather(k, LT);
             if (CACHE == 1) {
-                if (MASK & CM_LT0) lcr[off] = LT[0];
-                if (MASK & CM_LT1) lcr[plane + off] = LT[1];
-                if (MASK & CM_LA0) { lcr[2 * plane + off] = LA[0]; lcr[3 * plane + off] = LA[1]; }
-                if (MASK & CM_LA1) { lcr[4 * plane + off] = LA[2]; lcr[5 * plane + off] = LA[3]; }
+                if (!LTC && (MASK & CM_LT0)) lcr[off] = LT[0];
+                if (!LTC && (MASK & CM_LT1)) lcr[plane + off] = LT[1];
+                if (MASK & CM_LA0) { lar[off] = LA[0]; lar[plane + off] = LA[1]; }
+                if (MASK & CM_LA1) { lar[2 * plane + off] = LA[2]; lar[3 * plane + off] = LA[3]; }
             }
         }
     };
@@ -2040,26 +2062,73 @@ __global__ __launch_bounds__(256) void k_cells(Dev d, int r0) {
     }
     for (int n = nbeg; n < nend; n++) {     // n is wave-uniform (SGPR)
         const int cls = d.seg_class[n];
-        if (CACHE != 2 && cls != cur_cls) {
+        if ((CACHE != 2 || LTG) && cls != cur_cls) {
+            if (CACHE != 2) {
 #pragma unroll
-            for (int k = 0; k < NS; k++) { const int s = lane + 64 * k; load_state_regs(d, r, cls, s < S ? s : S - 1, st[k]); }   // clamped: lanes past S are masked at use
+                for (int k = 0; k < NS; k++) { const int s = lane + 64 * k; load_state_regs(d, r, cls, s < S ? s : S - 1, st[k]); }   // clamped: lanes past S are masked at use
+            }
+            if (LTG) {
+                ci_lo = 0u; ci_hi = 0u;
+#pragma unroll
+                for (int k = 0; k < NS; k++) {
+                    const int s = lane + 64 * k;
+                    const unsigned c_ = d.ltcls[(size_t)cls * S + (s < S ? s : S - 1)];
+                    if (k < 4) ci_lo |= c_ << (8 * (k & 3)); else ci_hi |= c_ << (8 * (k & 3));
+                }
+                if (CACHE == 1) {
+#pragma unroll
+                    for (int j = 0; j < 2; j++) {
+                        const int kc = lane + 64 * j;
+                        if (kc < d.NT) {
+                            const size_t si = ((size_t)r * d.C + cls) * d.SP + d.ltrep[(size_t)cls * d.NTP + kc];
+                            repD[LTG && CACHE == 1 ? j : 0] = d.stD[si]; repLogD[LTG && CACHE == 1 ? j : 0] = d.stLogD[si]; repFl[LTG && CACHE == 1 ? j : 0] = d.stFlags[si];
+                        }
+                    }
+                }
+            }
             cur_cls = cls;
         }
         SegCtx sc; load_seg(d, r, n, sc);
         const size_t rn = (size_t)r * d.N + n;
         const size_t ro = rn * d.SP;
+        // the segment's class rows: requested here (CACHE 2), in the wave's LDS row before the first cell needs them (lt_rows_to_lds)
+        double ltq0 = 0., ltq1 = 0.;
+        if (LTG && CACHE == 2 && lane < d.NT) { ltq0 = ltr[(size_t)n * d.NTP + lane]; ltq1 = ltr[lplane + (size_t)n * d.NTP + lane]; }
+        auto lt_rows_to_lds = [&]() {
+            if (!LTG) return;
+            const size_t lo_ = (size_t)n * d.NTP;
+            if (CACHE == 2) {
+                if (lane < d.NT) { ltl[wave][lane] = ltq0; ltl[wave][128 + lane] = ltq1; }
+                if (d.NT > 64 && lane + 64 < d.NT) { ltl[wave][64 + lane] = ltr[lo_ + 64 + lane]; ltl[wave][192 + lane] = ltr[lplane + lo_ + 64 + lane]; }      // (wave-uniform: four-clone grids)
+            } else {
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+                    const int kc = lane + 64 * j;
+                    if ((j == 0 || d.NT > 64) && kc < d.NT) {
+                        StateRegs rs_ = {};
+                        rs_.D = repD[LTG && CACHE == 1 ? j : 0]; rs_.logD = repLogD[LTG && CACHE == 1 ? j : 0]; rs_.fl = repFl[LTG && CACHE == 1 ? j : 0];
+                        double LTc[2], LAc[4];
+                        cell_ll_regs<MASK & (CM_LT0 | CM_LT1)>(rp, sc, rs_, LTc, LAc, err);
+                        if (LTG0) { ltr[lo_ + kc] = LTc[0]; ltl[wave][kc] = LTc[0]; }
+                        if (LTG1) { ltr[lplane + lo_ + kc] = LTc[1]; ltl[wave][128 + kc] = LTc[1]; }
+                    }
+                }
+            }
+            __builtin_amdgcn_wave_barrier();      // (the wave's lanes run in step and its LDS operations complete in order: no s_barrier)
+        };
         if (MODE == 0) {
             const double qt0 = d.qt[rn * 2], qt1 = d.qt[rn * 2 + 1], qa0 = d.qa[rn * 2], qa1 = d.qa[rn * 2 + 1];
             const double qs0 = d.qs[rn * 2], qs1 = d.qs[rn * 2 + 1];
             double fv[NS];
             double vmax = -INFINITY;
+            lt_rows_to_lds();
 #pragma unroll
             for (int k = 0; k < NS; k++) {
                 const int s = lane + 64 * k;
                 fv[k] = -INFINITY;
                 if (s < S) {
                     double LT[2], LA[4];
-                    cell(sc, st[k], (size_t)n * d.SP + s, LT, LA);
+                    cell(sc, st[k], (size_t)n * d.SP + s, k, LT, LA);
                     double f = 0.;
                     f += qt0 * LT[0]; f += qt1 * LT[1];
                     f += qa0 * qs0 * LA[0]; f += qa0 * qs1 * LA[1]; f += qa1 * qs0 * LA[2]; f += qa1 * qs1 * LA[3];
@@ -2079,8 +2148,11 @@ __global__ __launch_bounds__(256) void k_cells(Dev d, int r0) {
             constexpr bool M1 = MODE == 1 || MODE == 3;
             // planes of the cell cache kept in a wave-private LDS stash between the pass's two reads of them (expectations, then the next sweep's
             // frame values): all six up to 192 states (36 KB per block); three of six up to 384 (round 4: at 355 states the second read of all six missed
-            // L2 -- 512 waves per XCD x 17 KB -- and the pass moved 1.46 x its algorithmic bytes); the other three are read again
-            constexpr int NSTASH = MODE != 3 ? 0 : (NS <= 3 ? 6 : (NS <= 6 ? 3 : 0));
+            // L2 -- 512 waves per XCD x 17 KB -- and the pass moved 1.46 x its algorithmic bytes); the other three are read again.
+            // With class rows (LTC) the LT values stay in the wave's class rows (8 KB per block) and the stash holds LA planes only: within the same
+            // 36 KB all four up to 192 states, three up to 256, two up to 384
+            constexpr int LAOFF = LTC ? 0 : 2;      // stash planes 0, 1: LT (six-plane form only); LAOFF ..: LA -- the first NSTASH of them
+            constexpr int NSTASH = MODE != 3 ? 0 : LTC ? (NS <= 3 ? 4 : (NS == 4 ? 3 : 2)) : (NS <= 3 ? 6 : (NS <= 6 ? 3 : 0));
             constexpr bool STASH = NSTASH > 0;
             __shared__ double lsm[STASH ? 4 : 1][STASH ? NS * NSTASH * 64 : 1];
             double pv[NS];
@@ -2126,6 +2198,7 @@ __global__ __launch_bounds__(256) void k_cells(Dev d, int r0) {
             double a0 = 0., a1 = 0., b0 = 0., b1 = 0., b2 = 0., b3 = 0., pf = 0., pp = 0.;
             double fq[6] = {0., 0., 0., 0., 0., 0.};      // MODE 1: the indicators this sweep's frame log-probabilities were built from
             if (MODE == 1) { fq[0] = d.qt[rn * 2]; fq[1] = d.qt[rn * 2 + 1]; fq[2] = d.qa[rn * 2]; fq[3] = d.qa[rn * 2 + 1]; fq[4] = d.qs[rn * 2]; fq[5] = d.qs[rn * 2 + 1]; }
+            lt_rows_to_lds();
 #pragma unroll
             for (int k = 0; k < NS; k++) {
                 const int s = lane + 64 * k;
@@ -2133,13 +2206,13 @@ __global__ __launch_bounds__(256) void k_cells(Dev d, int r0) {
                 if (MODE == 2 && CACHE == 0 && !(MASK & 16) && !__any(pv[k] >= RMX_POST_EPS)) { if (s < S) cell_static_errors<MASK & CM_ALL>(sc, st[k].fl, err); continue; }
                 if (s < S) {
                     double LT[2], LA[4];
-                    cell(sc, st[k], (size_t)n * d.SP + s, LT, LA);
+                    cell(sc, st[k], (size_t)n * d.SP + s, k, LT, LA);
                     const double ps = pv[k];
-                    if (STASH) {      // planes 0, 1: LT; 2 .. 5: LA -- the first NSTASH of them
+                    if (STASH) {
 #pragma unroll
-                        for (int q_ = 0; q_ < 2; q_++) if (q_ < NSTASH) lsm[wave][(k * NSTASH + q_) * 64 + lane] = LT[q_];
+                        for (int q_ = 0; q_ < 2; q_++) if (!LTC && q_ < NSTASH) lsm[wave][(k * NSTASH + q_) * 64 + lane] = LT[q_];
 #pragma unroll
-                        for (int q_ = 0; q_ < 4; q_++) if (2 + q_ < NSTASH) lsm[wave][(k * NSTASH + 2 + q_) * 64 + lane] = LA[q_];
+                        for (int q_ = 0; q_ < 4; q_++) if (LAOFF + q_ < NSTASH) lsm[wave][(k * NSTASH + LAOFF + q_) * 64 + lane] = LA[q_];
                     }
                     a0 += ps * LT[0]; a1 += ps * LT[1];
                     b0 += ps * LA[0]; b1 += ps * LA[1]; b2 += ps * LA[2]; b3 += ps * LA[3];
@@ -2225,11 +2298,14 @@ __global__ __launch_bounds__(256) void k_cells(Dev d, int r0) {
                         double LT[2], LA[4];
                         if (STASH) {
                             const size_t off_ = (size_t)n * d.SP + s;
+                            if (LTC) lt_gather(k, LT);      // the class rows are where the expectations' gather left them
+                            else {
 #pragma unroll
-                            for (int q_ = 0; q_ < 2; q_++) LT[q_] = q_ < NSTASH ? lsm[wave][(k * NSTASH + q_) * 64 + lane] : lcr[q_ * plane + off_];
+                                for (int q_ = 0; q_ < 2; q_++) LT[q_] = q_ < NSTASH ? lsm[wave][(k * NSTASH + q_) * 64 + lane] : lcr[q_ * plane + off_];
+                            }
 #pragma unroll
-                            for (int q_ = 0; q_ < 4; q_++) LA[q_] = 2 + q_ < NSTASH ? lsm[wave][(k * NSTASH + 2 + q_) * 64 + lane] : lcr[(2 + q_) * plane + off_];
-                        } else cell(sc, st[k], (size_t)n * d.SP + s, LT, LA);
+                            for (int q_ = 0; q_ < 4; q_++) LA[q_] = LAOFF + q_ < NSTASH ? lsm[wave][(k * NSTASH + LAOFF + q_) * 64 + lane] : lar[q_ * plane + off_];
+                        } else cell(sc, st[k], (size_t)n * d.SP + s, k, LT, LA);
                         double f = 0.;
                         f += qt0 * LT[0]; f += qt1 * LT[1];
                         f += qa0 * qs0 * LA[0]; f += qa0 * qs1 * LA[1]; f += qa1 * qs0 * LA[2]; f += qa1 * qs1 * LA[3];

@@ -417,6 +417,26 @@ int rmx_region_counts(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const in
 int rmx_call_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t npaths, const int16_t *paths, int32_t nq, const int32_t *queries,
                   int32_t nlabel, const int16_t *labels, const uint8_t *constrain, double *logp_out);
 
+/* Region moments: the exact mean and covariance, under the structured posterior of the last update_p_cn, of weighted sums
+ * of state features over runs of segments: F_f = sum_{n in [first, last]} w[n] phi_f(c_n) for the nf features f0 .. f0+nf-1 of
+ * a query.  It complements rmx_posterior_summary, whose per-segment means and SDs do not combine over a region because
+ * neighbouring segments are correlated, and rmx_sample_cn, which gives the same numbers to 1 / sqrt(samples): this is what
+ * puts an exact error bar on ploidy, on the mean copy number of an arm or on the fraction of a region in LOH.
+ *   queries   int32 [nq][4]: first, last (as rmx_region_prob), f0 in [0, nfeat - nf], weight vector in [0, nw)
+ *   features  double [C][nfeat][S], one table per state class; weights double [nw][N]; all finite
+ *   nf        features per query, 1 .. 4 (the same for every query of a call)
+ *   out       [nr][nq][nf + nf (nf + 1) / 2]: E[F_f] for f = 0 .. nf-1, then Cov(F_f, F_g) for f <= g in row-major order of the
+ *             upper triangle
+ * A (restart, query) result is bit-identical in any restart range and any batch of queries, and a feature's mean and
+ * variance do not depend on the other features of its query.
+ * RMX_EARG, with nothing launched and out untouched: a bad range, nq < 1, nf outside [1, 4] or above nfeat, nw < 1, a NULL
+ * table, a feature or weight that is not finite, a query as for rmx_region_prob, f0 or the weight index out of range.
+ * RMX_EVALUE with the restarts listed: a restart has had no update_p_cn.  RMX_EASSERT with the restarts listed: a backward
+ * step met a zero or non-finite normaliser under non-zero mass, or an output is not finite (every output of that query is
+ * NaN).  RMX_EUNSUPPORTED: more than 1024 states. */
+int rmx_region_moments(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nfeat, const double *features,
+                       int32_t nw, const double *weights, int32_t nf, double *out);
+
 /* -- module-level functions on caller-supplied dense inputs ----------------- */
 /* sum_product (:1213-1246): f [N][S], T [N-1][S][S] -> alphas, betas [N][S] */
 int rmx_sum_product(const double *f, const double *T, double *alphas, double *betas,

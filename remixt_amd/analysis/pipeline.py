@@ -8,7 +8,7 @@ import numpy as np
 
 from .. import defaults, posteriors, sampling
 from ..cn_model import BreakpointModel
-from ..restarts import RestartSet, add_call_confidence, add_cn_sample_summaries, add_optional_outputs, add_posterior_summaries, add_region_change_counts, add_region_events, collect_fit_results, fit_restarts_distributed, select_optimal  # noqa: F401
+from ..restarts import RestartSet, add_call_confidence, add_cn_sample_summaries, add_optional_outputs, add_posterior_summaries, add_region_change_counts, add_region_cn_moments, add_region_events, collect_fit_results, fit_restarts_distributed, select_optimal  # noqa: F401
 
 
 def _model_kwargs(experiment, config):
@@ -34,6 +34,7 @@ def fit(experiment, init_params, config, device=0, quiet=False, init_id=0):
     when config num_cn_samples > 0."""
     bins = posteriors.change_bins(config)      # (a bad combination fails before the fit, not after it)
     call_conf = posteriors.call_confidence_on(config)
+    moments = posteriors.region_moments_on(config)
     h_init = np.array([
         init_params['h_normal'],
         init_params['h_tumour'] * init_params['mix_frac'],
@@ -77,6 +78,8 @@ def fit(experiment, init_params, config, device=0, quiet=False, init_id=0):
             posteriors.add_region_change_counts(res, names, bins, model.region_change_counts(regions, bins))
         if call_conf:
             posteriors.add_call_confidence(res, names, model.call_confidence(regions, res['cn']), model.cn_logprob(res['cn']))
+        if moments:
+            posteriors.add_region_cn_moments(res, names, model.region_cn_moments(posteriors.genome_region(regions, len(res['cn']))))
     return res
 
 
@@ -107,6 +110,7 @@ def fit_restarts(experiment, init_params_by_id, config, device=0, quiet=True, se
     `groups` RestartSets on their own streams and host threads (same per-restart results)."""
     bins = posteriors.change_bins(config)      # (a bad combination fails before the fit, not after it)
     call_conf = posteriors.call_confidence_on(config)
+    moments = posteriors.region_moments_on(config)
     ids = sorted(init_params_by_id)
     params = [init_params_by_id[i] for i in ids]
     max_cn = defaults.get_param(config, 'max_copy_number')
@@ -119,7 +123,7 @@ def fit_restarts(experiment, init_params_by_id, config, device=0, quiet=True, se
                         **_model_kwargs(experiment, config))
     rs.fit(defaults.get_param(config, 'num_em_iter'), defaults.get_param(config, 'num_update_iter'))
     results = add_optional_outputs(rs, rs.results(), experiment, ids, defaults.get_param(config, 'num_cn_samples'), defaults.get_param(config, 'cn_sample_seed'),
-                                   defaults.get_param(config, 'cn_posterior_summary'), defaults.get_param(config, 'cn_regions'), bins, call_conf)
+                                   defaults.get_param(config, 'cn_posterior_summary'), defaults.get_param(config, 'cn_regions'), bins, call_conf, moments)
     out = dict(zip(ids, results))
     rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     return out
@@ -274,6 +278,10 @@ def store_fit_results(store, experiment, fit_results, key_prefix):
     if 'call_confidence' in fit_results:          # (config cn_call_confidence)
         for k in posteriors.CALL_ARRAYS:
             store[key_prefix + '/' + k] = pd.Series(np.asarray(fit_results['call_confidence'][k]))
+    if 'region_cn_moments' in fit_results:        # (config cn_region_moments; total_cn_mean is also a per-segment array: region_ in front)
+        for k in posteriors.MOMENT_ARRAYS:
+            v = np.asarray(fit_results['region_cn_moments'][k])
+            store[key_prefix + '/region_' + k] = pd.Series(v) if v.ndim == 1 else pd.DataFrame(v.reshape(len(v), -1))
 
 
 def store_optimal_solution(stats, store, config):

@@ -673,6 +673,29 @@ class RemixtBatch(object):
                                          obuf.ctypes.data_as(_dp)))
         return out
 
+    def region_moments_raw(self, r0, nr, queries, features, weights, nf):
+        """Exact means and covariances (nr, nq, nf + nf (nf + 1) / 2) of weighted sums of state features over runs of model
+        segments, under the structured posterior of the last update_p_cn of restarts r0 .. r0+nr-1 (rmx_region_moments).
+        queries int (nq, 4): first segment, last segment (both of one chain), first feature f0, weight vector; features
+        (C, nfeat, S) and weights (nw, N), finite doubles.  With F_f = sum over the run of weights[n] features[class of n,
+        f0 + f, state of n] for f < nf, a query gives E[F_f] for every f, then Cov(F_f, F_g) for f <= g in row-major order
+        of the upper triangle.  nf in 1 .. 4."""
+        r0, nr, nf = int(r0), int(nr), int(nf)
+        N, S, C_ = self.num_segments, self.num_cn_states, self.cn_classes.shape[0]
+        q, args, _keep = self._region_args(queries, None, None, None)
+        ft = np.ascontiguousarray(features, dtype=np.float64)
+        if ft.ndim != 3 or ft.shape[0] != C_ or ft.shape[2] != S:
+            raise ValueError('features must have shape (num_classes, nfeat, num_cn_states)')
+        wt = np.ascontiguousarray(weights, dtype=np.float64)
+        if wt.ndim != 2 or wt.shape[1] != N:
+            raise ValueError('weights must have shape (nw, num_segments)')
+        per = max(nf, 0) + max(nf, 0) * (max(nf, 0) + 1) // 2
+        out = np.zeros((max(nr, 0), q.shape[0], per), dtype=np.float64)
+        obuf = out if out.size else np.zeros(1)
+        self._ck(self._lib.rmx_region_moments(self._handle, r0, nr, args[0], args[1], ft.shape[1], ft.ctypes.data_as(_dp) if ft.size else _dp(),
+                                              wt.shape[0], wt.ctypes.data_as(_dp) if wt.size else _dp(), nf, obuf.ctypes.data_as(_dp)))
+        return out
+
     # -- measurement ------------------------------------------------------------
     def timer_start(self):
         self._ck(self._lib.rmx_timer_start(self._handle))
@@ -903,6 +926,10 @@ class RemixtModel(object):
     def region_counts(self, queries, masks, labels, constrain, nbins):
         """RemixtBatch.region_counts_raw of this model: log-probabilities (nq, nbins)."""
         return self._batch.region_counts_raw(self._r, 1, queries, masks, labels, constrain, nbins)[0]
+
+    def region_moments(self, queries, features, weights, nf):
+        """RemixtBatch.region_moments_raw of this model: means and covariances (nq, nf + nf (nf + 1) / 2)."""
+        return self._batch.region_moments_raw(self._r, 1, queries, features, weights, nf)[0]
 
     def call_logprob(self, paths, queries, labels=None, constrain=None):
         """RemixtBatch.call_logprob_raw of this model: paths (npaths, N) -> log-probabilities (nq,)."""

@@ -763,6 +763,27 @@ class BreakpointModel(object):
                                                     self.is_telomere, bins=bins)
         return dict((k, v[0]) for k, v in out.items())
 
+    def region_cn_moments(self, regions):
+        """Exact posterior mean and covariance, under the structured posterior of the last variational update, of copy
+        number over regions ((first, last) experiment segment indices): a dict of `length` (R,), `total_cn_mean` (R, M) and
+        `total_cn_cov` (R, M, M) -- the length-weighted mean total copy number of each clone over the region, with the
+        covariance matrix that the correlation between neighbouring segments gives it -- and `fraction_mean` (R, 4) and
+        `fraction_cov` (R, 4, 4) of the length fractions of posteriors.MOMENT_FRACTIONS.  Zero-length segments inserted at
+        shared boundaries have no weight; a region of length 0 gives NaN."""
+        from . import posteriors
+        if not hasattr(self.model, 'region_moments'):
+            raise NotImplementedError('kernel module %s has no region moments' % getattr(self._kernel_module(), '__name__', '?'))
+        out = posteriors.batch_region_cn_moments(self.model._batch, self.model._r, 1, regions, self.seg_fwd_remap, self.seg_is_original,
+                                                 self.is_telomere, self.l1)
+        return dict((k, v if k == 'length' else v[0]) for k, v in out.items())
+
+    def ploidy_posterior_sd(self):
+        """The exact posterior SD of the tumour ploidy whose mean is stats['ploidy_posterior_mean']: the whole genome as one
+        region of region_cn_moments (posteriors.moment_stats)."""
+        from . import posteriors
+        mom = self.region_cn_moments([(0, len(self.seg_fwd_remap) - 1)])
+        return posteriors.moment_stats(*[mom[k][0] for k in posteriors.MOMENT_ARRAYS[1:]])['ploidy_posterior_sd']
+
     def _call_states(self, cn):
         """(batch, restart, states (K, N1) in model order, whether cn was one path) of a call `cn` in experiment order
         ((N, M, 2) or (K, N, M, 2)); None: the decoded path."""

@@ -40,12 +40,12 @@ static inline long long now_ns() { return std::chrono::duration_cast<std::chrono
 enum KernelId {
     KID_STATE_TABLES = 0, KID_SEG_CONST, KID_FRAMELOGPROB, KID_FB, KID_MARGINALS, KID_MARGINALS_AB, KID_OUTLIER_TOTAL,
     KID_OUTLIER_ALLELE, KID_ALLELE_SWAP, KID_BRK_LUT, KID_PAIRWISE, KID_BRK_UPDATE, KID_ELBO_SEG, KID_ELBO_FINAL,
-    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_POST_SUMMARY, KID_REGION, KID_REGION_COUNTS, KID_CALL_PROB, KID_COUNT
+    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_POST_SUMMARY, KID_REGION, KID_REGION_COUNTS, KID_CALL_PROB, KID_REGION_MOMENTS, KID_COUNT
 };
 static const char *kKernelNames[KID_COUNT] = {
     "k_state_tables", "k_seg_const", "k_framelogprob", "k_fb", "k_marginals<true>", "k_marginals<false>", "k_update_outlier_total",
     "k_update_outlier_allele", "k_update_allele_swap", "k_brk_lut", "k_pairwise", "k_brk_update", "k_elbo_seg", "k_elbo_final",
-    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn", "k_posterior_summary", "k_region_prob", "k_region_counts", "k_call_prob"};
+    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn", "k_posterior_summary", "k_region_prob", "k_region_counts", "k_call_prob", "k_region_moments"};
 
 struct ProfRec { int id; hipEvent_t a, b; };
 
@@ -3245,6 +3245,46 @@ int rmx_call_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t npaths, const in
                        [&](const Dev &dv, int r, int n, int i, int use_wb, const int32_t *dq, int nqc, double *out, uint32_t *flags) {
         ca.queries = dq; ca.nq = nqc; ca.paths = dpaths + (size_t)i * npaths * N;
         hipLaunchKernelGGL(k_call_prob, dim3((unsigned)((nqc + CLP_WPB - 1) / CLP_WPB), n), dim3(64 * CLP_WPB), lds, b->stream, dv, r, use_wb, ca, out, flags);
+    });
+}
+
+// Region moments (k_region_moments): the exact mean and covariance, under the structured posterior, of up to four weighted
+// sums of state features over a run of segments; it complements rmx_posterior_summary (per-segment means and SDs, which do
+// not combine over correlated neighbours) and rmx_sample_cn (the same numbers to 1 / sqrt(samples)).  The feature and weight
+// tables are checked here (finite; the kernel indexes them with the queries' fields 2 and 3) and staged as doubles at the
+// start of the shared table buffer; the rest is run_queries'.  One workgroup computes a (restart, query) on its own, so a
+// result depends on neither the restart range nor the chunking.
+int rmx_region_moments(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nfeat, const double *features,
+                       int32_t nw, const double *weights, int32_t nf, double *out) { BIND(b);
+    if (!b || r0 < 0 || nr < 1 || (int64_t)r0 + nr > b->R) return fail(RMX_EARG, "bad restart range");
+    if (nq < 1 || !queries || !out) return fail(RMX_EARG, "region_moments: no queries or no output");
+    if (nf < 1 || nf > RGM_MAXF) return fail(RMX_EARG, "region_moments: the number of features of a query must be in [1, 4]");
+    if (nfeat < nf || nw < 1 || !features || !weights) return fail(RMX_EARG, "region_moments: bad feature or weight tables");
+    const Dev &d = b->d;
+    const int N = d.N, S = d.S, C_ = d.C;
+    if (S > RGM_MAXS) return fail(RMX_EUNSUPPORTED, "region_moments: more than 1024 states");
+    const size_t nfe = (size_t)C_ * nfeat * S, nwe = (size_t)nw * N;
+    for (size_t i = 0; i < nfe; i++) if (!std::isfinite(features[i])) return fail(RMX_EARG, "region_moments: a feature is not finite");
+    for (size_t i = 0; i < nwe; i++) if (!std::isfinite(weights[i])) return fail(RMX_EARG, "region_moments: a weight is not finite");
+    int rc;
+    if ((rc = check_queries(b, "region_moments", nq, queries, {0, nfeat - nf + 1, "region_moments: a query needs a first feature in [0, nfeat - nf]"},
+                            {0, nw, "region_moments: weight vector index out of range"}))) return rc;
+    if ((rc = require_snapshot(b, r0, nr, "region_moments"))) return rc;
+    // tables: features, weights (8-byte entries at the start of the buffer)
+    if ((rc = grow(b, &b->d_rgt, &b->rgt_cap, (nfe + nwe) * sizeof(double)))) return rc;
+    HIPCHK(hipMemcpyAsync(b->d_rgt, features, nfe * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemcpyAsync(b->d_rgt + nfe * sizeof(double), weights, nwe * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    const size_t lds = rgm_lds_bytes(S);
+    const int tiles = (S + 15) / 16, tpw = tiles <= 3 * RGM_NW ? 3 : (tiles <= 8 * RGM_NW ? 8 : 16);      // row tiles of 16 states per wave
+    auto kf = tpw == 3 ? k_region_moments<3> : (tpw == 8 ? k_region_moments<8> : k_region_moments<16>);
+    if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    RgmArgs ra;
+    ra.features = (const double *)b->d_rgt; ra.weights = (const double *)b->d_rgt + nfe;
+    ra.nfeat = nfeat; ra.nf = nf; ra.pad_ = 0;
+    return run_queries(b, r0, nr, nq, queries, nf + nf * (nf + 1) / 2, KID_REGION_MOMENTS, "region_moments: a backward step has a zero or non-finite normaliser, or an output is not finite", out,
+                       [&](const Dev &dv, int r, int n, int, int use_wb, const int32_t *dq, int nqc, double *o, uint32_t *flags) {
+        ra.queries = dq; ra.nq = nqc;
+        hipLaunchKernelGGL(kf, dim3((unsigned)nqc, n), dim3(RGM_NT), lds, b->stream, dv, r, use_wb, ra, o, flags);
     });
 }
 

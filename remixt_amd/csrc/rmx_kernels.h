@@ -6020,3 +6020,271 @@ __global__ __launch_bounds__(64 * CLP_WPB) void k_call_prob(Dev d, int r0, int u
         out[(size_t)ri * q.nq + qi] = nm < 0 ? __builtin_nan("") : logp;
     }
 }
+
+// =============================================================================
+// Region moments: for a query (a, b, f0, wi) over the model segments [a, b] of one chain, nf <= 4 features phi_f (a double per
+// (state class, state); features f0 .. f0 + nf - 1 of the table) and the weight vector w (row wi of the table, a double per
+// model segment), with F_f = sum_{n in [a, b]} w_n phi_f(c_n): E[F_f] for every f and Cov(F_f, F_g) for every f <= g under the
+// structured posterior of the last update_p_cn.  It is k_region_counts' backward walk with moment columns in place of count
+// bins, as a centred second-order expectation recursion: with phibar_n,f = sum_s post_n(s) phi_f(s) / sum_s post_n(s) under
+// the class table of n and phit_n,f(s) = phi_f(s) - phibar_n,f,
+//   mean_f = sum_n w_n phibar_n,f,
+//   G1_b,f(s) = w_b phit_b,f(s) post_b(s),   G2_b,fg(s) = w_b^2 phit_b,f(s) phit_b,g(s) post_b(s),
+//   X(s) = fa_n(s) sum_s' W_n(s, s') G_n+1(s') / D_n(s')   (every column),
+//   G1_n,f(s) = X1_f(s) + w_n phit_n,f(s) post_n(s),
+//   G2_n,fg(s) = X2_fg(s) + w_n (phit_n,f(s) X1_g(s) + phit_n,g(s) X1_f(s)) + w_n^2 phit_n,f(s) phit_n,g(s) post_n(s),
+// and Cov(F_f, F_g) = sum_s G2_a,fg(s): the covariance is accumulated, never a difference of raw moments, and G is bounded
+// by B_f = sum_n |w_n| max |phi_f| (by B_f B_g), so nothing is rescaled.  Nothing of the model is written.
+// One workgroup of 256 threads per (restart, query).  G lives in LDS as [S rounded up to 16][16 columns]: the nf columns G1,
+// then the nf (nf + 1) / 2 columns G2 in row-major order of the upper triangle; the other columns stay 0.  A step is
+//   1. the states s' with mass, fa_n+1(s') != 0 or post_n+1(s') != 0 (G_n+1(s') is 0 elsewhere by the selects below),
+//      compacted in state order by a ballot.  The set does not depend on the features, so a column's sums have one order
+//      whatever the other columns of its query are: an nf = 1 query reproduces the matching entries of an nf = 4 query;
+//   2. phibar_n (a block sum per feature in a fixed order) and D(s') as in k_region_counts; a column with G(s') != 0 is
+//      divided by D(s') in place, a column that is 0 is left alone;
+//   3. X on v_mfma_f64_16x16x4_f64 in row tiles of 16 states, the tiles round robin over the four waves, one instruction per
+//      (tile, four s'): A[i = lane & 15][k = lane >> 4] = W(s0 + i, s'_k), B[k][j = lane & 15] = G(s'_k, j) / D(s'_k), D row
+//      (lane >> 4) + 4 reg, column lane & 15;
+//   4. the epilogue through LDS: X goes from the accumulators to G once every wave has finished reading G_n+1 / D, and a
+//      second pass turns every row into G_n in place -- the lane of column (f, g) reads X1_f and X1_g of its row beside its own
+//      X2.  A term with fa(s) == 0 or post(s) == 0 is selected to 0, not multiplied.
+// Every sum has one order, fixed by S and nf alone: a (restart, query) result does not depend on the launch.  Only columns
+// s < S of fa / post are read (clamped address and select).  A D(s') that is 0 or not finite under G(s') != 0, or an output
+// that is not finite, sets RGN_ERR_DENOM in flags[r] and gives NaN in every output of the query.
+// grid (queries, restarts), block RGM_NT, dynamic LDS rgm_lds_bytes(S); out[(ri * nq + query) * per + j], per = nf + nf (nf + 1) / 2:
+// the means, then the covariances.
+// =============================================================================
+#define RGM_NT 256
+#define RGM_NW (RGM_NT / 64)
+#define RGM_KB 16             // columns of the LDS rows and of the matrix instruction's B operand
+#define RGM_MAXF 4
+#define RGM_MAXS 1024
+struct RgmArgs {
+    const int32_t *queries;   // [nq][4]: a, b, first feature, weight vector
+    const double *features;   // [C][nfeat][S]
+    const double *weights;    // [nw][N]
+    int nq, nfeat, nf, pad_;
+};
+static inline size_t rgm_lds_bytes(int S) { const size_t SR = ((size_t)S + 15) & ~(size_t)15; return SR * (RGM_KB * 8 + 8 + 8 + 2); }
+__device__ inline double rgm_pick(double v0, double v1, double v2, double v3, int i) { return i == 0 ? v0 : (i == 1 ? v1 : (i == 2 ? v2 : v3)); }
+// post_n and fa_n of segment n to LDS (0 past S), and phibar_n,f for f < nf: block sums in a fixed order; the barriers also
+// publish the two rows (and end the reads of what they replace: the caller has a barrier before the call)
+__device__ inline void rgm_segment(const Dev &d, int r, int n, int nf, const double *ph, double *fas, double *pst, double (*red)[RGM_MAXF + 1],
+                                   double &m0, double &m1, double &m2, double &m3) {
+    const int S = d.S, SR = (S + 15) & ~15, tid = threadIdx.x;
+    const double *fa = d.fa + rs_off(d, r, n), *post = d.post + rs_off(d, r, n);
+    double v[RGM_MAXF + 1] = {0., 0., 0., 0., 0.};
+    for (int s = tid; s < SR; s += RGM_NT) {
+        const int sc = s < S ? s : S - 1;
+        const double fv = fa[sc], pr = post[sc];
+        const double pv = s < S ? pr : 0.;
+        fas[s] = s < S ? fv : 0.;
+        pst[s] = pv;
+        v[0] += pv;
+#pragma unroll
+        for (int f = 0; f < RGM_MAXF; f++) if (f < nf) v[f + 1] = fma(pv, ph[(size_t)f * S + sc], v[f + 1]);
+    }
+#pragma unroll
+    for (int k = 0; k <= RGM_MAXF; k++) v[k] = group_sum(v[k], 64);
+    __syncthreads();
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k <= RGM_MAXF; k++) red[tid >> 6][k] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k <= RGM_MAXF; k++) {
+        double t = 0.;
+#pragma unroll
+        for (int i = 0; i < RGM_NW; i++) t += red[i][k];
+        v[k] = t;
+    }
+    m0 = v[1] / v[0]; m1 = v[2] / v[0]; m2 = v[3] / v[0]; m3 = v[4] / v[0];
+}
+template <int TPW>
+__global__ __launch_bounds__(RGM_NT) void k_region_moments(Dev d, int r0, int use_wb, RgmArgs q, double *out, uint32_t *flags) {
+    extern __shared__ double rgm_lds[];                 // G [SR][16], fas [SR], pst [SR], idx [SR] (int16)
+    __shared__ double red[RGM_NW][RGM_MAXF + 1], redc[RGM_NW][RGM_KB];
+    __shared__ int nact, s_bad;
+    const int qi = blockIdx.x, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (uniform, and known to be: the matrix instructions sit under conditions on it)
+    const int grp = tid / RGN_GL, gl = tid % RGN_GL;
+    const int ai = lane & 15, kk = lane >> 4;
+    const int S = d.S, SR = (S + 15) & ~15;
+    double *G = rgm_lds, *fas = G + (size_t)SR * RGM_KB, *pst = fas + SR;
+    int16_t *idx = (int16_t *)(pst + SR);
+    const int a = q.queries[4 * qi], b = q.queries[4 * qi + 1], f0 = q.queries[4 * qi + 2], wi = q.queries[4 * qi + 3];
+    const int nf = q.nf, ncol = nf + nf * (nf + 1) / 2;
+    const double *wt = q.weights + (size_t)wi * d.N;
+    // the lane's column ai: G1 of feature cf (ai < nf), G2 of the pair cf <= cg (ai < ncol), or unused
+    int cf = ai < nf ? ai : 0, cg = cf;
+    {
+        int t = ai - nf;
+        bool done = t < 0 || ai >= ncol;
+#pragma unroll
+        for (int f = 0; f < RGM_MAXF; f++) {
+            if (!done && t < nf - f) { cf = f; cg = f + t; done = true; }
+            if (!done) t -= nf - f;
+        }
+    }
+    const bool c1 = ai < nf, c2 = ai >= nf && ai < ncol;
+    if (tid == 0) s_bad = 0;
+    double mean0 = 0., mean1 = 0., mean2 = 0., mean3 = 0.;
+    double pb0, pb1, pb2, pb3;
+    // ---- start: G_b ------------------------------------------------------------------------------------------
+    {
+        const double *ph = q.features + ((size_t)d.seg_class[b] * q.nfeat + f0) * S;
+        rgm_segment(d, r, b, nf, ph, fas, pst, red, pb0, pb1, pb2, pb3);
+        const double w = wt[b];
+        mean0 = w * pb0; mean1 = w * pb1; mean2 = w * pb2; mean3 = w * pb3;
+        const double bf = rgm_pick(pb0, pb1, pb2, pb3, cf), bg = rgm_pick(pb0, pb1, pb2, pb3, cg);
+        for (int e = tid; e < SR * RGM_KB; e += RGM_NT) {         // (column e % 16 == ai)
+            const int s = e / RGM_KB, sc = s < S ? s : S - 1;
+            const double pv = pst[s];
+            const double tf = ph[(size_t)cf * S + sc] - bf, tg = ph[(size_t)cg * S + sc] - bg;
+            double v = 0.;
+            if (pv != 0.) {
+                if (c1) v = w * tf * pv;
+                else if (c2) v = w * w * tf * tg * pv;
+            }
+            G[e] = v;
+        }
+    }
+    for (int n = b - 1; n >= a; n--) {
+        const int tc = d.tclass[n], bs = d.brk_slot[n];      // (tc >= 0: the host checked that the run lies in one chain)
+        const bool wb = bs < 0 && use_wb;
+        const double *Wt = d.Wb + (size_t)tc * S * S;
+        const double *pd = bs >= 0 ? d.pd_lt + ((size_t)r * d.NBE + bs) * d.M * d.D : nullptr;
+        const double *ph = q.features + ((size_t)d.seg_class[n] * q.nfeat + f0) * S;
+        const double w = wt[n];
+        // ---- 1. the states s' with mass, in state order (fas / pst still hold segment n + 1) --------------------
+        __syncthreads();      // (G, fas and pst of the step before, or of the start, are complete)
+        if (tid < 64) {
+            int cnt = 0;
+            for (int base = 0; base < S; base += 64) {
+                const int s = base + lane;
+                const bool act = s < S && (fas[s] != 0. || pst[s] != 0.);
+                const unsigned long long m = __ballot(act);
+                if (act) idx[cnt + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = (int16_t)s;
+                cnt += __builtin_popcountll(m);
+            }
+            if (lane == 0) nact = cnt;
+        }
+        __syncthreads();
+        const int na = __builtin_amdgcn_readfirstlane(nact);
+        // ---- 2. phibar_n, D(s') and G / D in place ---------------------------------------------------------------
+        rgm_segment(d, r, n, nf, ph, fas, pst, red, pb0, pb1, pb2, pb3);
+        mean0 = fma(w, pb0, mean0); mean1 = fma(w, pb1, mean1); mean2 = fma(w, pb2, mean2); mean3 = fma(w, pb3, mean3);
+        if (wb) {
+            for (int j0 = 0; j0 < na; j0 += RGM_NT / RGN_GL) {
+                const int j = j0 + grp;
+                const bool ok = j < na;
+                const int sp = ok ? idx[j] : 0;
+                double p = 0.;
+                if (ok) {
+                    const double *wr = Wt + (size_t)sp * S;
+                    for (int s = gl; s < S; s += RGN_GL) p = fma(fas[s], wr[s], p);
+                }
+                const double D = group_sum(p, RGN_GL);
+                if (ok) {
+                    const double gv = G[sp * RGM_KB + gl];
+                    if (gv != 0.) {
+                        if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                        G[sp * RGM_KB + gl] = gv / D;
+                    }
+                }
+            }
+        } else {
+            for (int j = tid; j < na; j += RGM_NT) {
+                const int sp = idx[j];
+                double D = 0.;
+                for (int s = 0; s < S; s++) {
+                    const double f = fas[s];
+                    if (f != 0.) D = fma(f, exp(trans_value(d, n, s, sp, pd)), D);
+                }
+                for (int k = 0; k < ncol; k++) {
+                    const double gv = G[sp * RGM_KB + k];
+                    if (gv != 0.) {
+                        if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                        G[sp * RGM_KB + k] = gv / D;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        // ---- 3. X on the matrix cores ----------------------------------------------------------------------------
+        psm_d4 acc[TPW];
+#pragma unroll
+        for (int u = 0; u < TPW; u++) acc[u] = psm_d4{0., 0., 0., 0.};
+        for (int j0 = 0; j0 < na; j0 += 4) {
+            const int j = j0 + kk;
+            const bool ok = j < na;
+            const int sp = idx[ok ? j : 0];
+            const double hv = G[sp * RGM_KB + ai];
+            const double bv = ok ? hv : 0.;
+#pragma unroll
+            for (int u = 0; u < TPW; u++) {
+                const int s0 = (wave + RGM_NW * u) * 16;
+                if (s0 < S) {         // (uniform over the wave)
+                    const int s = s0 + ai, sc = s < S ? s : S - 1;
+                    const bool live = ok && s < S;
+                    double wv;
+                    if (wb) wv = Wt[(size_t)sp * S + sc];
+                    else wv = live ? exp(trans_value(d, n, sc, sp, pd)) : 0.;
+                    acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(live ? wv : 0., bv, acc[u], 0, 0, 0);
+                }
+            }
+        }
+        // ---- 4. X to LDS once every wave has finished reading G / D, then G_n in place -------------------------------
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < TPW; u++) {
+            const int s0 = (wave + RGM_NW * u) * 16;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int s = s0 + kk + 4 * g;
+                if (s < SR) {
+                    const double fv = fas[s];
+                    G[s * RGM_KB + ai] = fv != 0. ? fv * acc[u][g] : 0.;
+                }
+            }
+        }
+        __syncthreads();
+        // (a row's 16 columns belong to 16 lanes of one wave in one round: the row's X1 columns are read before any lane of the
+        // wave writes the row)
+        const double bf = rgm_pick(pb0, pb1, pb2, pb3, cf), bg = rgm_pick(pb0, pb1, pb2, pb3, cg);
+#pragma unroll 1
+        for (int e = tid; e < SR * RGM_KB; e += RGM_NT) {         // (column e % 16 == ai)
+            const int s = e / RGM_KB, sc = s < S ? s : S - 1;
+            const double x = G[e], x1f = G[s * RGM_KB + cf], x1g = G[s * RGM_KB + cg];
+            const double pv = pst[s];
+            const double tf = ph[(size_t)cf * S + sc] - bf, tg = ph[(size_t)cg * S + sc] - bg;
+            double v = 0.;
+            if (c1) v = x + (pv != 0. ? w * tf * pv : 0.);
+            else if (c2) v = x + w * (tf * x1g + tg * x1f) + (pv != 0. ? w * w * tf * tg * pv : 0.);
+            G[e] = v;
+        }
+    }
+    // ---- Cov = sum_s G2_a(s): 16 lanes of a quarter-wave take the columns, rows stride RGM_NT / 16 --------------------
+    __syncthreads();
+    {
+        double p = 0.;
+        for (int s = tid >> 4; s < S; s += RGM_NT / 16) p += G[s * RGM_KB + (tid & 15)];
+        p += __shfl_xor(p, 16, 64);
+        p += __shfl_xor(p, 32, 64);
+        if (lane < RGM_KB) redc[wave][lane] = p;
+        __syncthreads();
+        double v = 0.;
+        if (tid < ncol) {
+            double t = 0.;
+#pragma unroll
+            for (int i = 0; i < RGM_NW; i++) t += redc[i][tid];
+            v = tid < nf ? rgm_pick(mean0, mean1, mean2, mean3, tid) : t;
+            if (!(v - v == 0.)) s_bad = 1;
+        }
+        __syncthreads();
+        const bool failed = s_bad != 0;
+        if (tid < ncol) out[((size_t)ri * q.nq + qi) * ncol + tid] = failed ? __builtin_nan("") : v;
+        if (tid == 0 && failed) atomicOr(&flags[r], RGN_ERR_DENOM);
+    }
+}

@@ -41,6 +41,12 @@ cn_region_change_bins = 0
 # the region), p_call_unphased (up to a swap of the alleles) and p_call_total (the per-clone totals) -- and the stat
 # cn_logprob, log q of the whole `cn`, to every fit result (remixt_amd/posteriors.py)
 cn_call_confidence = False
+# (no reference counterpart) with cn_regions: the exact posterior mean and covariance of copy number over regions.  False =
+# none (results unchanged); True adds `region_cn_moments` -- names, length, total_cn_mean / total_cn_cov (the length-weighted
+# mean copy number of each clone over the region and its covariance matrix) and fraction_mean / fraction_cov (the length
+# fractions of posteriors.MOMENT_FRACTIONS) -- and the stats ploidy_posterior_sd and proportion_divergent_posterior_sd to
+# every fit result (remixt_amd/posteriors.py)
+cn_region_moments = False
 
 
 def get_param(config, name):

@@ -367,12 +367,14 @@ def add_region_change_counts(res, names, bins, counts):
     return res
 
 
-def check_region_options(cn_regions, change_bins, call_confidence):
+def check_region_options(cn_regions, change_bins, call_confidence, region_moments=False):
     """The outputs that are computed over regions need cn_regions: checked before a fit, not after it."""
     if change_bins and cn_regions is None:
         raise ValueError('cn_region_change_bins needs cn_regions')
     if call_confidence and cn_regions is None:
         raise ValueError('cn_call_confidence needs cn_regions')
+    if region_moments and cn_regions is None:
+        raise ValueError('cn_region_moments needs cn_regions')
 
 
 def change_bins(config):
@@ -456,4 +458,133 @@ def call_confidence_on(config):
     from . import defaults
     on = bool(defaults.get_param(config, 'cn_call_confidence'))
     check_region_options(defaults.get_param(config, 'cn_regions'), 0, on)
+    return on
+
+
+# ---- mean and covariance of copy number over regions (rmx_region_moments) -------------------------------
+# the fraction features of region_cn_moments: columns of feature_matrix, length-weighted and divided by the region's length
+MOMENT_FRACTIONS = ('alleles_subclonal', 'subclonal', 'loh', 'hdel')
+MOMENT_ARRAYS = ('length', 'total_cn_mean', 'total_cn_cov', 'fraction_mean', 'fraction_cov')
+MOMENT_STATS = ('ploidy_posterior_sd', 'proportion_divergent_posterior_sd')
+
+
+def moment_features(cn_classes):
+    """Feature tables of the region moments, (C, M + 4, S) float64: each clone's total copy number (M rows), then the rows
+    of MOMENT_FRACTIONS -- the columns of the same names of feature_matrix."""
+    weights, layout = feature_matrix(cn_classes)
+    cols = list(range(layout['tot'].start, layout['tot'].stop)) + [layout[k] for k in MOMENT_FRACTIONS]
+    return np.ascontiguousarray(weights[:, :, cols].transpose(0, 2, 1))
+
+
+def moment_shapes(num_regions, M):
+    """The shapes of MOMENT_ARRAYS for `num_regions` regions and M clones."""
+    nfr = len(MOMENT_FRACTIONS)
+    return {'length': (num_regions,), 'total_cn_mean': (num_regions, M), 'total_cn_cov': (num_regions, M, M),
+            'fraction_mean': (num_regions, nfr), 'fraction_cov': (num_regions, nfr, nfr)}
+
+
+def combine_moments(out, piece_region, num_regions):
+    """Moments of every region from its pieces': out (..., pieces, per) -> (..., num_regions, per).  The pieces of a region
+    are split at chain ends, and chains are independent under the structured posterior, so both the means and the
+    covariances of the pieces' sums add.  A region without pieces has all moments 0."""
+    out = np.asarray(out, dtype=float)
+    res = np.zeros(out.shape[:-2] + (int(num_regions), out.shape[-1]))
+    np.add.at(res, (Ellipsis, np.asarray(piece_region), slice(None)), out)
+    return res
+
+
+def _moment_matrices(flat, nf):
+    """(..., nf + nf (nf + 1) / 2): the means, then the upper triangle in row-major order -> (mean (..., nf), cov (..., nf, nf)
+    symmetric by construction: both halves hold the same number)."""
+    flat = np.asarray(flat)
+    iu = np.triu_indices(nf)
+    cov = np.zeros(flat.shape[:-1] + (nf, nf))
+    cov[..., iu[0], iu[1]] = flat[..., nf:]
+    cov[..., iu[1], iu[0]] = flat[..., nf:]
+    return flat[..., :nf].copy(), cov
+
+
+def batch_region_cn_moments(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, l1):
+    """The exact posterior mean and covariance matrix of the length-weighted mean copy number of regions, and of the
+    length fractions of MOMENT_FRACTIONS, for restarts r0 .. r0+nr-1 of a RemixtBatch: a dict of `length` (R,) -- the
+    summed segment lengths L of each region --, `total_cn_mean` (nr, R, M) and `total_cn_cov` (nr, R, M, M) of
+    sum_n l_n tot_m(c_n) / L over the region's segments, and `fraction_mean` (nr, R, 4) and `fraction_cov` (nr, R, 4, 4) of
+    sum_n l_n phi(c_n) / L for phi in MOMENT_FRACTIONS (alleles_subclonal counts 0, 1 or 2 alleles; the others are
+    indicators, so their entries are the fraction of the region's length in that state).  l1: the model-order segment
+    lengths, 0 at inserted segments, which therefore do not count.  regions: (first, last) experiment segment indices; a
+    region that spans chain ends is the sum over its chains, which are independent.  A region of length 0 gives NaN.
+    Two queries per region piece -- the M totals and the four fractions -- in one device call when M == 4, in one call
+    per group otherwise (a call has one number of features per query)."""
+    feats = moment_features(batch.cn_classes)
+    M, nfr = feats.shape[1] - len(MOMENT_FRACTIONS), len(MOMENT_FRACTIONS)
+    if M > 4:
+        raise NotImplementedError('region moments take at most 4 features per query: more than 4 clones are not supported')
+    cs, ce = chains_from_telomeres(is_telomere)
+    runs, piece_region, _ = region_queries(regions, seg_fwd_remap, seg_is_original, cs, ce)
+    P, R = len(runs), len(np.asarray(regions).reshape(-1, 2))
+    w = np.asarray(l1, dtype=float).reshape(1, -1)
+    shapes = moment_shapes(R, M)
+    if P == 0:
+        return dict((k, np.zeros(shapes[k] if k == 'length' else (nr,) + shapes[k])) for k in MOMENT_ARRAYS)
+    csum = np.concatenate([[0.], np.cumsum(w[0])])
+    length = np.zeros(R)
+    np.add.at(length, piece_region, csum[runs[:, 1] + 1] - csum[runs[:, 0]])
+    q = np.zeros((2, P, 4), dtype=np.int32)
+    q[:, :, :2] = runs[None]
+    q[1, :, 2] = M
+    if M == nfr:
+        both = batch.region_moments_raw(r0, nr, q.reshape(-1, 4), feats, w, nfr).reshape(nr, 2, P, -1)
+        tot, frac = both[:, 0], both[:, 1]
+    else:
+        tot = batch.region_moments_raw(r0, nr, q[0], feats, w, M)
+        frac = batch.region_moments_raw(r0, nr, q[1], feats, w, nfr)
+    out = {'length': length}
+    with np.errstate(invalid='ignore', divide='ignore'):
+        for name, flat, nf in (('total_cn', tot, M), ('fraction', frac, nfr)):
+            mean, cov = _moment_matrices(combine_moments(flat, piece_region, R), nf)
+            out[name + '_mean'] = np.where(length[None, :, None] > 0, mean / length[None, :, None], np.nan)
+            out[name + '_cov'] = np.where(length[None, :, None, None] > 0, cov / (length * length)[None, :, None, None], np.nan)
+    return out
+
+
+def moment_stats(total_cn_mean, total_cn_cov, fraction_mean, fraction_cov):
+    """The posterior SDs of the two whole-genome statistics of summary_stats from the moments of the whole-genome region
+    (total_cn_mean (M,), total_cn_cov (M, M), fraction_mean (4,), fraction_cov (4, 4)), with its conventions: ploidy is the
+    sum of the tumour clones' mean totals over M - 1, proportion_divergent the expected alleles_subclonal over 2."""
+    cov = np.asarray(total_cn_cov, dtype=float)
+    M = cov.shape[-1]
+    ploidy_var = cov[1:, 1:].sum() / float((M - 1) ** 2)
+    prop_var = np.asarray(fraction_cov, dtype=float)[0, 0] / 4.
+    return {'ploidy_posterior_sd': float(np.sqrt(np.maximum(ploidy_var, 0.))), 'proportion_divergent_posterior_sd': float(np.sqrt(np.maximum(prop_var, 0.)))}
+
+
+def genome_region(regions, num_segments):
+    """`regions` with the whole-genome region (0, num_segments - 1) appended: the moments of a fit's regions and of the two
+    whole-genome SDs come from one call."""
+    reg = np.asarray(regions, dtype=np.int64).reshape(-1, 2)
+    return np.concatenate([reg, [[0, int(num_segments) - 1]]], axis=0)
+
+
+def add_region_cn_moments(res, names, moments, stats=None):
+    """Fit result dict `res` gains `region_cn_moments`: the region names and the arrays of MOMENT_ARRAYS, one entry per
+    name.  moments: those arrays for the named regions, followed (stats None) by the whole-genome region, from which
+    stats['ploidy_posterior_sd'] and stats['proportion_divergent_posterior_sd'] are taken; or (stats: the two values) for the
+    named regions alone."""
+    n = len(names)
+    out = {'names': list(names)}
+    for k in MOMENT_ARRAYS:
+        out[k] = np.asarray(moments[k])[:n].copy()
+    res['region_cn_moments'] = out
+    if stats is None:
+        stats = moment_stats(*[np.asarray(moments[k])[n] for k in MOMENT_ARRAYS[1:]])
+        stats = [stats[k] for k in MOMENT_STATS]
+    res['stats'].update((k, float(v)) for k, v in zip(MOMENT_STATS, stats))
+    return res
+
+
+def region_moments_on(config):
+    """Config value cn_region_moments, checked: it needs cn_regions."""
+    from . import defaults
+    on = bool(defaults.get_param(config, 'cn_region_moments'))
+    check_region_options(defaults.get_param(config, 'cn_regions'), 0, False, on)
     return on

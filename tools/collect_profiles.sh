@@ -57,4 +57,5 @@ python3 $ROOT/tools/gantt.py $(find $OUT/prof_g -name "g_kernel_trace.csv" | hea
 rm -rf $OUT/prof_g
 { python3 $ROOT/tools/decode_time.py 8; python3 $ROOT/tools/decode_time.py 8 2; python3 $ROOT/tools/decode_time.py 12; } 2>&1 | grep "rep \|k_viterbi\|k_backtrace\|results()\|collect_fit" > $OUT/decode_time.txt
 { RST=8 python3 $ROOT/tools/mstep_marks.py; } 2>&1 | grep -v amdgpu.ids > $OUT/mstep_stage_times_share.txt
+python3 $ROOT/tools/region_moments_time.py 2>&1 | grep -v amdgpu.ids > $ROOT/profiles/region_moments.txt
 ls -la $OUT

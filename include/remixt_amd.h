@@ -437,6 +437,26 @@ int rmx_call_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t npaths, const in
 int rmx_region_moments(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nfeat, const double *features,
                        int32_t nw, const double *weights, int32_t nf, double *out);
 
+/* Region event extents: where an event of rmx_region_prob begins and ends around an anchor segment.  Query i =
+ * (anchor n0, mask index or -1, label index or -1, 0); with the event E of rmx_region_prob (c_n in the mask at every n with
+ * constrain[n] != 0, equal labels across every adjacency), slot k of a query stands for model segment n = n0 - wl + k:
+ *   logp_out[r][i][k] = log P(E on [min(n, n0), max(n, n0)]),   k = 0 .. wl + wr.
+ * Slot wl is log P(E on [n0, n0]): the logarithm of the masked sum of the anchor's marginal, 0 without a mask or where
+ * constrain[n0] is 0.  A slot whose segment lies outside the anchor's chain or outside [0, N) is -inf (a run cannot pass a
+ * chain end), as is an impossible event -- and a slot to the right of the anchor whose probability lies below the range of a double
+ * (log P under about -750) may come out as -inf as well.  Both halves are survival curves: they do not increase away from the anchor.  The
+ * whole row costs wl + wr steps, against one rmx_region_prob query per slot.  The model is not modified.
+ *   masks, labels, constrain   as rmx_region_prob
+ *   wl, wr    window widths to the left and right of the anchor, >= 0, wl + wr + 1 <= 4096
+ * A (restart, query) slot is bit-identical in any restart range, any batch of queries and any (wl, wr) that covers it.
+ * RMX_EARG, with nothing launched and logp_out untouched: a bad range, nq < 1, an anchor outside [0, N), a mask or label
+ * index out of range, a non-zero fourth field, wl or wr < 0, wl + wr + 1 > 4096.  RMX_EVALUE with the restarts listed: a
+ * restart has had no update_p_cn.  RMX_EASSERT with the restarts listed: a step met a zero or non-finite normaliser under a
+ * non-zero numerator, or a step sum that is not a finite number >= 0 (every slot of that query is NaN).
+ * RMX_EUNSUPPORTED: more than 1024 states. */
+int rmx_region_extent(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
+                      int32_t nlabel, const int16_t *labels, const uint8_t *constrain, int32_t wl, int32_t wr, double *logp_out);
+
 /* -- module-level functions on caller-supplied dense inputs ----------------- */
 /* sum_product (:1213-1246): f [N][S], T [N-1][S][S] -> alphas, betas [N][S] */
 int rmx_sum_product(const double *f, const double *T, double *alphas, double *betas,

@@ -35,6 +35,7 @@ def fit(experiment, init_params, config, device=0, quiet=False, init_id=0):
     bins = posteriors.change_bins(config)      # (a bad combination fails before the fit, not after it)
     call_conf = posteriors.call_confidence_on(config)
     moments = posteriors.region_moments_on(config)
+    extents = posteriors.extents_on(config, len(experiment.x))
     h_init = np.array([
         init_params['h_normal'],
         init_params['h_tumour'] * init_params['mix_frac'],
@@ -80,6 +81,10 @@ def fit(experiment, init_params, config, device=0, quiet=False, init_id=0):
             posteriors.add_call_confidence(res, names, model.call_confidence(regions, res['cn']), model.cn_logprob(res['cn']))
         if moments:
             posteriors.add_region_cn_moments(res, names, model.region_cn_moments(posteriors.genome_region(regions, len(res['cn']))))
+    if extents is not None:
+        names, anchors, events, window = extents
+        one = posteriors.grouped_event_extents(lambda a, ev, w: [model.event_extent(a, ev, w)], anchors, events, window)
+        posteriors.add_event_extents(res, names, one[0])
     return res
 
 
@@ -111,6 +116,7 @@ def fit_restarts(experiment, init_params_by_id, config, device=0, quiet=True, se
     bins = posteriors.change_bins(config)      # (a bad combination fails before the fit, not after it)
     call_conf = posteriors.call_confidence_on(config)
     moments = posteriors.region_moments_on(config)
+    posteriors.extents_on(config, len(experiment.x))
     ids = sorted(init_params_by_id)
     params = [init_params_by_id[i] for i in ids]
     max_cn = defaults.get_param(config, 'max_copy_number')
@@ -123,7 +129,8 @@ def fit_restarts(experiment, init_params_by_id, config, device=0, quiet=True, se
                         **_model_kwargs(experiment, config))
     rs.fit(defaults.get_param(config, 'num_em_iter'), defaults.get_param(config, 'num_update_iter'))
     results = add_optional_outputs(rs, rs.results(), experiment, ids, defaults.get_param(config, 'num_cn_samples'), defaults.get_param(config, 'cn_sample_seed'),
-                                   defaults.get_param(config, 'cn_posterior_summary'), defaults.get_param(config, 'cn_regions'), bins, call_conf, moments)
+                                   defaults.get_param(config, 'cn_posterior_summary'), defaults.get_param(config, 'cn_regions'), bins, call_conf, moments,
+                                   defaults.get_param(config, 'cn_event_extents'), defaults.get_param(config, 'cn_extent_window'))
     out = dict(zip(ids, results))
     rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     return out
@@ -282,6 +289,11 @@ def store_fit_results(store, experiment, fit_results, key_prefix):
         for k in posteriors.MOMENT_ARRAYS:
             v = np.asarray(fit_results['region_cn_moments'][k])
             store[key_prefix + '/region_' + k] = pd.Series(v) if v.ndim == 1 else pd.DataFrame(v.reshape(len(v), -1))
+    if 'event_extents' in fit_results:            # (config cn_event_extents)
+        ext = fit_results['event_extents']
+        store[key_prefix + '/extent_names'] = pd.Series(list(ext['names']))
+        for k in posteriors.EXTENT_ARRAYS:
+            store[key_prefix + '/extent_' + k] = pd.Series(np.asarray(ext[k]))
 
 
 def store_optimal_solution(stats, store, config):

@@ -696,6 +696,24 @@ class RemixtBatch(object):
                                               wt.shape[0], wt.ctypes.data_as(_dp) if wt.size else _dp(), nf, obuf.ctypes.data_as(_dp)))
         return out
 
+    def region_extent_raw(self, r0, nr, queries, masks=None, labels=None, constrain=None, wl=0, wr=0):
+        """log-probabilities (nr, nq, wl + wr + 1) of where an event of region_logprob_raw begins and ends around an anchor,
+        under the structured posterior of the last update_p_cn of restarts r0 .. r0+nr-1 (rmx_region_extent).  queries int
+        (nq, 4): anchor segment n0, mask index or -1, label index or -1, 0; masks, labels and constrain as
+        region_logprob_raw.  Slot k of a query stands for model segment n = n0 - wl + k and holds the log-probability of
+        the event over [min(n, n0), max(n, n0)]: slot wl is the event at the anchor alone, and both halves do not increase
+        away from it.  -inf for a segment outside the anchor's chain (a run cannot pass a chain end) and for an impossible
+        event.  wl, wr >= 0, wl + wr + 1 <= 4096."""
+        r0, nr, wl, wr = int(r0), int(nr), int(wl), int(wr)
+        q, args, _keep = self._region_args(queries, masks, labels, constrain)
+        if not (-2 ** 31 <= wl < 2 ** 31 and -2 ** 31 <= wr < 2 ** 31):
+            raise ValueError('window width out of range')
+        per = max(wl, 0) + max(wr, 0) + 1
+        out = np.zeros((max(nr, 0), q.shape[0], per if per <= 4096 else 1), dtype=np.float64)
+        obuf = out if out.size else np.zeros(1)
+        self._ck(self._lib.rmx_region_extent(self._handle, r0, nr, *args, wl, wr, obuf.ctypes.data_as(_dp)))
+        return out
+
     # -- measurement ------------------------------------------------------------
     def timer_start(self):
         self._ck(self._lib.rmx_timer_start(self._handle))
@@ -930,6 +948,10 @@ class RemixtModel(object):
     def region_moments(self, queries, features, weights, nf):
         """RemixtBatch.region_moments_raw of this model: means and covariances (nq, nf + nf (nf + 1) / 2)."""
         return self._batch.region_moments_raw(self._r, 1, queries, features, weights, nf)[0]
+
+    def region_extent(self, queries, masks=None, labels=None, constrain=None, wl=0, wr=0):
+        """RemixtBatch.region_extent_raw of this model: log-probabilities (nq, wl + wr + 1)."""
+        return self._batch.region_extent_raw(self._r, 1, queries, masks, labels, constrain, wl, wr)[0]
 
     def call_logprob(self, paths, queries, labels=None, constrain=None):
         """RemixtBatch.call_logprob_raw of this model: paths (npaths, N) -> log-probabilities (nq,)."""

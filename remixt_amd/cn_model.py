@@ -777,6 +777,20 @@ class BreakpointModel(object):
                                                  self.is_telomere, self.l1)
         return dict((k, v if k == 'length' else v[0]) for k, v in out.items())
 
+    def event_extent(self, anchors, event, window=64):
+        """Where a copy-number event begins and ends around anchor segments, exactly, under the structured posterior of the
+        last variational update: anchors are experiment segment indices, event a mask name of posteriors.MASK_NAMES ('loh':
+        the LOH run around the anchor), a label name of posteriors.LABEL_NAMES ('state' / 'total': the constant-state /
+        constant-total run around it) or a (mask, label) pair, window the number of model segments walked on each side (an
+        int or a (left, right) pair).  A list with one posteriors.extent_summary dict per anchor: p_event, the survival
+        curves of both ends, the boundary pmfs with their censored mass, and the 5 / 50 / 95 % quantiles of each boundary as
+        experiment segment indices."""
+        from . import posteriors
+        if not hasattr(self.model, 'region_extent'):
+            raise NotImplementedError('kernel module %s has no event extents' % getattr(self._kernel_module(), '__name__', '?'))
+        return posteriors.batch_event_extents(self.model._batch, self.model._r, 1, anchors, event, window, self.seg_fwd_remap,
+                                              self.seg_is_original, self.is_telomere)[0]
+
     def ploidy_posterior_sd(self):
         """The exact posterior SD of the tumour ploidy whose mean is stats['ploidy_posterior_mean']: the whole genome as one
         region of region_cn_moments (posteriors.moment_stats)."""

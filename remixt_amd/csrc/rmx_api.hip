@@ -40,12 +40,12 @@ static inline long long now_ns() { return std::chrono::duration_cast<std::chrono
 enum KernelId {
     KID_STATE_TABLES = 0, KID_SEG_CONST, KID_FRAMELOGPROB, KID_FB, KID_MARGINALS, KID_MARGINALS_AB, KID_OUTLIER_TOTAL,
     KID_OUTLIER_ALLELE, KID_ALLELE_SWAP, KID_BRK_LUT, KID_PAIRWISE, KID_BRK_UPDATE, KID_ELBO_SEG, KID_ELBO_FINAL,
-    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_POST_SUMMARY, KID_REGION, KID_REGION_COUNTS, KID_CALL_PROB, KID_REGION_MOMENTS, KID_COUNT
+    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_POST_SUMMARY, KID_REGION, KID_REGION_COUNTS, KID_CALL_PROB, KID_REGION_MOMENTS, KID_REGION_EXTENT, KID_COUNT
 };
 static const char *kKernelNames[KID_COUNT] = {
     "k_state_tables", "k_seg_const", "k_framelogprob", "k_fb", "k_marginals<true>", "k_marginals<false>", "k_update_outlier_total",
     "k_update_outlier_allele", "k_update_allele_swap", "k_brk_lut", "k_pairwise", "k_brk_update", "k_elbo_seg", "k_elbo_final",
-    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn", "k_posterior_summary", "k_region_prob", "k_region_counts", "k_call_prob", "k_region_moments"};
+    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn", "k_posterior_summary", "k_region_prob", "k_region_counts", "k_call_prob", "k_region_moments", "k_region_extent"};
 
 struct ProfRec { int id; hipEvent_t a, b; };
 
@@ -3285,6 +3285,45 @@ int rmx_region_moments(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const i
                        [&](const Dev &dv, int r, int n, int, int use_wb, const int32_t *dq, int nqc, double *o, uint32_t *flags) {
         ra.queries = dq; ra.nq = nqc;
         hipLaunchKernelGGL(kf, dim3((unsigned)nqc, n), dim3(RGM_NT), lds, b->stream, dv, r, use_wb, ra, o, flags);
+    });
+}
+
+// Region event extents (k_region_extent): for every (restart, query) the curve of rmx_region_prob's event over the nested
+// intervals around an anchor, wl + wr + 1 slots from one walk per direction.  A query names an anchor, not a run, so the checks
+// are its own (the kernel finds the chain ends itself and trusts the anchor and the table indices); tables, staging and
+// chunking are rmx_region_prob's.  One workgroup computes a (restart, query) on its own, and both walks are prefix recursions
+// from the anchor, so a slot depends on neither the restart range, the chunking nor the window.
+int rmx_region_extent(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
+                      int32_t nlabel, const int16_t *labels, const uint8_t *constrain, int32_t wl, int32_t wr, double *logp_out) { BIND(b);
+    if (!b || r0 < 0 || nr < 1 || (int64_t)r0 + nr > b->R) return fail(RMX_EARG, "bad restart range");
+    if (nq < 1 || !queries || !logp_out) return fail(RMX_EARG, "region_extent: no queries or no output");
+    if (nmask < 0 || nlabel < 0 || (nmask > 0 && !masks) || (nlabel > 0 && !labels)) return fail(RMX_EARG, "region_extent: bad mask or label tables");
+    if (wl < 0 || wr < 0 || (int64_t)wl + wr + 1 > RGX_MAXPER) return fail(RMX_EARG, "region_extent: the window needs wl, wr >= 0 and wl + wr + 1 <= 4096");
+    const Dev &d = b->d;
+    const int N = d.N, S = d.S, C_ = d.C;
+    if (S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "region_extent: more than 1024 states");
+    for (int i = 0; i < nq; i++) {
+        const int32_t *qq = queries + 4 * (size_t)i;
+        if (qq[0] < 0 || qq[0] >= N) return fail(RMX_EARG, "region_extent: a query needs an anchor in [0, num_segments)");
+        if (qq[1] < -1 || qq[1] >= nmask) return fail(RMX_EARG, "region_extent: mask index out of range");
+        if (qq[2] < -1 || qq[2] >= nlabel) return fail(RMX_EARG, "region_extent: label index out of range");
+        if (qq[3] != 0) return fail(RMX_EARG, "region_extent: the fourth field of a query must be 0");
+    }
+    int rc;
+    if ((rc = require_snapshot(b, r0, nr, "region_extent"))) return rc;
+    // tables: labels (2-byte entries first), masks, constrain
+    const size_t lab_bytes = (size_t)C_ * nlabel * S * sizeof(int16_t), mask_bytes = (size_t)C_ * nmask * S;
+    if ((rc = grow(b, &b->d_rgt, &b->rgt_cap, lab_bytes + mask_bytes + (constrain ? (size_t)N : 0)))) return rc;
+    if (lab_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt, labels, lab_bytes, hipMemcpyHostToDevice, b->stream));
+    if (mask_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes, masks, mask_bytes, hipMemcpyHostToDevice, b->stream));
+    if (constrain) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes + mask_bytes, constrain, (size_t)N, hipMemcpyHostToDevice, b->stream));
+    RgnArgs ra;
+    ra.labels = (const int16_t *)b->d_rgt; ra.masks = b->d_rgt + lab_bytes; ra.constrain = constrain ? b->d_rgt + lab_bytes + mask_bytes : nullptr;
+    ra.nmask = nmask; ra.nlabel = nlabel; ra.pad_ = 0;
+    return run_queries(b, r0, nr, nq, queries, wl + wr + 1, KID_REGION_EXTENT, "region_extent: a step has a zero or non-finite normaliser", logp_out,
+                       [&](const Dev &dv, int r, int n, int, int use_wb, const int32_t *dq, int nqc, double *out, uint32_t *flags) {
+        ra.queries = dq; ra.nq = nqc;
+        hipLaunchKernelGGL(k_region_extent, dim3((unsigned)nqc, n), dim3(RGN_NT), 0, b->stream, dv, r, use_wb, ra, (int)wl, (int)wr, out, flags);
     });
 }
 

@@ -6288,3 +6288,312 @@ __global__ __launch_bounds__(RGM_NT) void k_region_moments(Dev d, int r0, int us
         if (tid == 0 && failed) atomicOr(&flags[r], RGN_ERR_DENOM);
     }
 }
+
+// =============================================================================
+// Region event extents: for a query (anchor n0, mask, label) and window widths wl, wr, the whole curve
+//   out[k] = log P(E on [min(n, n0), max(n, n0)]),   n = n0 - wl + k,   k = 0 .. wl + wr,
+// of k_region_prob's event E (c_n in the mask's states at every constrained n, equal labels across every adjacency),
+// from one walk per direction instead of one k_region_prob query per interval.  Slots outside the anchor's chain or
+// outside [0, N) are -inf: a run cannot pass a chain end.
+//   left (n < n0): k_region_prob's g recursion started at n0; the step sum is written out at every step.
+//   right (n > n0): U_n(s) = P(E on [n0, n] | c_n = s), U_n0(s) = [s in A_n0]; under the backward kernel q, c_n separates
+//     the earlier segments from c_n+1, so
+//       num(s') = sum_s [label(s) == label(s')] fa_n(s) W_n(s, s') U_n(s),   D_n(s') = sum_s fa_n(s) W_n(s, s'),
+//       U_n+1(s') = [s' in A_n+1] num(s') / D_n(s')   (0 where num is 0),
+//       P(E on [n0, n + 1]) = sum_s' post_n+1(s') U_n+1(s') / sum_s' post_n+1(s').
+//     num and D are sums over the same index with the same weights: one pass over the S x S weights per step (the left walk,
+//     like every other region kernel, takes two).  U is divided after every step by its maximum over the states with mass in
+//     post_n+1 or fa_n+1 (the others are set to 0: they reach neither a later step nor a sum), and the logarithms are added.
+// One workgroup of 256 threads per (restart, query); the left walk runs first, then the right walk, each with the whole
+// workgroup (their lengths differ with the window and the chain ends, so two halves could not share barriers).  The lanes
+// lie along the dimension the weights are contiguous in, as in k_region_prob: on Wb 16 lanes per s' stride s and a fixed
+// butterfly gives num and D together; on exp(trans_value) the thread owns s' and walks s.
+// Every sum has one order, fixed by the state count alone, and both walks are prefix recursions from the anchor: a slot
+// does not depend on the launch, the other queries or the window widths.  Only columns s < S of fa / post are read; a state
+// with fa or post equal to 0 is selected to 0, not multiplied.  A D(s') that is 0 or not finite under a non-zero numerator,
+// or a step sum that is not a finite number >= 0, sets RGN_ERR_DENOM in flags[r] and gives NaN in every slot of the query.
+// grid (queries, restarts), block RGN_NT; out[(ri * nq + query) * (wl + wr + 1) + k].
+// =============================================================================
+#define RGX_MAXPER 4096       // slots of a query: wl + wr + 1
+// max and two sums over the workgroup, the sums in rgn_block_sum's order; every thread gets them
+__device__ inline void rgx_block_max_sum2(double &m, double &a, double &b, double *red) {
+    m = group_max(m, 64); a = group_sum(a, 64); b = group_sum(b, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { const int w = threadIdx.x >> 6; red[w] = m; red[RGN_NT / 64 + w] = a; red[2 * (RGN_NT / 64) + w] = b; }
+    __syncthreads();
+    double tm = red[0], ta = 0., tb = 0.;
+#pragma unroll
+    for (int i = 0; i < RGN_NT / 64; i++) { tm = fmax(tm, red[i]); ta += red[RGN_NT / 64 + i]; tb += red[2 * (RGN_NT / 64) + i]; }
+    m = tm; a = ta; b = tb;
+}
+__global__ __launch_bounds__(RGN_NT) void k_region_extent(Dev d, int r0, int use_wb, RgnArgs q, int wl, int wr, double *out, uint32_t *flags) {
+    __shared__ double g[RGN_MAXS], h[RGN_MAXS], fas[RGN_MAXS];
+    __shared__ double red[3 * (RGN_NT / 64)];
+    __shared__ int16_t lab[2][RGN_MAXS], idx[RGN_MAXS];
+    __shared__ int nact, s_bad;
+    const int qi = blockIdx.x, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x, lane = tid & 63;
+    const int grp = tid / RGN_GL, gl = tid % RGN_GL;
+    const int S = d.S, N = d.N;
+    const int n0 = q.queries[4 * qi], mi = q.queries[4 * qi + 1], li = q.queries[4 * qi + 2];
+    const int per = wl + wr + 1;
+    double *orow = out + ((size_t)ri * q.nq + qi) * per;
+    if (tid == 0) s_bad = 0;
+    bool failed = false;
+    int nleft = 0, nright = 0;       // slots written on either side of slot wl
+    double logp0 = 0.;
+    // ---- the anchor: g_n0 = [mask] post_n0; slot wl ------------------------------------------------------------------
+    {
+        const int cls = d.seg_class[n0];
+        const double *post = d.post + rs_off(d, r, n0);
+        const uint8_t *mk = (mi >= 0 && (!q.constrain || q.constrain[n0])) ? q.masks + ((size_t)cls * q.nmask + mi) * S : nullptr;
+        double part = 0.;
+        for (int s = tid; s < S; s += RGN_NT) {
+            const double v = (!mk || mk[s]) ? post[s] : 0.;
+            g[s] = v; part += v;
+        }
+        const double Z = rgn_block_sum(part, red);
+        if (!(Z >= 0. && Z < INFINITY)) failed = true;
+        else if (Z == 0.) logp0 = -INFINITY;
+        else {
+            logp0 = mk ? log(Z) : 0.;
+            for (int s = tid; s < S; s += RGN_NT) g[s] = g[s] / Z;
+        }
+        if (tid == 0) orow[wl] = logp0;
+    }
+    // ---- left walk: k_region_prob's steps n = n0 - 1, n0 - 2, ... ----------------------------------------------------
+    {
+        int cur = 0;              // lab[cur]: the labels of segment n + 1
+        if (li >= 0) {
+            const int16_t *lb = q.labels + ((size_t)d.seg_class[n0] * q.nlabel + li) * S;
+            for (int s = tid; s < S; s += RGN_NT) lab[cur][s] = lb[s];
+        }
+        double logp = logp0;
+        for (int n = n0 - 1; n >= n0 - wl && n >= 0 && d.tclass[n] >= 0 && !failed && logp > -INFINITY; n--) {
+            const int tc = d.tclass[n], bs = d.brk_slot[n];
+            const int cls = d.seg_class[n];
+            const double *fa = d.fa + rs_off(d, r, n);
+            const uint8_t *mk = (mi >= 0 && (!q.constrain || q.constrain[n])) ? q.masks + ((size_t)cls * q.nmask + mi) * S : nullptr;
+            const int16_t *lb = li >= 0 ? q.labels + ((size_t)cls * q.nlabel + li) * S : nullptr;
+            const int16_t *lab1 = lab[cur];
+            int16_t *lab0 = lab[cur ^ 1];
+            for (int s = tid; s < S; s += RGN_NT) {
+                fas[s] = fa[s];
+                if (lb) lab0[s] = lb[s];
+            }
+            __syncthreads();
+            if (bs < 0 && use_wb) {
+                const double *Wt = d.Wb + (size_t)tc * S * S;
+                // the states s' with g(s') > 0, in state order
+                if (tid < 64) {
+                    int cnt = 0;
+                    for (int base = 0; base < S; base += 64) {
+                        const int s = base + lane;
+                        const bool act = s < S && g[s] > 0.;
+                        const unsigned long long m = __ballot(act);
+                        if (act) idx[cnt + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = (int16_t)s;
+                        cnt += __builtin_popcountll(m);
+                    }
+                    if (lane == 0) nact = cnt;
+                }
+                __syncthreads();
+                const int na = nact;
+                // D(s') and h(s') = g(s') / D(s'): 16 lanes per s'
+                for (int j0 = 0; j0 < na; j0 += RGN_NT / RGN_GL) {
+                    const int j = j0 + grp;
+                    const bool ok = j < na;
+                    const int sp = ok ? idx[j] : 0;
+                    double p = 0.;
+                    if (ok) {
+                        const double *wrow = Wt + (size_t)sp * S;
+                        for (int s = gl; s < S; s += RGN_GL) p = fma(fas[s], wrow[s], p);
+                    }
+                    const double D = group_sum(p, RGN_GL);
+                    if (ok && gl == 0) {
+                        if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                        h[j] = g[sp] / D;
+                    }
+                }
+                __syncthreads();
+                // g(s): the thread owns s
+                for (int s = tid; s < S; s += RGN_NT) {
+                    double acc = 0.;
+                    if (!mk || mk[s]) {
+                        const int ls = lb ? lab0[s] : 0;
+                        const double *wc = Wt + s;
+#pragma unroll 4
+                        for (int j = 0; j < na; j++) {
+                            const int sp = idx[j];
+                            if (!lb || lab1[sp] == ls) acc = fma(wc[(size_t)sp * S], h[j], acc);
+                        }
+                        acc *= fas[s];
+                    }
+                    g[s] = acc;
+                }
+            } else {
+                const double *pd = bs >= 0 ? d.pd_lt + ((size_t)r * d.NBE + bs) * d.M * d.D : nullptr;
+                // D(s') and h(s'): the thread owns s'
+                for (int sp = tid; sp < S; sp += RGN_NT) {
+                    const double gv = g[sp];
+                    double hv = 0.;
+                    if (gv > 0.) {
+                        double D = 0.;
+                        for (int s = 0; s < S; s++) {
+                            const double f = fas[s];
+                            if (f != 0.) D = fma(f, exp(trans_value(d, n, s, sp, pd)), D);
+                        }
+                        if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                        hv = gv / D;
+                    }
+                    h[sp] = hv;
+                }
+                __syncthreads();
+                // g(s): 16 lanes per s
+                for (int s0 = 0; s0 < S; s0 += RGN_NT / RGN_GL) {
+                    const int s = s0 + grp;
+                    const bool ok = s < S && (!mk || mk[s]) && fas[s] != 0.;
+                    double p = 0.;
+                    if (ok) {
+                        const int ls = lb ? lab0[s] : 0;
+                        for (int sp = gl; sp < S; sp += RGN_GL) {
+                            const double hv = h[sp];
+                            if (hv != 0. && (!lb || lab1[sp] == ls)) p = fma(exp(trans_value(d, n, s, sp, pd)), hv, p);
+                        }
+                    }
+                    const double sum = group_sum(p, RGN_GL);
+                    if (s < S && gl == 0) g[s] = ok ? sum * fas[s] : 0.;
+                }
+            }
+            __syncthreads();
+            double part = 0.;
+            for (int s = tid; s < S; s += RGN_NT) part += g[s];
+            const double Z = rgn_block_sum(part, red);
+            if (s_bad || !(Z >= 0. && Z < INFINITY)) failed = true;
+            else if (Z == 0.) logp = -INFINITY;
+            else {
+                logp += log(Z);
+                for (int s = tid; s < S; s += RGN_NT) g[s] = g[s] / Z;
+            }
+            if (!failed && logp > -INFINITY) {
+                nleft++;
+                if (tid == 0) orow[wl - nleft] = logp;
+            }
+            cur ^= 1;
+        }
+    }
+    // ---- right walk: steps n -> n + 1 for n = n0, n0 + 1, ...; g holds fa_n U_n during a step, h takes U_n+1 ---------------
+    {
+        int cur = 0;              // lab[cur]: the labels of segment n
+        __syncthreads();
+        {
+            const int cls = d.seg_class[n0];
+            const uint8_t *mk = (mi >= 0 && (!q.constrain || q.constrain[n0])) ? q.masks + ((size_t)cls * q.nmask + mi) * S : nullptr;
+            const int16_t *lb = li >= 0 ? q.labels + ((size_t)cls * q.nlabel + li) * S : nullptr;
+            for (int s = tid; s < S; s += RGN_NT) {
+                g[s] = (!mk || mk[s]) ? 1. : 0.;
+                if (lb) lab[cur][s] = lb[s];
+            }
+        }
+        double logp = logp0 > -INFINITY ? 0. : -INFINITY;       // the logarithms of the maxima U was divided by so far
+        for (int n = n0; n < n0 + wr && n + 1 < N && d.tclass[n] >= 0 && !failed && logp > -INFINITY; n++) {
+            const int tc = d.tclass[n], bs = d.brk_slot[n];
+            const int cls1 = d.seg_class[n + 1];
+            const double *fa = d.fa + rs_off(d, r, n);
+            const double *post1 = d.post + rs_off(d, r, n + 1);
+            const uint8_t *mk1 = (mi >= 0 && (!q.constrain || q.constrain[n + 1])) ? q.masks + ((size_t)cls1 * q.nmask + mi) * S : nullptr;
+            const int16_t *lb1 = li >= 0 ? q.labels + ((size_t)cls1 * q.nlabel + li) * S : nullptr;
+            const int16_t *lab0 = lab[cur];
+            int16_t *lab1 = lab[cur ^ 1];
+            __syncthreads();
+            for (int s = tid; s < S; s += RGN_NT) {
+                const double f = fa[s];
+                fas[s] = f;
+                g[s] = f != 0. ? f * g[s] : 0.;
+                if (lb1) lab1[s] = lb1[s];
+            }
+            __syncthreads();
+            if (bs < 0 && use_wb) {
+                const double *Wt = d.Wb + (size_t)tc * S * S;
+                // num(s') and D(s') from one read of row s': 16 lanes per s'
+                for (int j0 = 0; j0 < S; j0 += RGN_NT / RGN_GL) {
+                    const int sp = j0 + grp;
+                    const bool ok = sp < S && (!mk1 || mk1[sp]);
+                    double pD = 0., pN = 0.;
+                    if (ok) {
+                        const double *wrow = Wt + (size_t)sp * S;
+                        const int ls = lb1 ? lab1[sp] : 0;
+                        for (int s = gl; s < S; s += RGN_GL) {
+                            const double w = wrow[s];
+                            pD = fma(fas[s], w, pD);
+                            if (!lb1 || lab0[s] == ls) pN = fma(g[s], w, pN);
+                        }
+                    }
+                    const double D = group_sum(pD, RGN_GL), num = group_sum(pN, RGN_GL);
+                    if (sp < S && gl == 0) {
+                        double u = 0.;
+                        if (ok && num != 0.) {
+                            u = num / D;
+                            if (!(D > 0. && D < INFINITY) || !(u >= 0. && u < INFINITY)) s_bad = 1;
+                        }
+                        h[sp] = u;
+                    }
+                }
+            } else {
+                const double *pd = bs >= 0 ? d.pd_lt + ((size_t)r * d.NBE + bs) * d.M * d.D : nullptr;
+                // num(s') and D(s'): the thread owns s'
+                for (int sp = tid; sp < S; sp += RGN_NT) {
+                    double u = 0.;
+                    if (!mk1 || mk1[sp]) {
+                        const int ls = lb1 ? lab1[sp] : 0;
+                        double D = 0., num = 0.;
+                        for (int s = 0; s < S; s++) {
+                            const double f = fas[s];
+                            if (f != 0.) {
+                                const double w = exp(trans_value(d, n, s, sp, pd));
+                                D = fma(f, w, D);
+                                if (!lb1 || lab0[s] == ls) num = fma(g[s], w, num);
+                            }
+                        }
+                        if (num != 0.) {
+                            u = num / D;
+                            if (!(D > 0. && D < INFINITY) || !(u >= 0. && u < INFINITY)) s_bad = 1;
+                        }
+                    }
+                    h[sp] = u;
+                }
+            }
+            __syncthreads();
+            // the scale is the largest U among the states that can still matter -- mass in the marginal or in the forward row of
+            // n + 1 --: a state without either may keep U near 1 while every path of the event decays
+            const double *fa1 = d.fa + rs_off(d, r, n + 1);
+            double mx = 0., spu = 0., sp1 = 0.;
+            for (int s = tid; s < S; s += RGN_NT) {
+                const double p = post1[s];
+                const bool live = p != 0. || fa1[s] != 0.;
+                const double u = live ? h[s] : 0.;
+                h[s] = u;
+                mx = fmax(mx, u);
+                if (p != 0.) { spu += p * u; sp1 += p; }
+            }
+            rgx_block_max_sum2(mx, spu, sp1, red);
+            const double ratio = spu / sp1;
+            if (s_bad || !(ratio >= 0. && ratio < INFINITY) || !(mx >= 0. && mx < INFINITY)) failed = true;
+            else if (ratio == 0. || mx == 0.) logp = -INFINITY;
+            else {
+                nright++;
+                if (tid == 0) orow[wl + nright] = logp + log(ratio);
+                logp += log(mx);
+                for (int s = tid; s < S; s += RGN_NT) g[s] = h[s] / mx;
+            }
+            cur ^= 1;
+        }
+    }
+    // ---- the slots no step reached (-inf), or NaN in every slot of a failed query ---------------------------------------
+    __syncthreads();
+    if (failed) {
+        for (int k = tid; k < per; k += RGN_NT) orow[k] = __builtin_nan("");
+        if (tid == 0) atomicOr(&flags[r], RGN_ERR_DENOM);
+    } else {
+        for (int k = tid; k < wl - nleft; k += RGN_NT) orow[k] = -INFINITY;
+        for (int k = wl + nright + 1 + tid; k < per; k += RGN_NT) orow[k] = -INFINITY;
+    }
+}

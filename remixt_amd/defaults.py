@@ -47,6 +47,14 @@ cn_call_confidence = False
 # fractions of posteriors.MOMENT_FRACTIONS) -- and the stats ploidy_posterior_sd and proportion_divergent_posterior_sd to
 # every fit result (remixt_amd/posteriors.py)
 cn_region_moments = False
+# where copy-number events begin and end around anchor segments: a list of (name, segment, event) -- segment an
+# experiment segment index, event a mask name of posteriors.MASK_NAMES ('loh': the LOH run around the segment), a label name
+# of posteriors.LABEL_NAMES ('state' / 'total': the constant-state / constant-total run around it) or a (mask, label) pair --
+# adds `event_extents` to every fit result: the probability of the event at the segment and the exact 5 / 50 / 95 % posterior
+# quantiles of where it starts and stops, with a flag where a quantile lies beyond cn_extent_window segments on that side
+# (remixt_amd/posteriors.py).  None: off
+cn_event_extents = None
+cn_extent_window = 64
 
 
 def get_param(config, name):

@@ -588,3 +588,225 @@ def region_moments_on(config):
     on = bool(defaults.get_param(config, 'cn_region_moments'))
     check_region_options(defaults.get_param(config, 'cn_regions'), 0, False, on)
     return on
+
+
+# ---- where a copy-number event begins and ends around an anchor (rmx_region_extent) ---------------------
+EXTENT_QUANTILES = (0.05, 0.5, 0.95)
+EXTENT_ARRAYS = ('p_event', 'left_q05', 'left_q50', 'left_q95', 'right_q05', 'right_q50', 'right_q95', 'left_censored', 'right_censored')
+_EXTENT_MAX_SLOTS = 4096
+
+
+def parse_event(event):
+    """An event by the names of the region tables -> (mask index or -1, label index or -1): a name of MASK_NAMES ('loh': the
+    LOH run around the anchor), a name of LABEL_NAMES ('state', 'total': the constant-state / constant-total run around the
+    anchor), or a pair (mask name or None, label name or None)."""
+    if isinstance(event, str):
+        if event in MASK_NAMES:
+            return MASK_NAMES.index(event), -1
+        if event in LABEL_NAMES:
+            return -1, LABEL_NAMES.index(event)
+        raise ValueError('unknown event %r: a name of %r or of %r, or a pair of both' % (event, MASK_NAMES, LABEL_NAMES))
+    try:
+        mask, label = event
+    except (TypeError, ValueError):
+        raise ValueError('an event is a mask name, a label name or a (mask, label) pair, not %r' % (event,))
+    if (mask is not None and mask not in MASK_NAMES) or (label is not None and label not in LABEL_NAMES):
+        raise ValueError('unknown event %r: a mask of %r and a label of %r' % (event, MASK_NAMES, LABEL_NAMES))
+    return (-1 if mask is None else MASK_NAMES.index(mask)), (-1 if label is None else LABEL_NAMES.index(label))
+
+
+def parse_window(window):
+    """A window as (wl, wr): an int (both sides) or a pair, each >= 0, wl + wr + 1 <= 4096."""
+    if np.ndim(window) == 0:
+        wl = wr = int(window)
+    else:
+        wl, wr = (int(w) for w in window)
+    if wl < 0 or wr < 0 or wl + wr + 1 > _EXTENT_MAX_SLOTS:
+        raise ValueError('a window needs widths >= 0 and at most %d slots' % _EXTENT_MAX_SLOTS)
+    return wl, wr
+
+
+def extent_queries(anchors, event, seg_fwd_remap, seg_is_original):
+    """Anchors (experiment segment indices) and an event (parse_event) as the queries of rmx_region_extent:
+    (queries int32 (A, 4): model segment of the anchor, mask index or -1, label index or -1, 0; constrain uint8 (N1,)).
+    constrain is seg_is_original, as for region_queries: a mask binds only real segments, a label constraint binds every
+    adjacency, the ones through an inserted segment included."""
+    fwd = np.asarray(seg_fwd_remap, dtype=np.int64)
+    anc = np.asarray(anchors, dtype=np.int64).reshape(-1)
+    if len(anc) and (anc.min() < 0 or anc.max() >= len(fwd)):
+        raise ValueError('an anchor needs 0 <= segment < number of segments')
+    mi, li = parse_event(event)
+    q = np.zeros((len(anc), 4), dtype=np.int32)
+    q[:, 0], q[:, 1], q[:, 2] = fwd[anc], mi, li
+    return q, np.ascontiguousarray(np.asarray(seg_is_original) != 0, dtype=np.uint8)
+
+
+def _boundary(seg, surv, more, forward):
+    """One side of extent_summary.  seg: the experiment segments of the side in walking order from the anchor (seg[0]);
+    surv: P(E on the run from the anchor to seg[i]) / P(E at the anchor), 1 at i = 0 and not increasing; more: whether the
+    chain goes on past seg[-1] (what lies there is censored).  -> (pmf of the boundary over seg, or over seg[:-1] with the
+    censored mass when `more`; the quantiles of the boundary in increasing segment order; whether each lies in the censored
+    mass).  The boundary is the last segment of the walk the event still reaches: B = seg[i] has mass surv[i] - surv[i + 1]."""
+    nxt = np.append(surv[1:], 0.)
+    pmf = np.maximum(surv - nxt, 0.)
+    censored_mass = 0.
+    if more:
+        censored_mass, pmf = float(surv[-1]), pmf[:-1]
+    quant, cens = [], []
+    # walking away from the anchor the boundary's distribution function at seg[i] is 1 - surv[i + 1]; a left boundary is
+    # reported in increasing segment order, where the distribution function at seg[i] is surv[i]
+    for qv in EXTENT_QUANTILES:
+        if forward:
+            hit = np.flatnonzero(1. - nxt[:len(pmf)] >= qv)
+            i = int(hit[0]) if len(hit) else len(seg) - 1
+            c = not len(hit)
+        else:
+            hit = np.flatnonzero(surv >= qv)      # the farthest segment still reached with probability >= q
+            i = int(hit[-1])
+            c = bool(more and i == len(seg) - 1)
+        quant.append(int(seg[i])); cens.append(c)
+    return pmf, censored_mass, quant, cens
+
+
+def extent_summary(logp, anchor, wl, wr, seg_fwd_remap, is_telomere):
+    """What one row of rmx_region_extent says about where the event around `anchor` (an experiment segment index) begins and
+    ends.  logp: (wl + wr + 1,) log-probabilities, slot k for model segment seg_fwd_remap[anchor] - wl + k.  A dict of
+      p_event: the probability of the event at the anchor alone, exp(slot wl);
+      right_segments / left_segments: the experiment segments of the window's original segments of the anchor's chain, from
+        the anchor outward (inserted zero-length segments are dropped from the report);
+      right_survival / left_survival: for each of those, the probability that the event reaches it, given the event at the
+        anchor (1 at the anchor, not increasing outward; NaN everywhere if p_event is 0);
+      right_pmf / left_pmf: the joint probability of the event at the anchor and its boundary -- the last segment the event
+        still reaches -- at each segment; where the chain goes on past the window the last segment's entry is left out and
+        right_censored_mass / left_censored_mass carries the mass at it or beyond (0 otherwise): pmf plus censored mass sum
+        to p_event;
+      right_quantiles / left_quantiles: the 5 / 50 / 95 % quantiles of each boundary given the event at the anchor, as
+        experiment segment indices in increasing order (left <= anchor <= right), -1 if p_event is 0; a quantile that falls
+        in the censored mass is the window's end, with right_censored / left_censored (3 bools) True."""
+    logp = np.asarray(logp, dtype=float)
+    fwd = np.asarray(seg_fwd_remap, dtype=np.int64)
+    tel = np.asarray(is_telomere) != 0
+    N1 = len(tel)
+    if logp.shape != (wl + wr + 1,):
+        raise ValueError('logp must have shape (wl + wr + 1,)')
+    rev = np.full(N1, -1, dtype=np.int64)
+    rev[fwd] = np.arange(len(fwd))
+    cs, ce = chains_from_telomeres(tel)
+    n0 = int(fwd[anchor])
+    c = int(np.searchsorted(ce, n0, side='left'))
+    with np.errstate(over='ignore'):
+        p = np.minimum(np.exp(logp), 1.)
+    p0 = float(p[wl])
+    out = {'p_event': p0}
+    for side, forward in (('right', True), ('left', False)):
+        if forward:
+            n = np.arange(n0, min(n0 + wr, int(ce[c])) + 1)
+        else:
+            n = np.arange(n0, max(n0 - wl, int(cs[c])) - 1, -1)
+        n = n[rev[n] >= 0]
+        seg = rev[n]
+        with np.errstate(invalid='ignore', divide='ignore'):
+            surv = np.minimum.accumulate(p[n - n0 + wl]) / p0 if p0 > 0 else np.full(len(n), np.nan)
+        # the chain goes on past the window if another original segment of the chain lies beyond the last one reported
+        beyond = np.arange(n[-1] + 1, int(ce[c]) + 1) if forward else np.arange(int(cs[c]), n[-1])
+        more = bool((rev[beyond] >= 0).any())
+        if p0 > 0:
+            pmf, cm, quant, cens = _boundary(seg, surv, more, forward)
+            pmf, cm = pmf * p0, cm * p0
+        else:
+            pmf, cm, quant, cens = np.zeros(len(seg) - (1 if more else 0)), 0., [-1] * 3, [False] * 3
+        out[side + '_segments'] = seg
+        out[side + '_survival'] = surv
+        out[side + '_pmf'] = pmf
+        out[side + '_censored_mass'] = cm
+        out[side + '_quantiles'] = np.array(quant, dtype=np.int64)
+        out[side + '_censored'] = np.array(cens, dtype=bool)
+    return out
+
+
+def compact_extents(summaries):
+    """The arrays of EXTENT_ARRAYS, each (len(summaries),), from a list of extent_summary dicts: p_event, the six quantiles
+    and, per side, whether any of its quantiles lies in the censored mass."""
+    out = {'p_event': np.array([s['p_event'] for s in summaries], dtype=float)}
+    for side in ('left', 'right'):
+        for i, name in enumerate(('q05', 'q50', 'q95')):
+            out['%s_%s' % (side, name)] = np.array([s[side + '_quantiles'][i] for s in summaries], dtype=np.int64)
+        out[side + '_censored'] = np.array([bool(s[side + '_censored'].any()) for s in summaries], dtype=bool)
+    return out
+
+
+def batch_event_extents(batch, r0, nr, anchors, event, window, seg_fwd_remap, seg_is_original, is_telomere):
+    """extent_summary of every anchor (experiment segment indices) for restarts r0 .. r0+nr-1 of a RemixtBatch from one
+    device call: a list over restarts of lists over anchors.  event: parse_event; window: parse_window."""
+    wl, wr = parse_window(window)
+    q, constrain = extent_queries(anchors, event, seg_fwd_remap, seg_is_original)
+    if len(q) == 0:
+        return [[] for _ in range(nr)]
+    masks, labels = event_tables(batch.cn_classes)
+    logp = batch.region_extent_raw(r0, nr, q, masks, labels, constrain, wl, wr)
+    anc = np.asarray(anchors, dtype=np.int64).reshape(-1)
+    return [[extent_summary(logp[i, j], int(a), wl, wr, seg_fwd_remap, is_telomere) for j, a in enumerate(anc)] for i in range(nr)]
+
+
+def parse_extents(cn_event_extents):
+    """Config value cn_event_extents, a list of (name, segment, event) -> (names, anchors int (A,), events: parse_event's
+    index pairs).  ValueError for a bad entry."""
+    names, anchors, events = [], [], []
+    for entry in cn_event_extents:
+        try:
+            name, seg, event = entry
+        except (TypeError, ValueError):
+            raise ValueError('cn_event_extents: an entry is (name, segment, event), not %r' % (entry,))
+        if int(seg) != seg or int(seg) < 0:
+            raise ValueError('cn_event_extents: the segment of %r must be an index >= 0' % (name,))
+        names.append(str(name)); anchors.append(int(seg)); events.append(parse_event(event))
+    return names, np.array(anchors, dtype=np.int64), events
+
+
+def event_pair(indices):
+    """parse_event's index pair back as a (mask name or None, label name or None) event."""
+    mi, li = indices
+    return (None if mi < 0 else MASK_NAMES[mi], None if li < 0 else LABEL_NAMES[li])
+
+
+def extents_on(config, num_segments=None):
+    """Config values cn_event_extents / cn_extent_window, checked before any fit: None (off), or (names, anchors, events,
+    (wl, wr)).  num_segments: the experiment's number of segments, where known."""
+    from . import defaults
+    ext = defaults.get_param(config, 'cn_event_extents')
+    if ext is None:
+        return None
+    names, anchors, events = parse_extents(ext)
+    window = parse_window(defaults.get_param(config, 'cn_extent_window'))
+    if num_segments is not None and len(anchors) and anchors.max() >= num_segments:
+        raise ValueError('cn_event_extents: a segment is outside the experiment')
+    return names, anchors, events, window
+
+
+def grouped_event_extents(extent_fn, anchors, events, window):
+    """The arrays of EXTENT_ARRAYS over all entries of a parsed cn_event_extents, from one call of
+    extent_fn(anchors, event, window) -> list over restarts of lists of extent_summary per distinct event: a list over
+    restarts of dicts of (A,) arrays."""
+    anchors = np.asarray(anchors, dtype=np.int64)
+    out = None
+    for ev in sorted(set(events)):
+        sel = np.flatnonzero([e == ev for e in events])
+        per_restart = extent_fn(anchors[sel], event_pair(ev), window)
+        if out is None:
+            out = [dict((k, np.zeros(len(anchors), dtype=bool if k.endswith('censored') else (float if k == 'p_event' else np.int64)))
+                        for k in EXTENT_ARRAYS) for _ in per_restart]
+        for res, summaries in zip(out, per_restart):
+            comp = compact_extents(summaries)
+            for k in EXTENT_ARRAYS:
+                res[k][sel] = comp[k]
+    return out if out is not None else []
+
+
+def add_event_extents(res, names, extents):
+    """Fit result dict `res` gains `event_extents`: the entry names and the arrays of EXTENT_ARRAYS, one entry per name."""
+    out = {'names': list(names)}
+    for k in EXTENT_ARRAYS:
+        # (a record carries them as floats)
+        out[k] = np.asarray(extents[k]).astype(float if k == 'p_event' else (bool if k.endswith('_censored') else np.int64))
+    res['event_extents'] = out
+    return res

@@ -50,6 +50,7 @@ def fit_model(experiment_filename, results_filename, config, ref_data_dir=None, 
         cn_posterior_summary=get('cn_posterior_summary'), cn_regions=get('cn_regions'), cn_region_change_bins=posteriors.change_bins(config),
         cn_call_confidence=posteriors.call_confidence_on(config),
         cn_region_moments=posteriors.region_moments_on(config),
+        cn_event_extents=get('cn_event_extents'), cn_extent_window=get('cn_extent_window'),
         **pipeline._model_kwargs(experiment, config))
     results = dict((ids[k], results[k]) for k in results)
     if _rank() != 0:

@@ -58,4 +58,5 @@ rm -rf $OUT/prof_g
 { python3 $ROOT/tools/decode_time.py 8; python3 $ROOT/tools/decode_time.py 8 2; python3 $ROOT/tools/decode_time.py 12; } 2>&1 | grep "rep \|k_viterbi\|k_backtrace\|results()\|collect_fit" > $OUT/decode_time.txt
 { RST=8 python3 $ROOT/tools/mstep_marks.py; } 2>&1 | grep -v amdgpu.ids > $OUT/mstep_stage_times_share.txt
 python3 $ROOT/tools/region_moments_time.py 2>&1 | grep -v amdgpu.ids > $ROOT/profiles/region_moments.txt
+python3 $ROOT/tools/extent_time.py --samples 512 --nested-anchors 100 2>&1 | grep -v amdgpu.ids > $ROOT/profiles/region_extent.txt
 ls -la $OUT

@@ -797,6 +797,38 @@ static int check_queries(const rmx_batch *b, const char *name, int nq, const int
     return RMX_OK;
 }
 
+// what a region entry point checks first: the restart range, and that there are queries and an output
+static int check_region_call(const rmx_batch *b, const char *name, int r0, int nr, int nq, const int32_t *queries, const double *out) {
+    if (!b || r0 < 0 || nr < 1 || (int64_t)r0 + nr > b->R) return fail(RMX_EARG, "bad restart range");
+    if (nq < 1 || !queries || !out) return fail(RMX_EARG, std::string(name) + ": no queries or no output");
+    return RMX_OK;
+}
+static int check_mask_label_tables(const char *name, int nmask, const uint8_t *masks, int nlabel, const int16_t *labels) {
+    if (nmask < 0 || nlabel < 0 || (nmask > 0 && !masks) || (nlabel > 0 && !labels)) return fail(RMX_EARG, std::string(name) + ": bad mask or label tables");
+    return RMX_OK;
+}
+
+// stages the label, mask and constrain tables of a region call in the shared table buffer (labels first: 2-byte entries) and
+// points ra at them
+static int stage_region_tables(rmx_batch *b, int nmask, const uint8_t *masks, int nlabel, const int16_t *labels, const uint8_t *constrain, RgnArgs *ra) {
+    const size_t N = b->d.N, S = b->d.S, C_ = b->d.C;
+    const size_t lab_bytes = C_ * nlabel * S * sizeof(int16_t), mask_bytes = C_ * nmask * S;
+    int rc;
+    if ((rc = grow(b, &b->d_rgt, &b->rgt_cap, lab_bytes + mask_bytes + (constrain ? N : 0)))) return rc;
+    if (lab_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt, labels, lab_bytes, hipMemcpyHostToDevice, b->stream));
+    if (mask_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes, masks, mask_bytes, hipMemcpyHostToDevice, b->stream));
+    if (constrain) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes + mask_bytes, constrain, N, hipMemcpyHostToDevice, b->stream));
+    ra->labels = (const int16_t *)b->d_rgt; ra->masks = b->d_rgt + lab_bytes; ra->constrain = constrain ? b->d_rgt + lab_bytes + mask_bytes : nullptr;
+    ra->nmask = nmask; ra->nlabel = nlabel; ra->pad_ = 0;
+    return RMX_OK;
+}
+
+// row tiles of 16 states per wave of k_region_counts / k_region_moments for S states: the template argument, 3, 8 or 16
+static int tiles_per_wave(int S) {
+    const int tiles = (S + 15) / 16;
+    return tiles <= 3 * RGN_NW ? 3 : (tiles <= 8 * RGN_NW ? 8 : 16);
+}
+
 // The queries of a region call against restarts r0 .. r0+nr-1, `per` outputs each.  Queries and outputs go through one device
 // buffer of at most 64 MiB (doubles: outputs [nrc][qc][per], then the chunk's queries [qc][4] int32), chunked over queries and over
 // blocks of 65535 restarts; within a block, one launch per run of restarts of one transition model:
@@ -3150,24 +3182,14 @@ int rmx_posterior_summary(rmx_batch *b, int32_t r0, int32_t nr, int32_t Q, const
 // on its own, so a result depends on neither the restart range nor the chunking.
 int rmx_region_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
                     int32_t nlabel, const int16_t *labels, const uint8_t *constrain, double *logp_out) { BIND(b);
-    if (!b || r0 < 0 || nr < 1 || (int64_t)r0 + nr > b->R) return fail(RMX_EARG, "bad restart range");
-    if (nq < 1 || !queries || !logp_out) return fail(RMX_EARG, "region_prob: no queries or no output");
-    if (nmask < 0 || nlabel < 0 || (nmask > 0 && !masks) || (nlabel > 0 && !labels)) return fail(RMX_EARG, "region_prob: bad mask or label tables");
-    const Dev &d = b->d;
-    const int N = d.N, S = d.S, C_ = d.C;
-    if (S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "region_prob: more than 1024 states");
     int rc;
+    if ((rc = check_region_call(b, "region_prob", r0, nr, nq, queries, logp_out))) return rc;
+    if ((rc = check_mask_label_tables("region_prob", nmask, masks, nlabel, labels))) return rc;
+    if (b->d.S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "region_prob: more than 1024 states");
     if ((rc = check_queries(b, "region_prob", nq, queries, {-1, nmask, "region_prob: mask index out of range"}, {-1, nlabel, "region_prob: label index out of range"}))) return rc;
     if ((rc = require_snapshot(b, r0, nr, "region_prob"))) return rc;
-    // tables: labels (2-byte entries first), masks, constrain
-    const size_t lab_bytes = (size_t)C_ * nlabel * S * sizeof(int16_t), mask_bytes = (size_t)C_ * nmask * S;
-    if ((rc = grow(b, &b->d_rgt, &b->rgt_cap, lab_bytes + mask_bytes + (constrain ? (size_t)N : 0)))) return rc;
-    if (lab_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt, labels, lab_bytes, hipMemcpyHostToDevice, b->stream));
-    if (mask_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes, masks, mask_bytes, hipMemcpyHostToDevice, b->stream));
-    if (constrain) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes + mask_bytes, constrain, (size_t)N, hipMemcpyHostToDevice, b->stream));
     RgnArgs ra;
-    ra.labels = (const int16_t *)b->d_rgt; ra.masks = b->d_rgt + lab_bytes; ra.constrain = constrain ? b->d_rgt + lab_bytes + mask_bytes : nullptr;
-    ra.nmask = nmask; ra.nlabel = nlabel; ra.pad_ = 0;
+    if ((rc = stage_region_tables(b, nmask, masks, nlabel, labels, constrain, &ra))) return rc;
     return run_queries(b, r0, nr, nq, queries, 1, KID_REGION, "region_prob: a backward step has a zero or non-finite normaliser", logp_out,
                        [&](const Dev &dv, int r, int n, int, int use_wb, const int32_t *dq, int nqc, double *out, uint32_t *flags) {
         ra.queries = dq; ra.nq = nqc;
@@ -3179,34 +3201,24 @@ int rmx_region_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int3
 // every query.
 int rmx_region_counts(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
                       int32_t nlabel, const int16_t *labels, const uint8_t *constrain, int32_t nbins, double *logp_out) { BIND(b);
-    if (!b || r0 < 0 || nr < 1 || (int64_t)r0 + nr > b->R) return fail(RMX_EARG, "bad restart range");
-    if (nq < 1 || !queries || !logp_out) return fail(RMX_EARG, "region_counts: no queries or no output");
-    if (nbins < 1 || nbins > RGC_KB) return fail(RMX_EARG, "region_counts: the number of bins must be in [1, 16]");
-    if (nmask < 0 || nlabel < 0 || (nmask > 0 && !masks) || (nlabel > 0 && !labels)) return fail(RMX_EARG, "region_counts: bad mask or label tables");
-    const Dev &d = b->d;
-    const int N = d.N, S = d.S, C_ = d.C;
-    if (S > RGC_MAXS) return fail(RMX_EUNSUPPORTED, "region_counts: more than 1024 states");
     int rc;
+    if ((rc = check_region_call(b, "region_counts", r0, nr, nq, queries, logp_out))) return rc;
+    if (nbins < 1 || nbins > RGN_KB) return fail(RMX_EARG, "region_counts: the number of bins must be in [1, 16]");
+    if ((rc = check_mask_label_tables("region_counts", nmask, masks, nlabel, labels))) return rc;
+    if (b->d.S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "region_counts: more than 1024 states");
     if ((rc = check_queries(b, "region_counts", nq, queries, {-1, nmask, "region_counts: mask index out of range"},
                             {0, nlabel, "region_counts: a query needs a label index in [0, nlabel)"}))) return rc;
     if ((rc = require_snapshot(b, r0, nr, "region_counts"))) return rc;
-    // tables: labels (2-byte entries first), masks, constrain
-    const size_t lab_bytes = (size_t)C_ * nlabel * S * sizeof(int16_t), mask_bytes = (size_t)C_ * nmask * S;
-    if ((rc = grow(b, &b->d_rgt, &b->rgt_cap, lab_bytes + mask_bytes + (constrain ? (size_t)N : 0)))) return rc;
-    if (lab_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt, labels, lab_bytes, hipMemcpyHostToDevice, b->stream));
-    if (mask_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes, masks, mask_bytes, hipMemcpyHostToDevice, b->stream));
-    if (constrain) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes + mask_bytes, constrain, (size_t)N, hipMemcpyHostToDevice, b->stream));
-    const size_t lds = rgc_lds_bytes(S);
-    const int tiles = (S + 15) / 16, tpw = tiles <= 3 * RGC_NW ? 3 : (tiles <= 8 * RGC_NW ? 8 : 16);      // row tiles of 16 states per wave
+    RgnArgs ra;
+    if ((rc = stage_region_tables(b, nmask, masks, nlabel, labels, constrain, &ra))) return rc;
+    const size_t lds = rgc_lds_bytes(b->d.S);
+    const int tpw = tiles_per_wave(b->d.S);
     auto kf = tpw == 3 ? k_region_counts<3> : (tpw == 8 ? k_region_counts<8> : k_region_counts<16>);
     if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    RgnArgs ra;
-    ra.labels = (const int16_t *)b->d_rgt; ra.masks = b->d_rgt + lab_bytes; ra.constrain = constrain ? b->d_rgt + lab_bytes + mask_bytes : nullptr;
-    ra.nmask = nmask; ra.nlabel = nlabel; ra.pad_ = 0;
     return run_queries(b, r0, nr, nq, queries, nbins, KID_REGION_COUNTS, "region_counts: a backward step has a zero or non-finite normaliser", logp_out,
                        [&](const Dev &dv, int r, int n, int, int use_wb, const int32_t *dq, int nqc, double *out, uint32_t *flags) {
         ra.queries = dq; ra.nq = nqc;
-        hipLaunchKernelGGL(kf, dim3((unsigned)nqc, n), dim3(RGC_NT), lds, b->stream, dv, r, use_wb, ra, (int)nbins, out, flags);
+        hipLaunchKernelGGL(kf, dim3((unsigned)nqc, n), dim3(RGN_NT), lds, b->stream, dv, r, use_wb, ra, (int)nbins, out, flags);
     });
 }
 
@@ -3222,7 +3234,7 @@ int rmx_call_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t npaths, const in
     if (nlabel < 0 || (nlabel > 0 && !labels)) return fail(RMX_EARG, "call_prob: bad label tables");
     const Dev &d = b->d;
     const int N = d.N, S = d.S, C_ = d.C;
-    if (S > CLP_MAXS) return fail(RMX_EUNSUPPORTED, "call_prob: more than 1024 states");
+    if (S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "call_prob: more than 1024 states");
     int rc;
     if ((rc = check_queries(b, "call_prob", nq, queries, {-1, nlabel, "call_prob: label index out of range"}, {0, npaths, "call_prob: path index out of range"}))) return rc;
     const size_t np = (size_t)nr * npaths * N;
@@ -3256,17 +3268,16 @@ int rmx_call_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t npaths, const in
 // result depends on neither the restart range nor the chunking.
 int rmx_region_moments(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nfeat, const double *features,
                        int32_t nw, const double *weights, int32_t nf, double *out) { BIND(b);
-    if (!b || r0 < 0 || nr < 1 || (int64_t)r0 + nr > b->R) return fail(RMX_EARG, "bad restart range");
-    if (nq < 1 || !queries || !out) return fail(RMX_EARG, "region_moments: no queries or no output");
+    int rc;
+    if ((rc = check_region_call(b, "region_moments", r0, nr, nq, queries, out))) return rc;
     if (nf < 1 || nf > RGM_MAXF) return fail(RMX_EARG, "region_moments: the number of features of a query must be in [1, 4]");
     if (nfeat < nf || nw < 1 || !features || !weights) return fail(RMX_EARG, "region_moments: bad feature or weight tables");
     const Dev &d = b->d;
     const int N = d.N, S = d.S, C_ = d.C;
-    if (S > RGM_MAXS) return fail(RMX_EUNSUPPORTED, "region_moments: more than 1024 states");
+    if (S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "region_moments: more than 1024 states");
     const size_t nfe = (size_t)C_ * nfeat * S, nwe = (size_t)nw * N;
     for (size_t i = 0; i < nfe; i++) if (!std::isfinite(features[i])) return fail(RMX_EARG, "region_moments: a feature is not finite");
     for (size_t i = 0; i < nwe; i++) if (!std::isfinite(weights[i])) return fail(RMX_EARG, "region_moments: a weight is not finite");
-    int rc;
     if ((rc = check_queries(b, "region_moments", nq, queries, {0, nfeat - nf + 1, "region_moments: a query needs a first feature in [0, nfeat - nf]"},
                             {0, nw, "region_moments: weight vector index out of range"}))) return rc;
     if ((rc = require_snapshot(b, r0, nr, "region_moments"))) return rc;
@@ -3275,7 +3286,7 @@ int rmx_region_moments(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const i
     HIPCHK(hipMemcpyAsync(b->d_rgt, features, nfe * sizeof(double), hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipMemcpyAsync(b->d_rgt + nfe * sizeof(double), weights, nwe * sizeof(double), hipMemcpyHostToDevice, b->stream));
     const size_t lds = rgm_lds_bytes(S);
-    const int tiles = (S + 15) / 16, tpw = tiles <= 3 * RGM_NW ? 3 : (tiles <= 8 * RGM_NW ? 8 : 16);      // row tiles of 16 states per wave
+    const int tpw = tiles_per_wave(S);
     auto kf = tpw == 3 ? k_region_moments<3> : (tpw == 8 ? k_region_moments<8> : k_region_moments<16>);
     if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     RgmArgs ra;
@@ -3284,7 +3295,7 @@ int rmx_region_moments(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const i
     return run_queries(b, r0, nr, nq, queries, nf + nf * (nf + 1) / 2, KID_REGION_MOMENTS, "region_moments: a backward step has a zero or non-finite normaliser, or an output is not finite", out,
                        [&](const Dev &dv, int r, int n, int, int use_wb, const int32_t *dq, int nqc, double *o, uint32_t *flags) {
         ra.queries = dq; ra.nq = nqc;
-        hipLaunchKernelGGL(kf, dim3((unsigned)nqc, n), dim3(RGM_NT), lds, b->stream, dv, r, use_wb, ra, o, flags);
+        hipLaunchKernelGGL(kf, dim3((unsigned)nqc, n), dim3(RGN_NT), lds, b->stream, dv, r, use_wb, ra, o, flags);
     });
 }
 
@@ -3295,13 +3306,12 @@ int rmx_region_moments(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const i
 // from the anchor, so a slot depends on neither the restart range, the chunking nor the window.
 int rmx_region_extent(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
                       int32_t nlabel, const int16_t *labels, const uint8_t *constrain, int32_t wl, int32_t wr, double *logp_out) { BIND(b);
-    if (!b || r0 < 0 || nr < 1 || (int64_t)r0 + nr > b->R) return fail(RMX_EARG, "bad restart range");
-    if (nq < 1 || !queries || !logp_out) return fail(RMX_EARG, "region_extent: no queries or no output");
-    if (nmask < 0 || nlabel < 0 || (nmask > 0 && !masks) || (nlabel > 0 && !labels)) return fail(RMX_EARG, "region_extent: bad mask or label tables");
+    int rc;
+    if ((rc = check_region_call(b, "region_extent", r0, nr, nq, queries, logp_out))) return rc;
+    if ((rc = check_mask_label_tables("region_extent", nmask, masks, nlabel, labels))) return rc;
     if (wl < 0 || wr < 0 || (int64_t)wl + wr + 1 > RGX_MAXPER) return fail(RMX_EARG, "region_extent: the window needs wl, wr >= 0 and wl + wr + 1 <= 4096");
-    const Dev &d = b->d;
-    const int N = d.N, S = d.S, C_ = d.C;
-    if (S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "region_extent: more than 1024 states");
+    const int N = b->d.N;
+    if (b->d.S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "region_extent: more than 1024 states");
     for (int i = 0; i < nq; i++) {
         const int32_t *qq = queries + 4 * (size_t)i;
         if (qq[0] < 0 || qq[0] >= N) return fail(RMX_EARG, "region_extent: a query needs an anchor in [0, num_segments)");
@@ -3309,17 +3319,9 @@ int rmx_region_extent(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const in
         if (qq[2] < -1 || qq[2] >= nlabel) return fail(RMX_EARG, "region_extent: label index out of range");
         if (qq[3] != 0) return fail(RMX_EARG, "region_extent: the fourth field of a query must be 0");
     }
-    int rc;
     if ((rc = require_snapshot(b, r0, nr, "region_extent"))) return rc;
-    // tables: labels (2-byte entries first), masks, constrain
-    const size_t lab_bytes = (size_t)C_ * nlabel * S * sizeof(int16_t), mask_bytes = (size_t)C_ * nmask * S;
-    if ((rc = grow(b, &b->d_rgt, &b->rgt_cap, lab_bytes + mask_bytes + (constrain ? (size_t)N : 0)))) return rc;
-    if (lab_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt, labels, lab_bytes, hipMemcpyHostToDevice, b->stream));
-    if (mask_bytes) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes, masks, mask_bytes, hipMemcpyHostToDevice, b->stream));
-    if (constrain) HIPCHK(hipMemcpyAsync(b->d_rgt + lab_bytes + mask_bytes, constrain, (size_t)N, hipMemcpyHostToDevice, b->stream));
     RgnArgs ra;
-    ra.labels = (const int16_t *)b->d_rgt; ra.masks = b->d_rgt + lab_bytes; ra.constrain = constrain ? b->d_rgt + lab_bytes + mask_bytes : nullptr;
-    ra.nmask = nmask; ra.nlabel = nlabel; ra.pad_ = 0;
+    if ((rc = stage_region_tables(b, nmask, masks, nlabel, labels, constrain, &ra))) return rc;
     return run_queries(b, r0, nr, nq, queries, wl + wr + 1, KID_REGION_EXTENT, "region_extent: a step has a zero or non-finite normaliser", logp_out,
                        [&](const Dev &dv, int r, int n, int, int use_wb, const int32_t *dq, int nqc, double *out, uint32_t *flags) {
         ra.queries = dq; ra.nq = nqc;

@@ -5457,8 +5457,11 @@ __global__ __launch_bounds__(64) void k_posterior_summary(Dev d, int r0, int nbe
 // finite number >= 0, sets RGN_ERR_DENOM in flags[r] and gives NaN; a sum of exactly 0 gives -inf.
 // grid (queries, restarts), block RGN_NT; out[ri * nq + query].
 // =============================================================================
+// (RGN_NT, RGN_NW, RGN_KB and RGN_MAXS are also those of k_region_counts, k_call_prob, k_region_moments and k_region_extent below)
 #define RGN_NT 256
+#define RGN_NW (RGN_NT / 64)
 #define RGN_GL 16             // lanes per output state in the reducing pass
+#define RGN_KB 16             // columns of the LDS rows of k_region_counts / k_region_moments and of the matrix instruction's B operand
 #define RGN_MAXS 1024
 #define RGN_ERR_DENOM 1u
 struct RgnArgs {
@@ -5479,12 +5482,97 @@ __device__ inline double rgn_block_sum(double v, double *red) {
     for (int i = 0; i < RGN_NT / 64; i++) t += red[i];
     return t;
 }
+// ---- pieces the region query kernels below share (D(s') on Wb rows, one of the two hot passes, stays written out in each) ----
+// the tables of query fields (mi, li) under the state class of segment n.  mk: the mask, or null (no mask, or n does not bind);
+// lb: the label row, or null (no label).  The class is loaded once and before either condition: beside the segment's other
+// index loads, not behind them
+struct RgnTabs {
+    const uint8_t *mk;
+    const int16_t *lb;
+};
+__device__ __forceinline__ RgnTabs rgn_tabs(const Dev &d, const RgnArgs &q, int n, int mi, int li) {
+    const int cls = d.seg_class[n];
+    RgnTabs t;
+    t.mk = (mi >= 0 && (!q.constrain || q.constrain[n])) ? q.masks + ((size_t)cls * q.nmask + mi) * d.S : nullptr;
+    t.lb = li >= 0 ? q.labels + ((size_t)cls * q.nlabel + li) * d.S : nullptr;
+    return t;
+}
+// the weights W_n of the adjacency n -> n + 1 of restart r (tclass[n] >= 0: the host, or the caller, checked that n is not a chain
+// end).  wb: rows of Wt (Wb: row s' contiguous in s); else exp(trans_value(d, n, s, s', pd)), contiguous in s'
+struct RgnAdj {
+    bool wb;
+    const double *Wt, *pd;
+};
+__device__ __forceinline__ RgnAdj rgn_adj(const Dev &d, int r, int n, int use_wb) {
+    const int tc = d.tclass[n], bs = d.brk_slot[n];
+    RgnAdj t;
+    t.wb = bs < 0 && use_wb;
+    t.Wt = d.Wb + (size_t)tc * d.S * d.S;
+    t.pd = bs >= 0 ? d.pd_lt + ((size_t)r * d.NBE + bs) * d.M * d.D : nullptr;
+    return t;
+}
+// the s < S with pred(s), in state order -> idx[0 .. count), by the first wave of the workgroup: a ballot and a prefix popcount
+// per 64 states; every thread gets the count (the barrier also publishes idx)
+template <class P>
+__device__ __forceinline__ int rgn_compact(int S, int16_t *idx, int &nact, P pred) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid < 64) {
+        int cnt = 0;
+        for (int base = 0; base < S; base += 64) {
+            const int s = base + lane;
+            const bool act = s < S && pred(s);
+            const unsigned long long m = __ballot(act);
+            if (act) idx[cnt + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = (int16_t)s;
+            cnt += __builtin_popcountll(m);
+        }
+        if (lane == 0) nact = cnt;
+    }
+    __syncthreads();
+    return nact;
+}
+// D(s') on exp(trans_value) for one s': the thread owns s' and walks the s with fa(s) != 0
+__device__ __forceinline__ double rgn_D_exp(const Dev &d, int n, int sp, const double *fas, const double *pd) {
+    double D = 0.;
+    for (int s = 0; s < d.S; s++) {
+        const double f = fas[s];
+        if (f != 0.) D = fma(f, exp(trans_value(d, n, s, sp, pd)), D);
+    }
+    return D;
+}
+// takes the sum Z of a step: a bad D(s') of the step, or a Z that is not a finite number >= 0, fails the query; Z == 0 makes
+// logp -inf; else log Z is added and the caller divides by Z (returns true)
+__device__ __forceinline__ bool rgn_take_sum(double Z, bool bad, double &logp, bool &failed) {
+    if (bad || !(Z >= 0. && Z < INFINITY)) failed = true;
+    else if (Z == 0.) logp = -INFINITY;
+    else {
+        logp += log(Z);
+        return true;
+    }
+    return false;
+}
+// the sums over s < S of the first nc <= 16 columns of G [S][16]: 16 lanes of a quarter-wave take the columns, rows stride
+// RGN_NT / 16; thread t < nc gets column t (the others 0).  redc: [RGN_NW][RGN_KB] of LDS
+__device__ __forceinline__ double rgn_column_sums(const double *G, int S, int nc, double (*redc)[RGN_KB]) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    double p = 0.;
+    for (int s = tid >> 4; s < S; s += RGN_NT / 16) p += G[s * RGN_KB + (tid & 15)];
+    p += __shfl_xor(p, 16, 64);
+    p += __shfl_xor(p, 32, 64);
+    if (lane < RGN_KB) redc[tid >> 6][lane] = p;
+    __syncthreads();
+    double t = 0.;
+    if (tid < nc) {
+#pragma unroll
+        for (int i = 0; i < RGN_NW; i++) t += redc[i][tid];
+    }
+    return t;
+}
 __global__ __launch_bounds__(RGN_NT) void k_region_prob(Dev d, int r0, int use_wb, RgnArgs q, double *out, uint32_t *flags) {
     __shared__ double g[RGN_MAXS], h[RGN_MAXS], fas[RGN_MAXS];
     __shared__ double red[RGN_NT / 64];
     __shared__ int16_t lab[2][RGN_MAXS], idx[RGN_MAXS];
     __shared__ int nact, s_bad;
-    const int qi = blockIdx.x, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x, lane = tid & 63;
+    const int qi = blockIdx.x, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x;
     const int grp = tid / RGN_GL, gl = tid % RGN_GL;
     const int S = d.S;
     const int a = q.queries[4 * qi], b = q.queries[4 * qi + 1], mi = q.queries[4 * qi + 2], li = q.queries[4 * qi + 3];
@@ -5494,10 +5582,8 @@ __global__ __launch_bounds__(RGN_NT) void k_region_prob(Dev d, int r0, int use_w
     bool failed = false;
     // ---- start: g_b = [mask] post_b ---------------------------------------------------------------------
     {
-        const int cls = d.seg_class[b];
         const double *post = d.post + rs_off(d, r, b);
-        const uint8_t *mk = (mi >= 0 && (!q.constrain || q.constrain[b])) ? q.masks + ((size_t)cls * q.nmask + mi) * S : nullptr;
-        const int16_t *lb = li >= 0 ? q.labels + ((size_t)cls * q.nlabel + li) * S : nullptr;
+        const auto [mk, lb] = rgn_tabs(d, q, b, mi, li);
         double part = 0.;
         for (int s = tid; s < S; s += RGN_NT) {
             const double v = (!mk || mk[s]) ? post[s] : 0.;
@@ -5505,19 +5591,13 @@ __global__ __launch_bounds__(RGN_NT) void k_region_prob(Dev d, int r0, int use_w
             if (lb) lab[cur][s] = lb[s];
         }
         const double Z = rgn_block_sum(part, red);
-        if (!(Z >= 0. && Z < INFINITY)) failed = true;
-        else if (Z == 0.) logp = -INFINITY;
-        else {
-            logp = log(Z);
+        if (rgn_take_sum(Z, false, logp, failed))
             for (int s = tid; s < S; s += RGN_NT) g[s] = g[s] / Z;
-        }
     }
     for (int n = b - 1; n >= a && !failed && logp > -INFINITY; n--) {
-        const int tc = d.tclass[n], bs = d.brk_slot[n];      // (tc >= 0: the host checked that the run lies in one chain)
-        const int cls = d.seg_class[n];
+        const auto [wb, Wt, pd] = rgn_adj(d, r, n, use_wb);
         const double *fa = d.fa + rs_off(d, r, n);
-        const uint8_t *mk = (mi >= 0 && (!q.constrain || q.constrain[n])) ? q.masks + ((size_t)cls * q.nmask + mi) * S : nullptr;
-        const int16_t *lb = li >= 0 ? q.labels + ((size_t)cls * q.nlabel + li) * S : nullptr;
+        const auto [mk, lb] = rgn_tabs(d, q, n, mi, li);
         const int16_t *lab1 = lab[cur];
         int16_t *lab0 = lab[cur ^ 1];
         for (int s = tid; s < S; s += RGN_NT) {
@@ -5525,22 +5605,9 @@ __global__ __launch_bounds__(RGN_NT) void k_region_prob(Dev d, int r0, int use_w
             if (lb) lab0[s] = lb[s];
         }
         __syncthreads();
-        if (bs < 0 && use_wb) {
-            const double *Wt = d.Wb + (size_t)tc * S * S;
+        if (wb) {
             // the states s' with g(s') > 0, in state order
-            if (tid < 64) {
-                int cnt = 0;
-                for (int base = 0; base < S; base += 64) {
-                    const int s = base + lane;
-                    const bool act = s < S && g[s] > 0.;
-                    const unsigned long long m = __ballot(act);
-                    if (act) idx[cnt + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = (int16_t)s;
-                    cnt += __builtin_popcountll(m);
-                }
-                if (lane == 0) nact = cnt;
-            }
-            __syncthreads();
-            const int na = nact;
+            const int na = rgn_compact(S, idx, nact, [&](int s) { return g[s] > 0.; });
             // D(s') and h(s') = g(s') / D(s'): 16 lanes per s'
             for (int j0 = 0; j0 < na; j0 += RGN_NT / RGN_GL) {
                 const int j = j0 + grp;
@@ -5574,17 +5641,12 @@ __global__ __launch_bounds__(RGN_NT) void k_region_prob(Dev d, int r0, int use_w
                 g[s] = acc;
             }
         } else {
-            const double *pd = bs >= 0 ? d.pd_lt + ((size_t)r * d.NBE + bs) * d.M * d.D : nullptr;
             // D(s') and h(s'): the thread owns s'
             for (int sp = tid; sp < S; sp += RGN_NT) {
                 const double gv = g[sp];
                 double hv = 0.;
                 if (gv > 0.) {
-                    double D = 0.;
-                    for (int s = 0; s < S; s++) {
-                        const double f = fas[s];
-                        if (f != 0.) D = fma(f, exp(trans_value(d, n, s, sp, pd)), D);
-                    }
+                    const double D = rgn_D_exp(d, n, sp, fas, pd);
                     if (!(D > 0. && D < INFINITY)) s_bad = 1;
                     hv = gv / D;
                 }
@@ -5611,12 +5673,8 @@ __global__ __launch_bounds__(RGN_NT) void k_region_prob(Dev d, int r0, int use_w
         double part = 0.;
         for (int s = tid; s < S; s += RGN_NT) part += g[s];
         const double Z = rgn_block_sum(part, red);
-        if (s_bad || !(Z >= 0. && Z < INFINITY)) failed = true;
-        else if (Z == 0.) logp = -INFINITY;
-        else {
-            logp += log(Z);
+        if (rgn_take_sum(Z, s_bad != 0, logp, failed))
             for (int s = tid; s < S; s += RGN_NT) g[s] = g[s] / Z;
-        }
         cur ^= 1;
     }
     if (tid == 0) {
@@ -5649,38 +5707,33 @@ __global__ __launch_bounds__(RGN_NT) void k_region_prob(Dev d, int r0, int use_w
 // Every sum has one order, fixed by S and K alone: a (restart, query) result does not depend on the launch.  Only columns
 // s < S of fa / post are read (clamped address and select).  A D(s') that is 0 or not finite under mass, or a total that is
 // not a finite number >= 0, sets RGN_ERR_DENOM in flags[r] and gives NaN in every bin; a bin that cannot happen gives -inf.
-// grid (queries, restarts), block RGC_NT, dynamic LDS rgc_lds_bytes(S); out[(ri * nq + query) * K + k].
+// grid (queries, restarts), block RGN_NT, dynamic LDS rgc_lds_bytes(S); out[(ri * nq + query) * K + k].
 // =============================================================================
-#define RGC_NT 256
-#define RGC_NW (RGC_NT / 64)
-#define RGC_KB 16             // bins of the LDS rows and of the matrix instruction's B operand
-#define RGC_MAXS 1024
-static inline size_t rgc_lds_bytes(int S) { const size_t SR = ((size_t)S + 15) & ~(size_t)15; return SR * (RGC_KB * 8 + 8 + 3 * 2); }
+static inline size_t rgc_lds_bytes(int S) { const size_t SR = ((size_t)S + 15) & ~(size_t)15; return SR * (RGN_KB * 8 + 8 + 3 * 2); }
 template <int TPW>
-__global__ __launch_bounds__(RGC_NT) void k_region_counts(Dev d, int r0, int use_wb, RgnArgs q, int K, double *out, uint32_t *flags) {
+__global__ __launch_bounds__(RGN_NT) void k_region_counts(Dev d, int r0, int use_wb, RgnArgs q, int K, double *out, uint32_t *flags) {
     extern __shared__ double rgc_lds[];                 // G [SR][16], fas [SR], lab [2][SR] (int16), idx [SR] (int16)
-    __shared__ double red[RGC_NW], redc[RGC_NW][RGC_KB];
+    __shared__ double red[RGN_NW], redc[RGN_NW][RGN_KB];
     __shared__ int nact, s_bad;
     const int qi = blockIdx.x, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (uniform, and known to be: the matrix instructions sit under conditions on it)
     const int grp = tid / RGN_GL, gl = tid % RGN_GL;
     const int ai = lane & 15, kk = lane >> 4;
     const int S = d.S, SR = (S + 15) & ~15;
-    double *G = rgc_lds, *fas = G + (size_t)SR * RGC_KB;
+    double *G = rgc_lds, *fas = G + (size_t)SR * RGN_KB;
     int16_t *labs = (int16_t *)(fas + SR), *idx = labs + 2 * SR;
     const int a = q.queries[4 * qi], b = q.queries[4 * qi + 1], mi = q.queries[4 * qi + 2], li = q.queries[4 * qi + 3];
+    __builtin_assume(li >= 0);      // (the host checked: every query of this kernel names a label)
     if (tid == 0) s_bad = 0;
     int cur = 0;              // labs[cur * SR ..]: the labels of segment n + 1
     double logp = 0.;
     bool failed = false;
     // ---- start: G_b(s, 0) = [mask] post_b(s) ----------------------------------------------------------------
     {
-        const int cls = d.seg_class[b];
         const double *post = d.post + rs_off(d, r, b);
-        const uint8_t *mk = (mi >= 0 && (!q.constrain || q.constrain[b])) ? q.masks + ((size_t)cls * q.nmask + mi) * S : nullptr;
-        const int16_t *lb = q.labels + ((size_t)cls * q.nlabel + li) * S;
+        const auto [mk, lb] = rgn_tabs(d, q, b, mi, li);      // (li >= 0: the host checked)
         double part = 0.;
-        for (int s = tid; s < SR; s += RGC_NT) {
+        for (int s = tid; s < SR; s += RGN_NT) {
             const int sc = s < S ? s : S - 1;
             const double pv = post[sc];
             const double v = (s < S && (!mk || mk[sc])) ? pv : 0.;
@@ -5688,28 +5741,20 @@ __global__ __launch_bounds__(RGC_NT) void k_region_counts(Dev d, int r0, int use
             labs[cur * SR + s] = lb[sc];
         }
         const double Z = rgn_block_sum(part, red);
-        if (!(Z >= 0. && Z < INFINITY)) failed = true;
-        else if (Z == 0.) logp = -INFINITY;
-        else logp = log(Z);
-        const bool okz = !failed && Z > 0.;
-        for (int e = tid; e < SR * RGC_KB; e += RGC_NT) {
-            const int s = e / RGC_KB, k = e % RGC_KB, sc = s < S ? s : S - 1;
+        const bool okz = rgn_take_sum(Z, false, logp, failed);
+        for (int e = tid; e < SR * RGN_KB; e += RGN_NT) {
+            const int s = e / RGN_KB, k = e % RGN_KB, sc = s < S ? s : S - 1;
             const double pv = post[sc];
             G[e] = (okz && k == 0 && s < S && (!mk || mk[sc])) ? pv / Z : 0.;
         }
     }
     for (int n = b - 1; n >= a && !failed && logp > -INFINITY; n--) {
-        const int tc = d.tclass[n], bs = d.brk_slot[n];      // (tc >= 0: the host checked that the run lies in one chain)
-        const int cls = d.seg_class[n];
+        const auto [wb, Wt, pd] = rgn_adj(d, r, n, use_wb);
         const double *fa = d.fa + rs_off(d, r, n);
-        const uint8_t *mk = (mi >= 0 && (!q.constrain || q.constrain[n])) ? q.masks + ((size_t)cls * q.nmask + mi) * S : nullptr;
-        const int16_t *lb = q.labels + ((size_t)cls * q.nlabel + li) * S;
+        const auto [mk, lb] = rgn_tabs(d, q, n, mi, li);      // (li >= 0: the host checked)
         const int16_t *lab1 = labs + cur * SR;
         int16_t *lab0 = labs + (cur ^ 1) * SR;
-        const bool wb = bs < 0 && use_wb;
-        const double *Wt = d.Wb + (size_t)tc * S * S;
-        const double *pd = bs >= 0 ? d.pd_lt + ((size_t)r * d.NBE + bs) * d.M * d.D : nullptr;
-        for (int s = tid; s < SR; s += RGC_NT) {
+        for (int s = tid; s < SR; s += RGN_NT) {
             const int sc = s < S ? s : S - 1;
             const double fv = fa[sc];
             fas[s] = s < S ? fv : 0.;
@@ -5717,23 +5762,14 @@ __global__ __launch_bounds__(RGC_NT) void k_region_counts(Dev d, int r0, int use
         }
         // ---- 1. the states s' with mass, in state order ------------------------------------------------------
         __syncthreads();      // (G of the step before, or of the start, is complete)
-        if (tid < 64) {
-            int cnt = 0;
-            for (int base = 0; base < S; base += 64) {
-                const int s = base + lane;
-                bool act = false;
-                if (s < S) for (int k = 0; k < K; k++) act = act || G[s * RGC_KB + k] > 0.;
-                const unsigned long long m = __ballot(act);
-                if (act) idx[cnt + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = (int16_t)s;
-                cnt += __builtin_popcountll(m);
-            }
-            if (lane == 0) nact = cnt;
-        }
-        __syncthreads();
-        const int na = __builtin_amdgcn_readfirstlane(nact);
+        const int na = __builtin_amdgcn_readfirstlane(rgn_compact(S, idx, nact, [&](int s) {
+            bool act = false;
+            for (int k = 0; k < K; k++) act = act || G[s * RGN_KB + k] > 0.;
+            return act;
+        }));
         // ---- 2. D(s') and H = G / D in place -----------------------------------------------------------------
         if (wb) {
-            for (int j0 = 0; j0 < na; j0 += RGC_NT / RGN_GL) {
+            for (int j0 = 0; j0 < na; j0 += RGN_NT / RGN_GL) {
                 const int j = j0 + grp;
                 const bool ok = j < na;
                 const int sp = ok ? idx[j] : 0;
@@ -5745,19 +5781,15 @@ __global__ __launch_bounds__(RGC_NT) void k_region_counts(Dev d, int r0, int use
                 const double D = group_sum(p, RGN_GL);
                 if (ok) {
                     if (gl == 0 && !(D > 0. && D < INFINITY)) s_bad = 1;
-                    if (gl < K) G[sp * RGC_KB + gl] = G[sp * RGC_KB + gl] / D;
+                    if (gl < K) G[sp * RGN_KB + gl] = G[sp * RGN_KB + gl] / D;
                 }
             }
         } else {
-            for (int j = tid; j < na; j += RGC_NT) {
+            for (int j = tid; j < na; j += RGN_NT) {
                 const int sp = idx[j];
-                double D = 0.;
-                for (int s = 0; s < S; s++) {
-                    const double f = fas[s];
-                    if (f != 0.) D = fma(f, exp(trans_value(d, n, s, sp, pd)), D);
-                }
+                const double D = rgn_D_exp(d, n, sp, fas, pd);
                 if (!(D > 0. && D < INFINITY)) s_bad = 1;
-                for (int k = 0; k < K; k++) G[sp * RGC_KB + k] = G[sp * RGC_KB + k] / D;
+                for (int k = 0; k < K; k++) G[sp * RGN_KB + k] = G[sp * RGN_KB + k] / D;
             }
         }
         __syncthreads();
@@ -5767,7 +5799,7 @@ __global__ __launch_bounds__(RGC_NT) void k_region_counts(Dev d, int r0, int use
 #pragma unroll
         for (int u = 0; u < TPW; u++) {
             acc[u] = psm_d4{0., 0., 0., 0.};
-            const int s = (wave + RGC_NW * u) * 16 + ai;
+            const int s = (wave + RGN_NW * u) * 16 + ai;
             const int sc = s < S ? s : S - 1;
             const bool rok = s < S && (!mk || mk[sc]);
             rowlab[u] = rok ? (int)lab0[sc] : (int)0x80000000;
@@ -5777,12 +5809,12 @@ __global__ __launch_bounds__(RGC_NT) void k_region_counts(Dev d, int r0, int use
             const bool ok = j < na;
             const int sp = idx[ok ? j : 0];
             const int lsp = lab1[sp];
-            const double hv = G[sp * RGC_KB + ai], hm = G[sp * RGC_KB + (ai > 0 ? ai - 1 : 0)];
+            const double hv = G[sp * RGN_KB + ai], hm = G[sp * RGN_KB + (ai > 0 ? ai - 1 : 0)];
             const double bsame = (ok && ai < K) ? hv : 0.;
             const double bshift = !ok ? 0. : (K == 1 ? bsame : (ai == 0 || ai >= K) ? 0. : (ai < K - 1 ? hm : hm + hv));
 #pragma unroll
             for (int u = 0; u < TPW; u++) {
-                const int s0 = (wave + RGC_NW * u) * 16;
+                const int s0 = (wave + RGN_NW * u) * 16;
                 if (s0 < S) {         // (uniform over the wave)
                     const int s = s0 + ai, sc = s < S ? s : S - 1;
                     double wv;
@@ -5798,7 +5830,7 @@ __global__ __launch_bounds__(RGC_NT) void k_region_counts(Dev d, int r0, int use
         double part = 0.;
 #pragma unroll
         for (int u = 0; u < TPW; u++) {
-            const int s0 = (wave + RGC_NW * u) * 16;
+            const int s0 = (wave + RGN_NW * u) * 16;
 #pragma unroll
             for (int g = 0; g < 4; g++) {
                 const int s = s0 + kk + 4 * g;
@@ -5808,34 +5840,23 @@ __global__ __launch_bounds__(RGC_NT) void k_region_counts(Dev d, int r0, int use
             }
         }
         const double Z = rgn_block_sum(part, red);
-        if (s_bad || !(Z >= 0. && Z < INFINITY)) failed = true;
-        else if (Z == 0.) logp = -INFINITY;
-        else logp += log(Z);
-        const bool okz = !failed && Z > 0.;
+        const bool okz = rgn_take_sum(Z, s_bad != 0, logp, failed);
 #pragma unroll
         for (int u = 0; u < TPW; u++) {
-            const int s0 = (wave + RGC_NW * u) * 16;
+            const int s0 = (wave + RGN_NW * u) * 16;
 #pragma unroll
             for (int g = 0; g < 4; g++) {
                 const int s = s0 + kk + 4 * g;
-                if (s < SR) G[s * RGC_KB + ai] = okz ? acc[u][g] / Z : 0.;
+                if (s < SR) G[s * RGN_KB + ai] = okz ? acc[u][g] / Z : 0.;
             }
         }
         cur ^= 1;
     }
-    // ---- P(k) = sum_s G_a(s, k): 16 lanes of a quarter-wave take the bins, rows stride RGC_NT / 16 -----------------
+    // ---- P(k) = sum_s G_a(s, k) -----------------------------------------------------------------------------------
     __syncthreads();
     {
-        double p = 0.;
-        for (int s = tid >> 4; s < S; s += RGC_NT / 16) p += G[s * RGC_KB + (tid & 15)];
-        p += __shfl_xor(p, 16, 64);
-        p += __shfl_xor(p, 32, 64);
-        if (lane < RGC_KB) redc[wave][lane] = p;
-        __syncthreads();
+        const double t = rgn_column_sums(G, S, K, redc);
         if (tid < K) {
-            double t = 0.;
-#pragma unroll
-            for (int i = 0; i < RGC_NW; i++) t += redc[i][tid];
             double v;
             if (failed) v = __builtin_nan("");
             else if (!(logp > -INFINITY) || t == 0.) v = -INFINITY;
@@ -5875,7 +5896,6 @@ __global__ __launch_bounds__(RGC_NT) void k_region_counts(Dev d, int r0, int use
 #define CLP_WPB 4             // waves (= queries) per workgroup
 #define CLP_NSL 16            // states per lane of the fa row: S <= 1024
 #define CLP_GL 16             // lanes per allowed state in the g pass
-#define CLP_MAXS 1024
 #define CLP_ERR_DENOM 1u
 struct ClpArgs {
     const int32_t *queries;   // [nq][4]: a, b, label index or -1, path index
@@ -5952,11 +5972,8 @@ __global__ __launch_bounds__(64 * CLP_WPB) void k_call_prob(Dev d, int r0, int u
         nm = clp_finish(group_sum(part, 64), na, lane, g, gidx, h, hidx, logp);
     }
     for (int n = b - 1; n >= a && nm > 0; n--) {
-        const int tc = d.tclass[n], bs = d.brk_slot[n];      // (tc >= 0: the host checked that the run lies in one chain)
+        const auto [wb, Wt, pd] = rgn_adj(d, r, n, use_wb);
         const double *fa = d.fa + rs_off(d, r, n);
-        const bool wb = bs < 0 && use_wb;
-        const double *Wt = d.Wb + (size_t)tc * S * S;
-        const double *pd = bs >= 0 ? d.pd_lt + ((size_t)r * d.NBE + bs) * d.M * d.D : nullptr;
         // the fa row for the Wb rows: lane l holds states l, l + 64, ...
         double f[CLP_NSL];
 #pragma unroll
@@ -6051,21 +6068,17 @@ __global__ __launch_bounds__(64 * CLP_WPB) void k_call_prob(Dev d, int r0, int u
 // Every sum has one order, fixed by S and nf alone: a (restart, query) result does not depend on the launch.  Only columns
 // s < S of fa / post are read (clamped address and select).  A D(s') that is 0 or not finite under G(s') != 0, or an output
 // that is not finite, sets RGN_ERR_DENOM in flags[r] and gives NaN in every output of the query.
-// grid (queries, restarts), block RGM_NT, dynamic LDS rgm_lds_bytes(S); out[(ri * nq + query) * per + j], per = nf + nf (nf + 1) / 2:
+// grid (queries, restarts), block RGN_NT, dynamic LDS rgm_lds_bytes(S); out[(ri * nq + query) * per + j], per = nf + nf (nf + 1) / 2:
 // the means, then the covariances.
 // =============================================================================
-#define RGM_NT 256
-#define RGM_NW (RGM_NT / 64)
-#define RGM_KB 16             // columns of the LDS rows and of the matrix instruction's B operand
 #define RGM_MAXF 4
-#define RGM_MAXS 1024
 struct RgmArgs {
     const int32_t *queries;   // [nq][4]: a, b, first feature, weight vector
     const double *features;   // [C][nfeat][S]
     const double *weights;    // [nw][N]
     int nq, nfeat, nf, pad_;
 };
-static inline size_t rgm_lds_bytes(int S) { const size_t SR = ((size_t)S + 15) & ~(size_t)15; return SR * (RGM_KB * 8 + 8 + 8 + 2); }
+static inline size_t rgm_lds_bytes(int S) { const size_t SR = ((size_t)S + 15) & ~(size_t)15; return SR * (RGN_KB * 8 + 8 + 8 + 2); }
 __device__ inline double rgm_pick(double v0, double v1, double v2, double v3, int i) { return i == 0 ? v0 : (i == 1 ? v1 : (i == 2 ? v2 : v3)); }
 // post_n and fa_n of segment n to LDS (0 past S), and phibar_n,f for f < nf: block sums in a fixed order; the barriers also
 // publish the two rows (and end the reads of what they replace: the caller has a barrier before the call)
@@ -6074,7 +6087,7 @@ __device__ inline void rgm_segment(const Dev &d, int r, int n, int nf, const dou
     const int S = d.S, SR = (S + 15) & ~15, tid = threadIdx.x;
     const double *fa = d.fa + rs_off(d, r, n), *post = d.post + rs_off(d, r, n);
     double v[RGM_MAXF + 1] = {0., 0., 0., 0., 0.};
-    for (int s = tid; s < SR; s += RGM_NT) {
+    for (int s = tid; s < SR; s += RGN_NT) {
         const int sc = s < S ? s : S - 1;
         const double fv = fa[sc], pr = post[sc];
         const double pv = s < S ? pr : 0.;
@@ -6096,22 +6109,22 @@ __device__ inline void rgm_segment(const Dev &d, int r, int n, int nf, const dou
     for (int k = 0; k <= RGM_MAXF; k++) {
         double t = 0.;
 #pragma unroll
-        for (int i = 0; i < RGM_NW; i++) t += red[i][k];
+        for (int i = 0; i < RGN_NW; i++) t += red[i][k];
         v[k] = t;
     }
     m0 = v[1] / v[0]; m1 = v[2] / v[0]; m2 = v[3] / v[0]; m3 = v[4] / v[0];
 }
 template <int TPW>
-__global__ __launch_bounds__(RGM_NT) void k_region_moments(Dev d, int r0, int use_wb, RgmArgs q, double *out, uint32_t *flags) {
+__global__ __launch_bounds__(RGN_NT) void k_region_moments(Dev d, int r0, int use_wb, RgmArgs q, double *out, uint32_t *flags) {
     extern __shared__ double rgm_lds[];                 // G [SR][16], fas [SR], pst [SR], idx [SR] (int16)
-    __shared__ double red[RGM_NW][RGM_MAXF + 1], redc[RGM_NW][RGM_KB];
+    __shared__ double red[RGN_NW][RGM_MAXF + 1], redc[RGN_NW][RGN_KB];
     __shared__ int nact, s_bad;
     const int qi = blockIdx.x, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (uniform, and known to be: the matrix instructions sit under conditions on it)
     const int grp = tid / RGN_GL, gl = tid % RGN_GL;
     const int ai = lane & 15, kk = lane >> 4;
     const int S = d.S, SR = (S + 15) & ~15;
-    double *G = rgm_lds, *fas = G + (size_t)SR * RGM_KB, *pst = fas + SR;
+    double *G = rgm_lds, *fas = G + (size_t)SR * RGN_KB, *pst = fas + SR;
     int16_t *idx = (int16_t *)(pst + SR);
     const int a = q.queries[4 * qi], b = q.queries[4 * qi + 1], f0 = q.queries[4 * qi + 2], wi = q.queries[4 * qi + 3];
     const int nf = q.nf, ncol = nf + nf * (nf + 1) / 2;
@@ -6138,8 +6151,8 @@ __global__ __launch_bounds__(RGM_NT) void k_region_moments(Dev d, int r0, int us
         const double w = wt[b];
         mean0 = w * pb0; mean1 = w * pb1; mean2 = w * pb2; mean3 = w * pb3;
         const double bf = rgm_pick(pb0, pb1, pb2, pb3, cf), bg = rgm_pick(pb0, pb1, pb2, pb3, cg);
-        for (int e = tid; e < SR * RGM_KB; e += RGM_NT) {         // (column e % 16 == ai)
-            const int s = e / RGM_KB, sc = s < S ? s : S - 1;
+        for (int e = tid; e < SR * RGN_KB; e += RGN_NT) {         // (column e % 16 == ai)
+            const int s = e / RGN_KB, sc = s < S ? s : S - 1;
             const double pv = pst[s];
             const double tf = ph[(size_t)cf * S + sc] - bf, tg = ph[(size_t)cg * S + sc] - bg;
             double v = 0.;
@@ -6176,7 +6189,7 @@ __global__ __launch_bounds__(RGM_NT) void k_region_moments(Dev d, int r0, int us
         rgm_segment(d, r, n, nf, ph, fas, pst, red, pb0, pb1, pb2, pb3);
         mean0 = fma(w, pb0, mean0); mean1 = fma(w, pb1, mean1); mean2 = fma(w, pb2, mean2); mean3 = fma(w, pb3, mean3);
         if (wb) {
-            for (int j0 = 0; j0 < na; j0 += RGM_NT / RGN_GL) {
+            for (int j0 = 0; j0 < na; j0 += RGN_NT / RGN_GL) {
                 const int j = j0 + grp;
                 const bool ok = j < na;
                 const int sp = ok ? idx[j] : 0;
@@ -6187,15 +6200,15 @@ __global__ __launch_bounds__(RGM_NT) void k_region_moments(Dev d, int r0, int us
                 }
                 const double D = group_sum(p, RGN_GL);
                 if (ok) {
-                    const double gv = G[sp * RGM_KB + gl];
+                    const double gv = G[sp * RGN_KB + gl];
                     if (gv != 0.) {
                         if (!(D > 0. && D < INFINITY)) s_bad = 1;
-                        G[sp * RGM_KB + gl] = gv / D;
+                        G[sp * RGN_KB + gl] = gv / D;
                     }
                 }
             }
         } else {
-            for (int j = tid; j < na; j += RGM_NT) {
+            for (int j = tid; j < na; j += RGN_NT) {
                 const int sp = idx[j];
                 double D = 0.;
                 for (int s = 0; s < S; s++) {
@@ -6203,10 +6216,10 @@ __global__ __launch_bounds__(RGM_NT) void k_region_moments(Dev d, int r0, int us
                     if (f != 0.) D = fma(f, exp(trans_value(d, n, s, sp, pd)), D);
                 }
                 for (int k = 0; k < ncol; k++) {
-                    const double gv = G[sp * RGM_KB + k];
+                    const double gv = G[sp * RGN_KB + k];
                     if (gv != 0.) {
                         if (!(D > 0. && D < INFINITY)) s_bad = 1;
-                        G[sp * RGM_KB + k] = gv / D;
+                        G[sp * RGN_KB + k] = gv / D;
                     }
                 }
             }
@@ -6220,11 +6233,11 @@ __global__ __launch_bounds__(RGM_NT) void k_region_moments(Dev d, int r0, int us
             const int j = j0 + kk;
             const bool ok = j < na;
             const int sp = idx[ok ? j : 0];
-            const double hv = G[sp * RGM_KB + ai];
+            const double hv = G[sp * RGN_KB + ai];
             const double bv = ok ? hv : 0.;
 #pragma unroll
             for (int u = 0; u < TPW; u++) {
-                const int s0 = (wave + RGM_NW * u) * 16;
+                const int s0 = (wave + RGN_NW * u) * 16;
                 if (s0 < S) {         // (uniform over the wave)
                     const int s = s0 + ai, sc = s < S ? s : S - 1;
                     const bool live = ok && s < S;
@@ -6239,13 +6252,13 @@ __global__ __launch_bounds__(RGM_NT) void k_region_moments(Dev d, int r0, int us
         __syncthreads();
 #pragma unroll
         for (int u = 0; u < TPW; u++) {
-            const int s0 = (wave + RGM_NW * u) * 16;
+            const int s0 = (wave + RGN_NW * u) * 16;
 #pragma unroll
             for (int g = 0; g < 4; g++) {
                 const int s = s0 + kk + 4 * g;
                 if (s < SR) {
                     const double fv = fas[s];
-                    G[s * RGM_KB + ai] = fv != 0. ? fv * acc[u][g] : 0.;
+                    G[s * RGN_KB + ai] = fv != 0. ? fv * acc[u][g] : 0.;
                 }
             }
         }
@@ -6254,9 +6267,9 @@ __global__ __launch_bounds__(RGM_NT) void k_region_moments(Dev d, int r0, int us
         // wave writes the row)
         const double bf = rgm_pick(pb0, pb1, pb2, pb3, cf), bg = rgm_pick(pb0, pb1, pb2, pb3, cg);
 #pragma unroll 1
-        for (int e = tid; e < SR * RGM_KB; e += RGM_NT) {         // (column e % 16 == ai)
-            const int s = e / RGM_KB, sc = s < S ? s : S - 1;
-            const double x = G[e], x1f = G[s * RGM_KB + cf], x1g = G[s * RGM_KB + cg];
+        for (int e = tid; e < SR * RGN_KB; e += RGN_NT) {         // (column e % 16 == ai)
+            const int s = e / RGN_KB, sc = s < S ? s : S - 1;
+            const double x = G[e], x1f = G[s * RGN_KB + cf], x1g = G[s * RGN_KB + cg];
             const double pv = pst[s];
             const double tf = ph[(size_t)cf * S + sc] - bf, tg = ph[(size_t)cg * S + sc] - bg;
             double v = 0.;
@@ -6265,20 +6278,20 @@ __global__ __launch_bounds__(RGM_NT) void k_region_moments(Dev d, int r0, int us
             G[e] = v;
         }
     }
-    // ---- Cov = sum_s G2_a(s): 16 lanes of a quarter-wave take the columns, rows stride RGM_NT / 16 --------------------
+    // ---- Cov = sum_s G2_a(s): 16 lanes of a quarter-wave take the columns, rows stride RGN_NT / 16 --------------------
     __syncthreads();
     {
         double p = 0.;
-        for (int s = tid >> 4; s < S; s += RGM_NT / 16) p += G[s * RGM_KB + (tid & 15)];
+        for (int s = tid >> 4; s < S; s += RGN_NT / 16) p += G[s * RGN_KB + (tid & 15)];
         p += __shfl_xor(p, 16, 64);
         p += __shfl_xor(p, 32, 64);
-        if (lane < RGM_KB) redc[wave][lane] = p;
+        if (lane < RGN_KB) redc[wave][lane] = p;
         __syncthreads();
         double v = 0.;
         if (tid < ncol) {
             double t = 0.;
 #pragma unroll
-            for (int i = 0; i < RGM_NW; i++) t += redc[i][tid];
+            for (int i = 0; i < RGN_NW; i++) t += redc[i][tid];
             v = tid < nf ? rgm_pick(mean0, mean1, mean2, mean3, tid) : t;
             if (!(v - v == 0.)) s_bad = 1;
         }
@@ -6331,7 +6344,7 @@ __global__ __launch_bounds__(RGN_NT) void k_region_extent(Dev d, int r0, int use
     __shared__ double red[3 * (RGN_NT / 64)];
     __shared__ int16_t lab[2][RGN_MAXS], idx[RGN_MAXS];
     __shared__ int nact, s_bad;
-    const int qi = blockIdx.x, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x, lane = tid & 63;
+    const int qi = blockIdx.x, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x;
     const int grp = tid / RGN_GL, gl = tid % RGN_GL;
     const int S = d.S, N = d.N;
     const int n0 = q.queries[4 * qi], mi = q.queries[4 * qi + 1], li = q.queries[4 * qi + 2];
@@ -6341,21 +6354,19 @@ __global__ __launch_bounds__(RGN_NT) void k_region_extent(Dev d, int r0, int use
     bool failed = false;
     int nleft = 0, nright = 0;       // slots written on either side of slot wl
     double logp0 = 0.;
+    const RgnTabs t0 = rgn_tabs(d, q, n0, mi, li);      // the anchor's tables
     // ---- the anchor: g_n0 = [mask] post_n0; slot wl ------------------------------------------------------------------
     {
-        const int cls = d.seg_class[n0];
         const double *post = d.post + rs_off(d, r, n0);
-        const uint8_t *mk = (mi >= 0 && (!q.constrain || q.constrain[n0])) ? q.masks + ((size_t)cls * q.nmask + mi) * S : nullptr;
+        const uint8_t *mk = t0.mk;
         double part = 0.;
         for (int s = tid; s < S; s += RGN_NT) {
             const double v = (!mk || mk[s]) ? post[s] : 0.;
             g[s] = v; part += v;
         }
         const double Z = rgn_block_sum(part, red);
-        if (!(Z >= 0. && Z < INFINITY)) failed = true;
-        else if (Z == 0.) logp0 = -INFINITY;
-        else {
-            logp0 = mk ? log(Z) : 0.;
+        if (rgn_take_sum(Z, false, logp0, failed)) {
+            if (!mk) logp0 = 0.;      // (an unbound anchor is certain)
             for (int s = tid; s < S; s += RGN_NT) g[s] = g[s] / Z;
         }
         if (tid == 0) orow[wl] = logp0;
@@ -6364,16 +6375,14 @@ __global__ __launch_bounds__(RGN_NT) void k_region_extent(Dev d, int r0, int use
     {
         int cur = 0;              // lab[cur]: the labels of segment n + 1
         if (li >= 0) {
-            const int16_t *lb = q.labels + ((size_t)d.seg_class[n0] * q.nlabel + li) * S;
+            const int16_t *lb = t0.lb;
             for (int s = tid; s < S; s += RGN_NT) lab[cur][s] = lb[s];
         }
         double logp = logp0;
         for (int n = n0 - 1; n >= n0 - wl && n >= 0 && d.tclass[n] >= 0 && !failed && logp > -INFINITY; n--) {
-            const int tc = d.tclass[n], bs = d.brk_slot[n];
-            const int cls = d.seg_class[n];
+            const auto [wb, Wt, pd] = rgn_adj(d, r, n, use_wb);
             const double *fa = d.fa + rs_off(d, r, n);
-            const uint8_t *mk = (mi >= 0 && (!q.constrain || q.constrain[n])) ? q.masks + ((size_t)cls * q.nmask + mi) * S : nullptr;
-            const int16_t *lb = li >= 0 ? q.labels + ((size_t)cls * q.nlabel + li) * S : nullptr;
+            const auto [mk, lb] = rgn_tabs(d, q, n, mi, li);
             const int16_t *lab1 = lab[cur];
             int16_t *lab0 = lab[cur ^ 1];
             for (int s = tid; s < S; s += RGN_NT) {
@@ -6381,22 +6390,9 @@ __global__ __launch_bounds__(RGN_NT) void k_region_extent(Dev d, int r0, int use
                 if (lb) lab0[s] = lb[s];
             }
             __syncthreads();
-            if (bs < 0 && use_wb) {
-                const double *Wt = d.Wb + (size_t)tc * S * S;
+            if (wb) {
                 // the states s' with g(s') > 0, in state order
-                if (tid < 64) {
-                    int cnt = 0;
-                    for (int base = 0; base < S; base += 64) {
-                        const int s = base + lane;
-                        const bool act = s < S && g[s] > 0.;
-                        const unsigned long long m = __ballot(act);
-                        if (act) idx[cnt + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = (int16_t)s;
-                        cnt += __builtin_popcountll(m);
-                    }
-                    if (lane == 0) nact = cnt;
-                }
-                __syncthreads();
-                const int na = nact;
+                const int na = rgn_compact(S, idx, nact, [&](int s) { return g[s] > 0.; });
                 // D(s') and h(s') = g(s') / D(s'): 16 lanes per s'
                 for (int j0 = 0; j0 < na; j0 += RGN_NT / RGN_GL) {
                     const int j = j0 + grp;
@@ -6430,17 +6426,12 @@ __global__ __launch_bounds__(RGN_NT) void k_region_extent(Dev d, int r0, int use
                     g[s] = acc;
                 }
             } else {
-                const double *pd = bs >= 0 ? d.pd_lt + ((size_t)r * d.NBE + bs) * d.M * d.D : nullptr;
                 // D(s') and h(s'): the thread owns s'
                 for (int sp = tid; sp < S; sp += RGN_NT) {
                     const double gv = g[sp];
                     double hv = 0.;
                     if (gv > 0.) {
-                        double D = 0.;
-                        for (int s = 0; s < S; s++) {
-                            const double f = fas[s];
-                            if (f != 0.) D = fma(f, exp(trans_value(d, n, s, sp, pd)), D);
-                        }
+                        const double D = rgn_D_exp(d, n, sp, fas, pd);
                         if (!(D > 0. && D < INFINITY)) s_bad = 1;
                         hv = gv / D;
                     }
@@ -6467,12 +6458,8 @@ __global__ __launch_bounds__(RGN_NT) void k_region_extent(Dev d, int r0, int use
             double part = 0.;
             for (int s = tid; s < S; s += RGN_NT) part += g[s];
             const double Z = rgn_block_sum(part, red);
-            if (s_bad || !(Z >= 0. && Z < INFINITY)) failed = true;
-            else if (Z == 0.) logp = -INFINITY;
-            else {
-                logp += log(Z);
+            if (rgn_take_sum(Z, s_bad != 0, logp, failed))
                 for (int s = tid; s < S; s += RGN_NT) g[s] = g[s] / Z;
-            }
             if (!failed && logp > -INFINITY) {
                 nleft++;
                 if (tid == 0) orow[wl - nleft] = logp;
@@ -6485,9 +6472,7 @@ __global__ __launch_bounds__(RGN_NT) void k_region_extent(Dev d, int r0, int use
         int cur = 0;              // lab[cur]: the labels of segment n
         __syncthreads();
         {
-            const int cls = d.seg_class[n0];
-            const uint8_t *mk = (mi >= 0 && (!q.constrain || q.constrain[n0])) ? q.masks + ((size_t)cls * q.nmask + mi) * S : nullptr;
-            const int16_t *lb = li >= 0 ? q.labels + ((size_t)cls * q.nlabel + li) * S : nullptr;
+            const auto [mk, lb] = t0;
             for (int s = tid; s < S; s += RGN_NT) {
                 g[s] = (!mk || mk[s]) ? 1. : 0.;
                 if (lb) lab[cur][s] = lb[s];
@@ -6495,12 +6480,10 @@ __global__ __launch_bounds__(RGN_NT) void k_region_extent(Dev d, int r0, int use
         }
         double logp = logp0 > -INFINITY ? 0. : -INFINITY;       // the logarithms of the maxima U was divided by so far
         for (int n = n0; n < n0 + wr && n + 1 < N && d.tclass[n] >= 0 && !failed && logp > -INFINITY; n++) {
-            const int tc = d.tclass[n], bs = d.brk_slot[n];
-            const int cls1 = d.seg_class[n + 1];
+            const auto [wb, Wt, pd] = rgn_adj(d, r, n, use_wb);
             const double *fa = d.fa + rs_off(d, r, n);
             const double *post1 = d.post + rs_off(d, r, n + 1);
-            const uint8_t *mk1 = (mi >= 0 && (!q.constrain || q.constrain[n + 1])) ? q.masks + ((size_t)cls1 * q.nmask + mi) * S : nullptr;
-            const int16_t *lb1 = li >= 0 ? q.labels + ((size_t)cls1 * q.nlabel + li) * S : nullptr;
+            const auto [mk1, lb1] = rgn_tabs(d, q, n + 1, mi, li);
             const int16_t *lab0 = lab[cur];
             int16_t *lab1 = lab[cur ^ 1];
             __syncthreads();
@@ -6511,8 +6494,7 @@ __global__ __launch_bounds__(RGN_NT) void k_region_extent(Dev d, int r0, int use
                 if (lb1) lab1[s] = lb1[s];
             }
             __syncthreads();
-            if (bs < 0 && use_wb) {
-                const double *Wt = d.Wb + (size_t)tc * S * S;
+            if (wb) {
                 // num(s') and D(s') from one read of row s': 16 lanes per s'
                 for (int j0 = 0; j0 < S; j0 += RGN_NT / RGN_GL) {
                     const int sp = j0 + grp;
@@ -6538,7 +6520,6 @@ __global__ __launch_bounds__(RGN_NT) void k_region_extent(Dev d, int r0, int use
                     }
                 }
             } else {
-                const double *pd = bs >= 0 ? d.pd_lt + ((size_t)r * d.NBE + bs) * d.M * d.D : nullptr;
                 // num(s') and D(s'): the thread owns s'
                 for (int sp = tid; sp < S; sp += RGN_NT) {
                     double u = 0.;

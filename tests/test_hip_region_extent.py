@@ -110,7 +110,9 @@ def test_against_twin(hip, cases, N, M, max_cn):
 
 @pytest.mark.parametrize('N,M,max_cn', GRIDS)
 def test_against_region_prob(hip, cases, N, M, max_cn):
-    """Every slot against k_region_prob on the same interval."""
+    """Every slot against k_region_prob on the same interval.  The left walk runs k_region_prob's start and step with the
+    same sums in the same order: where the mask binds at the anchor (both then start from the same log Z) the left slots
+    are equal to the last bit."""
     case = cases[(N, M, max_cn)]
     got = _raw(case, case.anchors)[0]
     want = np.full(got.shape, -np.inf)
@@ -125,6 +127,12 @@ def test_against_region_prob(hip, cases, N, M, max_cn):
     for (i, k), row in zip(where, lp):
         want[i, :, k] = row
     _check_rows(got, want, 'S %d against k_region_prob' % case.S)
+    bound = [(i, j) for i, n0 in enumerate(case.anchors) if case.constrain[n0] for j, (mk, lb) in enumerate(CONSTRAINTS) if mk is not None]
+    assert bound
+    for i, j in bound:
+        left = (got[i, j, :W], want[i, j, :W])
+        print('anchor %d constraint %s: %d left slots differ from k_region_prob' % (case.anchors[i], CONSTRAINTS[j], (left[0] != left[1]).sum()))
+        assert np.array_equal(*left), (case.anchors[i], CONSTRAINTS[j], left)
 
 
 @pytest.mark.parametrize('N,M,max_cn', GRIDS)

@@ -1,0 +1,100 @@
+"""The raw outputs of the posterior queries on seeded scenarios, for comparing two builds of the library to the last bit:
+sample_states, posterior_summary_raw, region_logprob_raw, region_counts_raw (1, 5 and 16 bins), call_logprob_raw,
+region_moments_raw (nf 1 and 4) and region_extent_raw, each with and without a constrain vector that leaves segments unbound.
+Scenarios: the three grids of tests/test_hip_sample_cn.py (60, 40 and 24 segments at 165, 355 and 457 states) and 16 segments at
+max_copy_number 16 (more than 512 states: the <16> instantiations), three chains, four restarts after two sweeps, restarts 1 and 2
+with their snapshot retaken under the other transition model (exp(trans_value) on plain adjacencies too).  Queries: a segment, a
+pair, every whole chain, a run from a chain start and one to a chain end, a pair across every kind of adjacency the scenario has;
+anchors at a chain's first, middle and last segment and on both sides of a breakend adjacency.
+Usage: python tools/query_bits.py OUT.npz            (RMX_LIB_PATH selects the library, one fresh process per library)
+       python tools/query_bits.py --compare A.npz B.npz   (np.array_equal(equal_nan=True) per array; exit status 1 if one differs)"""
+import sys, os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+GRIDS = [(60, 3, 8), (40, 3, 12), (24, 4, 6), (16, 3, 16)]
+R = 4
+CONSTRAINTS = ((-1, -1), (1, -1), (-1, 1), (5, 2), (0, 0))       # (mask, label) indices
+
+
+def compare(fa, fb):
+    a, b = np.load(fa), np.load(fb)
+    same = sorted(a.files) == sorted(b.files)
+    if not same:
+        print('different arrays: %s' % sorted(set(a.files) ^ set(b.files)))
+    for k in sorted(set(a.files) & set(b.files)):
+        eq = a[k].shape == b[k].shape and a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k], equal_nan=a[k].dtype.kind == 'f')
+        fin = int(np.isfinite(a[k]).sum()) if a[k].dtype.kind == 'f' else a[k].size
+        print('%-28s %-18s %7d finite or integer entries: %s' % (k, a[k].shape, fin, 'equal' if eq else 'DIFFERS'))
+        same = same and eq
+    print('every array equal' if same else 'NOT EQUAL')
+    return 0 if same else 1
+
+
+def scenario(N, M, max_cn, out):
+    from remixt_amd import posteriors, synthetic
+    from remixt_amd.restarts import RestartSet
+    e = synthetic.make_experiment(N, num_clones=M, max_copy_number=max_cn, num_chains=3, seed=0)
+    ps = synthetic.make_init_params(e, R, max_cn, num_clones=M)
+    fr = (0.6, 0.4) if M == 3 else (0.5, 0.3, 0.2)
+    hs = [np.array([p['h_normal']] + [p['h_tumour'] * f for f in fr]) for p in ps]
+    rs = RestartSet(e, ps, max_cn, num_clones=M, quiet=True, seeds=list(range(R)), h_init=hs)
+    try:
+        b, m = rs.batch, rs.models[0]
+        # the sweeps run on the total read counts alone: a state and its allele swap tie, so probabilities are not all 0 or 1
+        for r in range(R):
+            b.set_array(r, 'allele_likelihood_mask', np.zeros(b.num_segments, dtype=np.int64))
+        rs.variational_update(2)
+        b.transition_model = 1
+        b.update_p_cn(1, 3)
+        N1, S = b.num_segments, b.num_cn_states
+        masks, labels = posteriors.event_tables(b.cn_classes)
+        cs, ce = posteriors.chains_from_telomeres(m.is_telomere)
+        bidx = np.asarray(m.breakpoint_idx)
+        inner = np.ones(N1 - 1, dtype=bool); inner[ce[:-1]] = False
+        plain, be = np.flatnonzero(inner & (bidx[:-1] < 0)), np.flatnonzero(inner & (bidx[:-1] >= 0))
+        c = int(np.argmax(ce - cs))
+        mid = int((cs[c] + ce[c]) // 2)
+        runs = [(mid, mid), (mid, min(mid + 1, int(ce[c])))] + [(int(a), int(z)) for a, z in zip(cs, ce)]
+        runs += [(int(cs[1]), int(min(cs[1] + 3, ce[1]))), (int(max(ce[0] - 2, cs[0])), int(ce[0]))]
+        runs += [(int(n), int(n) + 1) for n in list(plain[:1]) + list(be[:2])]
+        anchors = [int(cs[c]), mid, int(ce[c])] + [int(n) + k for n in be[:1] for k in (0, 1)]
+        bound = np.asarray(m.seg_is_original, dtype=bool).copy()
+        bound[2::5] = False
+        qr = np.array([[a, z, mi, li] for a, z in runs for mi, li in CONSTRAINTS], dtype=np.int32)
+        qc = np.array([[a, z, mi, li] for a, z in runs for mi, li in ((-1, 0), (1, 1), (5, 2))], dtype=np.int32)
+        qp = np.array([[a, z, li, 0] for a, z in runs for li in (-1, 0, 1, 2)], dtype=np.int32)
+        qx = np.array([[n0, mi, li, 0] for n0 in anchors for mi, li in CONSTRAINTS], dtype=np.int32)
+        feats = posteriors.moment_features(b.cn_classes)
+        weights = np.stack([np.asarray(m.l1, dtype=float), np.ones(N1)])
+        qm1 = np.array([[a, z, f0, wi] for a, z in runs for f0, wi in ((0, 0), (feats.shape[1] - 1, 1))], dtype=np.int32)
+        qm4 = np.array([[a, z, 0, wi] for a, z in runs for wi in (0, 1)], dtype=np.int32)
+        key = lambda name: 'S%d_%s' % (S, name)
+        out[key('sample_states')] = b.sample_states(0, R, 9, [11, 12, 13, 14])
+        proj, stats, argmax = b.posterior_summary_raw(0, R, weights=np.ascontiguousarray(np.transpose(masks, (0, 2, 1)).astype(float)))
+        out[key('summary_proj')], out[key('summary_stats')], out[key('summary_argmax')] = proj, stats, argmax
+        paths = argmax.astype(np.int16)[:, None]
+        for tag, con in (('all', None), ('unbound', bound)):
+            out[key('region_logprob_' + tag)] = b.region_logprob_raw(0, R, qr, masks, labels, con)
+            for K in (1, 5, 16):
+                out[key('region_counts%d_%s' % (K, tag))] = b.region_counts_raw(0, R, qc, masks, labels, con, K)
+            out[key('call_logprob_' + tag)] = b.call_logprob_raw(0, R, paths, qp, labels, con)
+            out[key('region_extent_' + tag)] = b.region_extent_raw(0, R, qx, masks, labels, con, 6, 6)
+        out[key('region_moments1')] = b.region_moments_raw(0, R, qm1, feats, weights, 1)
+        out[key('region_moments4')] = b.region_moments_raw(0, R, qm4, feats, weights, 4)
+        print('%d states, %d model segments, %d chains, %d plain and %d breakend adjacencies, %d runs, %d anchors, %d of %d segments unbound' % (
+            S, N1, len(cs), len(plain), len(be), len(runs), len(anchors), (~bound).sum(), N1), flush=True)
+    finally:
+        rs.close()
+
+
+if __name__ == '__main__':
+    if len(sys.argv) == 4 and sys.argv[1] == '--compare':
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    if len(sys.argv) != 2:
+        sys.exit(__doc__)
+    out = {}
+    for N, M, max_cn in GRIDS:
+        scenario(N, M, max_cn, out)
+    np.savez(sys.argv[1], **out)
+    print('%d arrays -> %s' % (len(out), sys.argv[1]))

@@ -457,6 +457,23 @@ int rmx_region_moments(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const i
 int rmx_region_extent(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
                       int32_t nlabel, const int16_t *labels, const uint8_t *constrain, int32_t wl, int32_t wr, double *logp_out);
 
+/* Region event spans: the joint law of where an event of rmx_region_prob begins and ends around an anchor segment, and so of
+ * its length.  Query i = (anchor n0, mask index or -1, label index or -1, 0); with the event E of rmx_region_prob,
+ *   logp_out[r][i][a][c] = log P(E on [n0 - a, n0 + c]),   a = 0 .. wl,   c = 0 .. wr.
+ * Entry (0, 0) is the event at the anchor alone; row 0 is the right half of rmx_region_extent and column 0 its left half,
+ * mirrored.  An entry whose interval leaves the anchor's chain or [0, N) is -inf (a run cannot pass a chain end), as is an
+ * impossible event.  The table does not increase in a or in c.  The model is not modified.
+ *   masks, labels, constrain   as rmx_region_prob
+ *   wl, wr    window widths to the left and right of the anchor, >= 0, (wl + 1) (wr + 1) <= 16384
+ * An entry is bit-identical in any restart range, any batch of queries and any (wl, wr) that covers it.
+ * RMX_EARG, with nothing launched and logp_out untouched: a bad range, nq < 1, an anchor outside [0, N), a mask or label
+ * index out of range, a non-zero fourth field, wl or wr < 0, (wl + 1) (wr + 1) > 16384.  RMX_EVALUE with the restarts listed: a
+ * restart has had no update_p_cn.  RMX_EASSERT with the restarts listed: a backward step met a zero or non-finite
+ * normaliser under a column with mass, or a column sum that is not a finite number >= 0 (every entry of that query is NaN).
+ * RMX_EUNSUPPORTED: more than 1024 states. */
+int rmx_region_span(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
+                    int32_t nlabel, const int16_t *labels, const uint8_t *constrain, int32_t wl, int32_t wr, double *logp_out);
+
 /* -- module-level functions on caller-supplied dense inputs ----------------- */
 /* sum_product (:1213-1246): f [N][S], T [N-1][S][S] -> alphas, betas [N][S] */
 int rmx_sum_product(const double *f, const double *T, double *alphas, double *betas,

@@ -36,6 +36,7 @@ def fit(experiment, init_params, config, device=0, quiet=False, init_id=0):
     call_conf = posteriors.call_confidence_on(config)
     moments = posteriors.region_moments_on(config)
     extents = posteriors.extents_on(config, len(experiment.x))
+    lengths = posteriors.lengths_on(config, len(experiment.x))
     h_init = np.array([
         init_params['h_normal'],
         init_params['h_tumour'] * init_params['mix_frac'],
@@ -85,6 +86,10 @@ def fit(experiment, init_params, config, device=0, quiet=False, init_id=0):
         names, anchors, events, window = extents
         one = posteriors.grouped_event_extents(lambda a, ev, w: [model.event_extent(a, ev, w)], anchors, events, window)
         posteriors.add_event_extents(res, names, one[0])
+    if lengths is not None:
+        names, anchors, events, window, edges = lengths
+        one = posteriors.grouped_event_spans(lambda a, ev, w: [model.event_span(a, ev, w)], anchors, events, window, edges)
+        posteriors.add_event_lengths(res, names, one[0])
     return res
 
 
@@ -117,6 +122,7 @@ def fit_restarts(experiment, init_params_by_id, config, device=0, quiet=True, se
     call_conf = posteriors.call_confidence_on(config)
     moments = posteriors.region_moments_on(config)
     posteriors.extents_on(config, len(experiment.x))
+    lengths = posteriors.lengths_on(config, len(experiment.x))
     ids = sorted(init_params_by_id)
     params = [init_params_by_id[i] for i in ids]
     max_cn = defaults.get_param(config, 'max_copy_number')
@@ -130,7 +136,8 @@ def fit_restarts(experiment, init_params_by_id, config, device=0, quiet=True, se
     rs.fit(defaults.get_param(config, 'num_em_iter'), defaults.get_param(config, 'num_update_iter'))
     results = add_optional_outputs(rs, rs.results(), experiment, ids, defaults.get_param(config, 'num_cn_samples'), defaults.get_param(config, 'cn_sample_seed'),
                                    defaults.get_param(config, 'cn_posterior_summary'), defaults.get_param(config, 'cn_regions'), bins, call_conf, moments,
-                                   defaults.get_param(config, 'cn_event_extents'), defaults.get_param(config, 'cn_extent_window'))
+                                   defaults.get_param(config, 'cn_event_extents'), defaults.get_param(config, 'cn_extent_window'),
+                                   lengths is not None, () if lengths is None else lengths[4])
     out = dict(zip(ids, results))
     rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     return out
@@ -294,6 +301,13 @@ def store_fit_results(store, experiment, fit_results, key_prefix):
         store[key_prefix + '/extent_names'] = pd.Series(list(ext['names']))
         for k in posteriors.EXTENT_ARRAYS:
             store[key_prefix + '/extent_' + k] = pd.Series(np.asarray(ext[k]))
+    if 'event_lengths' in fit_results:            # (config cn_event_lengths)
+        ln = fit_results['event_lengths']
+        store[key_prefix + '/span_names'] = pd.Series(list(ln['names']))
+        for k in posteriors.SPAN_ARRAYS:
+            store[key_prefix + '/span_' + k] = pd.Series(np.asarray(ln[k]))
+        for k in posteriors.SPAN_EDGE_ARRAYS:
+            store[key_prefix + '/span_' + k] = pd.DataFrame(np.asarray(ln[k]))
 
 
 def store_optimal_solution(stats, store, config):

@@ -714,6 +714,24 @@ class RemixtBatch(object):
         self._ck(self._lib.rmx_region_extent(self._handle, r0, nr, *args, wl, wr, obuf.ctypes.data_as(_dp)))
         return out
 
+    def region_span_raw(self, r0, nr, queries, masks=None, labels=None, constrain=None, wl=0, wr=0):
+        """log-probabilities (nr, nq, wl + 1, wr + 1) of an event of region_logprob_raw over every interval around an anchor,
+        under the structured posterior of the last update_p_cn of restarts r0 .. r0+nr-1 (rmx_region_span): the joint law of
+        the event's two ends.  queries, masks, labels and constrain as region_extent_raw.  Entry (a, c) of a query with anchor
+        n0 is the log-probability of the event over model segments [n0 - a, n0 + c]: entry (0, 0) is the event at the anchor
+        alone, row 0 and column 0 are the two halves of region_extent_raw, and the table does not increase in a or in c.
+        -inf for an interval that leaves the anchor's chain and for an impossible event.  wl, wr >= 0,
+        (wl + 1) (wr + 1) <= 16384."""
+        r0, nr, wl, wr = int(r0), int(nr), int(wl), int(wr)
+        q, args, _keep = self._region_args(queries, masks, labels, constrain)
+        if not (-2 ** 31 <= wl < 2 ** 31 and -2 ** 31 <= wr < 2 ** 31):
+            raise ValueError('window width out of range')
+        ok = wl >= 0 and wr >= 0 and (wl + 1) * (wr + 1) <= 16384
+        out = np.zeros((max(nr, 0), q.shape[0]) + ((wl + 1, wr + 1) if ok else (1, 1)), dtype=np.float64)
+        obuf = out if out.size else np.zeros(1)
+        self._ck(self._lib.rmx_region_span(self._handle, r0, nr, *args, wl, wr, obuf.ctypes.data_as(_dp)))
+        return out
+
     # -- measurement ------------------------------------------------------------
     def timer_start(self):
         self._ck(self._lib.rmx_timer_start(self._handle))
@@ -952,6 +970,10 @@ class RemixtModel(object):
     def region_extent(self, queries, masks=None, labels=None, constrain=None, wl=0, wr=0):
         """RemixtBatch.region_extent_raw of this model: log-probabilities (nq, wl + wr + 1)."""
         return self._batch.region_extent_raw(self._r, 1, queries, masks, labels, constrain, wl, wr)[0]
+
+    def region_span(self, queries, masks=None, labels=None, constrain=None, wl=0, wr=0):
+        """RemixtBatch.region_span_raw of this model: log-probabilities (nq, wl + 1, wr + 1)."""
+        return self._batch.region_span_raw(self._r, 1, queries, masks, labels, constrain, wl, wr)[0]
 
     def call_logprob(self, paths, queries, labels=None, constrain=None):
         """RemixtBatch.call_logprob_raw of this model: paths (npaths, N) -> log-probabilities (nq,)."""

@@ -791,6 +791,18 @@ class BreakpointModel(object):
         return posteriors.batch_event_extents(self.model._batch, self.model._r, 1, anchors, event, window, self.seg_fwd_remap,
                                               self.seg_is_original, self.is_telomere)[0]
 
+    def event_span(self, anchors, event, window=64):
+        """The joint law of where a copy-number event begins and ends around anchor segments, and so of its length, exactly,
+        under the structured posterior of the last variational update; anchors, event and window as event_extent (the
+        window's table may hold at most 16 384 entries).  A list with one posteriors.span_summary dict per anchor: p_event,
+        the joint survival function and pmf of (left end, right end), the length of every cell in the units of the segment
+        lengths, the 5 / 50 / 95 % quantiles of the length and its distribution function."""
+        from . import posteriors
+        if not hasattr(self.model, 'region_span'):
+            raise NotImplementedError('kernel module %s has no event spans' % getattr(self._kernel_module(), '__name__', '?'))
+        return posteriors.batch_event_spans(self.model._batch, self.model._r, 1, anchors, event, window, self.seg_fwd_remap,
+                                            self.seg_is_original, self.is_telomere, self.l1)[0]
+
     def ploidy_posterior_sd(self):
         """The exact posterior SD of the tumour ploidy whose mean is stats['ploidy_posterior_mean']: the whole genome as one
         region of region_cn_moments (posteriors.moment_stats)."""

@@ -40,12 +40,14 @@ static inline long long now_ns() { return std::chrono::duration_cast<std::chrono
 enum KernelId {
     KID_STATE_TABLES = 0, KID_SEG_CONST, KID_FRAMELOGPROB, KID_FB, KID_MARGINALS, KID_MARGINALS_AB, KID_OUTLIER_TOTAL,
     KID_OUTLIER_ALLELE, KID_ALLELE_SWAP, KID_BRK_LUT, KID_PAIRWISE, KID_BRK_UPDATE, KID_ELBO_SEG, KID_ELBO_FINAL,
-    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_POST_SUMMARY, KID_REGION, KID_REGION_COUNTS, KID_CALL_PROB, KID_REGION_MOMENTS, KID_REGION_EXTENT, KID_COUNT
+    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_POST_SUMMARY, KID_REGION, KID_REGION_COUNTS, KID_CALL_PROB, KID_REGION_MOMENTS, KID_REGION_EXTENT, KID_REGION_SPAN, KID_COUNT
 };
 static const char *kKernelNames[KID_COUNT] = {
     "k_state_tables", "k_seg_const", "k_framelogprob", "k_fb", "k_marginals<true>", "k_marginals<false>", "k_update_outlier_total",
     "k_update_outlier_allele", "k_update_allele_swap", "k_brk_lut", "k_pairwise", "k_brk_update", "k_elbo_seg", "k_elbo_final",
-    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn", "k_posterior_summary", "k_region_prob", "k_region_counts", "k_call_prob", "k_region_moments", "k_region_extent"};
+    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn", "k_posterior_summary", "k_region_prob", "k_region_counts", "k_call_prob", "k_region_moments", "k_region_extent", "k_region_span"};
+// (ids are appended, never reordered: profiles written by earlier builds keep their meaning.  Before k_region_span the two lists ended
+//  `KID_REGION_MOMENTS, KID_REGION_EXTENT, KID_COUNT` and `"k_region_moments", "k_region_extent"};`, which tests/test_region_extent_cpu.py pins)
 
 struct ProfRec { int id; hipEvent_t a, b; };
 
@@ -3327,6 +3329,46 @@ int rmx_region_extent(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const in
         ra.queries = dq; ra.nq = nqc;
         hipLaunchKernelGGL(k_region_extent, dim3((unsigned)nqc, n), dim3(RGN_NT), 0, b->stream, dv, r, use_wb, ra, (int)wl, (int)wr, out, flags);
     });
+}
+
+// Region event spans (k_region_span): for every (restart, query) the table of rmx_region_prob's event over every interval
+// [n0 - a, n0 + c] around an anchor, (wl + 1) (wr + 1) entries from one walk per group of 16 right ends.  The checks are
+// rmx_region_extent's with the window rule of a table; tables, staging and chunking are rmx_region_prob's.  One workgroup computes
+// a (restart, query, column group) on its own and a column does not depend on its neighbours, so an entry depends on neither
+// the restart range, the chunking nor the window.  A failed workgroup leaves NaN in its own columns; the query's other groups
+// are set to NaN here, after the call.
+int rmx_region_span(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
+                    int32_t nlabel, const int16_t *labels, const uint8_t *constrain, int32_t wl, int32_t wr, double *logp_out) { BIND(b);
+    int rc;
+    if ((rc = check_region_call(b, "region_span", r0, nr, nq, queries, logp_out))) return rc;
+    if ((rc = check_mask_label_tables("region_span", nmask, masks, nlabel, labels))) return rc;
+    if (!rmxh::span_window_ok(wl, wr, RGS_MAXPER)) return fail(RMX_EARG, "region_span: the window needs wl, wr >= 0 and (wl + 1) (wr + 1) <= 16384");
+    const int N = b->d.N;
+    if (b->d.S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "region_span: more than 1024 states");
+    for (int i = 0; i < nq; i++) {
+        const int32_t *qq = queries + 4 * (size_t)i;
+        if (qq[0] < 0 || qq[0] >= N) return fail(RMX_EARG, "region_span: a query needs an anchor in [0, num_segments)");
+        if (qq[1] < -1 || qq[1] >= nmask) return fail(RMX_EARG, "region_span: mask index out of range");
+        if (qq[2] < -1 || qq[2] >= nlabel) return fail(RMX_EARG, "region_span: label index out of range");
+        if (qq[3] != 0) return fail(RMX_EARG, "region_span: the fourth field of a query must be 0");
+    }
+    if ((rc = require_snapshot(b, r0, nr, "region_span"))) return rc;
+    RgnArgs ra;
+    if ((rc = stage_region_tables(b, nmask, masks, nlabel, labels, constrain, &ra))) return rc;
+    const size_t lds = rgs_lds_bytes(b->d.S);
+    const int tpw = tiles_per_wave(b->d.S);
+    auto kf = tpw == 3 ? k_region_span<3> : (tpw == 8 ? k_region_span<8> : k_region_span<16>);
+    if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int ng = wr / RGN_KB + 1;
+    const size_t per = ((size_t)wl + 1) * ((size_t)wr + 1);
+    rc = run_queries(b, r0, nr, nq, queries, (int)per, KID_REGION_SPAN, "region_span: a backward step has a zero or non-finite normaliser", logp_out,
+                     [&](const Dev &dv, int r, int n, int, int use_wb, const int32_t *dq, int nqc, double *out, uint32_t *flags) {
+        ra.queries = dq; ra.nq = nqc;
+        hipLaunchKernelGGL(kf, dim3((unsigned)nqc * (unsigned)ng, n), dim3(RGN_NT), lds, b->stream, dv, r, use_wb, ra, (int)wl, (int)wr, out, flags);
+    });
+    // a failed query is NaN in every entry, not only in the columns of the group that failed
+    if (rc == RMX_EASSERT) rmxh::span_spread_nan(logp_out, r0, nr, nq, per, g_err_restarts.data(), (int32_t)g_err_restarts.size());
+    return rc;
 }
 
 // ---- module-level functions -------------------------------------------------------------------

@@ -2,6 +2,7 @@
 // suite can compile them with gcc -fsanitize=address,undefined (tests/csrc/host_sanitize.cpp, tests/test_sanitizers_cpu.py):
 //   compress_cn_states   rmx_compress_cn_states: dense (N,S,M,2) int64 state array -> class tables + class id per segment
 //   lt_classes           the total-copy classes of the state tables (compact read-depth planes of the cell cache)
+//   span_window_ok, span_spread_nan  rmx_region_span: the window rule of a table, and NaN in every entry of a failed query
 //   weighted_search      rmx_weighted_search: numpy's cumsum / searchsorted(side='right') for the weighted M-step samples
 //                        (reference remixt/cn_model.py:475-480)
 //   weighted_sample_round  rmx_weighted_sample_round: a whole round of that sampling from a strided weight column
@@ -24,6 +25,29 @@
 #endif
 
 namespace rmxh {
+
+// rmx_region_span's window rule: wl, wr >= 0 and a table of (wl + 1) (wr + 1) <= max_entries entries (no overflow for any int32 pair)
+inline bool span_window_ok(int32_t wl, int32_t wr, int64_t max_entries) {
+    return wl >= 0 && wr >= 0 && ((int64_t)wl + 1) * ((int64_t)wr + 1) <= max_entries;
+}
+// rmx_region_span after a failed call: out is [nr][nq][per]; in every restart of `restarts` (absolute indices; the ones outside
+// [r0, r0 + nr) are skipped) a query with a NaN in any entry becomes NaN in every entry -- a workgroup that fails leaves NaN in the
+// columns of its own group only.  Returns the number of queries it filled.
+inline int64_t span_spread_nan(double *out, int32_t r0, int32_t nr, int32_t nq, size_t per, const int32_t *restarts, int32_t nrestarts) {
+    int64_t filled = 0;
+    if (!out || !restarts) return filled;
+    for (int32_t k = 0; k < nrestarts; k++) {
+        const int64_t ri = (int64_t)restarts[k] - r0;
+        if (ri < 0 || ri >= nr) continue;
+        for (int32_t i = 0; i < nq; i++) {
+            double *t = out + ((size_t)ri * nq + i) * per;
+            bool bad = false;
+            for (size_t e = 0; e < per && !bad; e++) bad = std::isnan(t[e]);
+            if (bad) { std::fill(t, t + per, std::nan("")); filled++; }
+        }
+    }
+    return filled;
+}
 
 inline int compress_cn_states(const int64_t *cn_states, int32_t N, int32_t S, int32_t M, int32_t max_classes,
                               int32_t *seg_class_out, int64_t *classes_out, int32_t *num_classes) {

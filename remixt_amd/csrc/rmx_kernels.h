@@ -6578,3 +6578,248 @@ __global__ __launch_bounds__(RGN_NT) void k_region_extent(Dev d, int r0, int use
         for (int k = wl + nright + 1 + tid; k < per; k += RGN_NT) orow[k] = -INFINITY;
     }
 }
+
+// =============================================================================
+// Region event spans: for a query (anchor n0, mask, label) and window widths wl, wr, the whole table
+//   out[a][c] = log P(E on [n0 - a, n0 + c]),   a = 0 .. wl,   c = 0 .. wr,
+// of k_region_prob's event E: the joint survival function of the event's two ends, where k_region_extent gives the two
+// marginal curves (its right half is row 0, its left half column 0).  Entries whose interval leaves the anchor's chain or
+// [0, N) are -inf.  It is k_region_prob's backward g recursion with one column per right end j = n0 + c: column j starts at
+// segment j with g_j(s) = [s in A_j] post_j(s) and is walked left; its step sum at every n <= n0 is entry (n0 - n, j - n0).
+// All columns cross the same adjacencies, so they ride in the 16 columns of the FP64 matrix instruction's B operand and
+// share one read of the S x S weights per pass -- k_region_counts' shape with 16 right ends where that kernel has 16 bins.
+// One workgroup of 256 threads per (restart, query, column group); group gi holds the right offsets 16 gi .. 16 gi + 15 and
+// walks n from min(n0 + min(wr, 16 gi + 15), chain end) down to max(n0 - wl, chain start) (it finds the chain ends itself,
+// from tclass).  Arriving at a segment n >= n0 + 16 gi it starts that column; at every n <= n0 it writes the 16 columns'
+// values.  G lives in LDS as [S rounded up to 16][16 columns]; a step n + 1 -> n is
+//   1. the states s' with fa_n+1(s') != 0 or post_n+1(s') != 0 compacted in state order by a ballot (G_n+1(s', .) is 0
+//      elsewhere by the selects below) -- k_region_moments' set: it does not depend on the columns;
+//   2. D(s') for those, as in k_region_counts; a column with G(s') != 0 is divided by D(s') in place;
+//   3. G_n on v_mfma_f64_16x16x4_f64 in row tiles of 16 states, the tiles round robin over the four waves, one instruction
+//      per (tile, four s'): A[i = lane & 15][k = lane >> 4] = W(s0 + i, s'_k) selected (never multiplied) to 0 off-label, on a
+//      masked row and for s >= S, B[k][j = lane & 15] = G(s'_k, j) / D(s'_k), D row (lane >> 4) + 4 reg, column lane & 15;
+//   4. [fa_n(s) != 0] fa_n(s) times the accumulators, each column's sum from the registers (16-lane groups, then the four
+//      waves, in that order), and G written divided by its column's sum; the logarithm goes to the column's accumulator.
+// Every column is scaled on its own and the compacted set is not chosen from the columns, so a column does not depend on
+// its neighbours: an entry is bit-identical in any restart range, any batch of queries and any (wl, wr) that covers it
+// (group boundaries depend on n0 and gi only).  Every sum has one order, fixed by S alone.  Only columns s < S of fa / post
+// are read (clamped address and select).  The label is optional.  A D(s') that is 0 or not finite under a column with mass,
+// or a column sum that is not a finite number >= 0, sets RGN_ERR_DENOM in flags[r] and gives NaN in every entry of the
+// workgroup (the host extends it to the query's other groups); a column sum of exactly 0 gives -inf from there on.
+// grid (queries * groups, restarts), groups = wr / 16 + 1, block RGN_NT, dynamic LDS rgs_lds_bytes(S);
+// out[((ri * nq + query) * (wl + 1) + a) * (wr + 1) + c].
+// =============================================================================
+#define RGS_MAXPER 16384      // entries of a query: (wl + 1) (wr + 1)
+static inline size_t rgs_lds_bytes(int S) { const size_t SR = ((size_t)S + 15) & ~(size_t)15; return SR * (RGN_KB * 8 + 8 + 8 + 3 * 2); }
+// the smallest lo and the largest hi over the workgroup; every thread gets them
+__device__ inline void rgs_block_min_max(int &lo, int &hi, int (*ired)[RGN_NW]) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { lo = min(lo, __shfl_xor(lo, o, 64)); hi = max(hi, __shfl_xor(hi, o, 64)); }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { ired[0][threadIdx.x >> 6] = lo; ired[1][threadIdx.x >> 6] = hi; }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < RGN_NW; i++) { lo = min(lo, ired[0][i]); hi = max(hi, ired[1][i]); }
+}
+// (the 8-tile form takes 273 registers, one workgroup per CU where k_region_counts<8> has two; asked for two waves per SIMD with
+// amdgpu_waves_per_eu it spilled ten registers to scratch, so the hint is not here)
+template <int TPW>
+__global__ __launch_bounds__(RGN_NT) void k_region_span(Dev d, int r0, int use_wb, RgnArgs q, int wl, int wr, double *out, uint32_t *flags) {
+    extern __shared__ double rgs_lds[];                 // G [SR][16], fas [SR], pst [SR], lab [2][SR] (int16), idx [SR] (int16)
+    __shared__ double red[RGN_NW], redc[RGN_NW][RGN_KB];
+    __shared__ int ired[2][RGN_NW];
+    __shared__ int nact, s_bad;
+    const int ng = wr / RGN_KB + 1;
+    const int qi = blockIdx.x / ng, gi = blockIdx.x % ng, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (uniform, and known to be: the matrix instructions sit under conditions on it)
+    const int grp = tid / RGN_GL, gl = tid % RGN_GL;
+    const int ai = lane & 15, kk = lane >> 4;
+    const int S = d.S, N = d.N, SR = (S + 15) & ~15;
+    double *G = rgs_lds, *fas = G + (size_t)SR * RGN_KB, *pst = fas + SR;
+    int16_t *labs = (int16_t *)(pst + SR), *idx = labs + 2 * SR;
+    const int n0 = q.queries[4 * qi], mi = q.queries[4 * qi + 1], li = q.queries[4 * qi + 2];
+    const int c0 = gi * RGN_KB;                          // the group's first right offset
+    const int ncol = min(RGN_KB, wr - c0 + 1);           // its columns inside the window
+    const size_t W1 = (size_t)wr + 1;
+    double *otab = out + ((size_t)ri * q.nq + qi) * ((size_t)wl + 1) * W1 + c0;       // entry (a, c0 + j): otab[a * W1 + j]
+    if (tid == 0) s_bad = 0;
+    for (int e = tid; e < SR * RGN_KB; e += RGN_NT) G[e] = 0.;
+    // ---- where the walk begins and ends: the window, cut at the ends of the anchor's chain ------------------------------
+    int top = n0 + c0 + ncol - 1, lo = n0 - wl;
+    {
+        int ctop = 0x7fffffff, clo = (int)0x80000000;
+        for (int i = tid; i < c0 + ncol - 1; i += RGN_NT) {
+            const int n = n0 + i;
+            if (n + 1 >= N || d.tclass[n] < 0) { ctop = n; break; }         // (n is the last segment of the chain)
+        }
+        for (int i = 1 + tid; i <= wl; i += RGN_NT) {
+            const int n = n0 - i;
+            if (n < 0 || d.tclass[n] < 0) { clo = n + 1; break; }           // (n + 1 is the first segment of the chain)
+        }
+        rgs_block_min_max(ctop, clo, ired);
+        top = min(top, ctop); lo = max(lo, clo);
+    }
+    int cst = 0;              // the lane's column ai: 0 not started, 1 has mass, 2 impossible from here on
+    double logacc = 0.;       // the logarithms of the sums column ai was divided by so far
+    int cur = 0;              // labs[cur * SR ..]: the labels of segment n + 1
+    int adone = -1;           // the last row written
+    for (int n = top; n >= lo && top >= n0 + c0; n--) {
+        const bool step = n < top;
+        const auto [mk, lb] = rgn_tabs(d, q, n, mi, li);
+        const int16_t *lab1 = labs + cur * SR;
+        int16_t *lab0 = labs + (cur ^ 1) * SR;
+        // ---- 1. the states s' with mass, in state order (fas / pst still hold segment n + 1) ---------------------------
+        __syncthreads();      // (G, fas and pst of the segment before are complete)
+        int na = 0;
+        if (step) na = __builtin_amdgcn_readfirstlane(rgn_compact(S, idx, nact, [&](int s) { return fas[s] != 0. || pst[s] != 0.; }));
+        // ---- the rows of segment n; the masked sum of post_n, for the column that starts here -----------------------------
+        double part = 0.;
+        {
+            const double *fa = d.fa + rs_off(d, r, n), *post = d.post + rs_off(d, r, n);
+            for (int s = tid; s < SR; s += RGN_NT) {
+                const int sc = s < S ? s : S - 1;
+                const double fv = fa[sc], pr = post[sc];
+                fas[s] = s < S ? fv : 0.;
+                pst[s] = s < S ? pr : 0.;
+                if (lb) lab0[s] = lb[sc];
+                part += (s < S && (!mk || mk[sc])) ? pr : 0.;
+            }
+        }
+        __syncthreads();
+        if (step) {
+            const auto [wb, Wt, pd] = rgn_adj(d, r, n, use_wb);
+            // ---- 2. D(s') and G / D in place ---------------------------------------------------------------------------
+            if (wb) {
+                for (int j0 = 0; j0 < na; j0 += RGN_NT / RGN_GL) {
+                    const int j = j0 + grp;
+                    const bool ok = j < na;
+                    const int sp = ok ? idx[j] : 0;
+                    double p = 0.;
+                    if (ok) {
+                        const double *wrow = Wt + (size_t)sp * S;
+                        for (int s = gl; s < S; s += RGN_GL) p = fma(fas[s], wrow[s], p);
+                    }
+                    const double D = group_sum(p, RGN_GL);
+                    if (ok) {
+                        const double gv = G[sp * RGN_KB + gl];
+                        if (gv != 0.) {
+                            if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                            G[sp * RGN_KB + gl] = gv / D;
+                        }
+                    }
+                }
+            } else {
+                for (int j = tid; j < na; j += RGN_NT) {
+                    const int sp = idx[j];
+                    bool mass = false;
+                    for (int k = 0; k < RGN_KB; k++) mass = mass || G[sp * RGN_KB + k] != 0.;
+                    if (mass) {
+                        const double D = rgn_D_exp(d, n, sp, fas, pd);
+                        if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                        for (int k = 0; k < RGN_KB; k++) {
+                            const double gv = G[sp * RGN_KB + k];
+                            if (gv != 0.) G[sp * RGN_KB + k] = gv / D;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            // ---- 3. G_n on the matrix cores ------------------------------------------------------------------------------
+            psm_d4 acc[TPW];
+            int rowlab[TPW];      // label of the lane's A row of tile u (0 without a label), or INT_MIN: the row takes nothing (masked, or s >= S)
+#pragma unroll
+            for (int u = 0; u < TPW; u++) {
+                acc[u] = psm_d4{0., 0., 0., 0.};
+                const int s = (wave + RGN_NW * u) * 16 + ai;
+                const int sc = s < S ? s : S - 1;
+                const bool rok = s < S && (!mk || mk[sc]);
+                rowlab[u] = rok ? (lb ? (int)lab0[sc] : 0) : (int)0x80000000;
+            }
+            for (int j0 = 0; j0 < na; j0 += 4) {
+                const int j = j0 + kk;
+                const bool ok = j < na;
+                const int sp = idx[ok ? j : 0];
+                const int lsp = lb ? (int)lab1[sp] : 0;
+                const double hv = G[sp * RGN_KB + ai];
+                const double bv = ok ? hv : 0.;
+#pragma unroll
+                for (int u = 0; u < TPW; u++) {
+                    const int s0 = (wave + RGN_NW * u) * 16;
+                    if (s0 < S) {         // (uniform over the wave)
+                        const int s = s0 + ai, sc = s < S ? s : S - 1;
+                        const bool live = ok && rowlab[u] == lsp;
+                        double wv;
+                        if (wb) wv = Wt[(size_t)sp * S + sc];
+                        else wv = live ? exp(trans_value(d, n, sc, sp, pd)) : 0.;
+                        acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(live ? wv : 0., bv, acc[u], 0, 0, 0);
+                    }
+                }
+            }
+            // ---- 4. [fa != 0] fa(s) and each column's sum, from the registers; the barrier also ends every wave's reads of G / D ----
+            double csum = 0.;
+#pragma unroll
+            for (int u = 0; u < TPW; u++) {
+                const int s0 = (wave + RGN_NW * u) * 16;
+#pragma unroll
+                for (int g = 0; g < 4; g++) {
+                    const int s = s0 + kk + 4 * g;
+                    const double fv = s < SR ? fas[s] : 0.;
+                    const double v = fv != 0. ? fv * acc[u][g] : 0.;
+                    acc[u][g] = v;
+                    csum += v;
+                }
+            }
+            csum += __shfl_xor(csum, 16, 64);
+            csum += __shfl_xor(csum, 32, 64);
+            if (lane < RGN_KB) redc[wave][lane] = csum;
+            __syncthreads();
+            double Z = 0.;
+#pragma unroll
+            for (int i = 0; i < RGN_NW; i++) Z += redc[i][ai];
+            if (cst == 1) {
+                if (!(Z >= 0. && Z < INFINITY)) { s_bad = 1; cst = 2; }
+                else if (Z == 0.) cst = 2;
+                else logacc += log(Z);
+            }
+            const bool lv = cst == 1;
+#pragma unroll
+            for (int u = 0; u < TPW; u++) {
+                const int s0 = (wave + RGN_NW * u) * 16;
+#pragma unroll
+                for (int g = 0; g < 4; g++) {
+                    const int s = s0 + kk + 4 * g;
+                    if (s < SR) G[s * RGN_KB + ai] = lv ? acc[u][g] / Z : 0.;
+                }
+            }
+        }
+        // ---- the column whose right end is n starts: g_n = [mask] post_n, divided by its sum ------------------------------
+        const int jn = n - n0 - c0;
+        if (jn >= 0) {            // (jn < ncol: the walk began at or below the group's last right end)
+            const double Z0 = rgn_block_sum(part, red);         // (its barriers also put step 4's writes of G before the ones below)
+            const bool bad0 = !(Z0 >= 0. && Z0 < INFINITY), ok0 = !bad0 && Z0 > 0.;
+            if (bad0) s_bad = 1;
+            if (ai == jn) { cst = ok0 ? 1 : 2; logacc = ok0 ? log(Z0) : 0.; }
+            for (int s = tid; s < SR; s += RGN_NT) {
+                const int sc = s < S ? s : S - 1;
+                const double pv = pst[s];
+                G[s * RGN_KB + jn] = (ok0 && s < S && (!mk || mk[sc]) && pv != 0.) ? pv / Z0 : 0.;
+            }
+        }
+        // ---- row n0 - n of the table -----------------------------------------------------------------------------------------
+        if (n <= n0) {
+            if (tid < ncol) otab[(size_t)(n0 - n) * W1 + tid] = cst == 1 ? logacc : -INFINITY;       // (tid < 16: column ai == tid)
+            adone = n0 - n;
+        }
+        cur ^= 1;
+        // every column has started and none has mass: the rows below are -inf (the columns' states are the same in every wave)
+        if (n <= n0 + c0 && __ballot(cst == 1) == 0ull) break;
+    }
+    // ---- the rows no step reached (-inf), or NaN in every entry of a failed workgroup --------------------------------------
+    __syncthreads();
+    const bool failed = s_bad != 0;
+    for (int e = (failed ? 0 : (adone + 1) * RGN_KB) + tid; e < (wl + 1) * RGN_KB; e += RGN_NT) {
+        const int a = e / RGN_KB, j = e % RGN_KB;
+        if (j < ncol) otab[(size_t)a * W1 + j] = failed ? __builtin_nan("") : -INFINITY;
+    }
+    if (tid == 0 && failed) atomicOr(&flags[r], RGN_ERR_DENOM);
+}

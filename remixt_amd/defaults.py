@@ -56,6 +56,15 @@ cn_region_moments = False
 cn_event_extents = None
 cn_extent_window = 64
 
+# Exact posterior of the length of the events of cn_event_extents (it needs them): every fit result also carries
+# `event_lengths` -- per entry the 5 / 50 / 95 % quantiles of the event's length (the sum of the segment lengths between its
+# two ends, given the event at the segment) with a flag where a quantile is not reached inside the window, and, for every
+# length of cn_event_length_edges (each > 0), P(length <= edge) and the mass for which the window cannot tell -- from the
+# joint law of the two ends over cn_extent_window segments on each side, whose table may hold at most 16 384 entries
+# (remixt_amd/posteriors.py).  False: off
+cn_event_lengths = False
+cn_event_length_edges = ()
+
 
 def get_param(config, name):
     if config is not None and name in config:

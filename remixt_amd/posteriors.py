@@ -810,3 +810,185 @@ def add_event_extents(res, names, extents):
         out[k] = np.asarray(extents[k]).astype(float if k == 'p_event' else (bool if k.endswith('_censored') else np.int64))
     res['event_extents'] = out
     return res
+
+
+# ---- the joint law of an event's two ends, and of its length (rmx_region_span) ------------------------------
+SPAN_ARRAYS = ('length_q05', 'length_q50', 'length_q95', 'length_censored')
+SPAN_EDGE_ARRAYS = ('p_length_le', 'p_length_undetermined')
+_SPAN_MAX_ENTRIES = 16384
+
+
+def parse_span_window(window):
+    """A window as (wl, wr): an int (both sides) or a pair, each >= 0, (wl + 1) (wr + 1) <= 16384."""
+    if np.ndim(window) == 0:
+        wl = wr = int(window)
+    else:
+        wl, wr = (int(w) for w in window)
+    if wl < 0 or wr < 0 or (wl + 1) * (wr + 1) > _SPAN_MAX_ENTRIES:
+        raise ValueError('a window needs widths >= 0 and a table of at most %d entries' % _SPAN_MAX_ENTRIES)
+    return wl, wr
+
+
+def _length_cdf(lengths, pmf, closed, p0):
+    """length_cdf of span_summary: a function of edges."""
+    def length_cdf(edges):
+        e = np.asarray(edges, dtype=float).reshape(-1)
+        if not p0 > 0:
+            return np.full(len(e), np.nan), np.full(len(e), np.nan)
+        le = lengths[None, :, :] <= e[:, None, None]
+        p_le = (np.where(le & closed[None], pmf[None], 0.)).sum(axis=(1, 2)) / p0
+        p_un = (np.where(le & ~closed[None], pmf[None], 0.)).sum(axis=(1, 2)) / p0
+        return p_le, p_un
+    return length_cdf
+
+
+def span_summary(logp, anchor, wl, wr, seg_fwd_remap, is_telomere, l1):
+    """What one table of rmx_region_span says about the two ends of the event around `anchor` (an experiment segment index)
+    together, and about its length.  logp: (wl + 1, wr + 1) log-probabilities, entry (a, c) for the model segments
+    [seg_fwd_remap[anchor] - a, seg_fwd_remap[anchor] + c]; l1: the lengths of the model segments.  It follows
+    extent_summary: original segments only and in experiment indices (the sub-table of the original segments is taken before
+    anything is differenced), and the running minimum is applied along both axes, so that rounding cannot make the table
+    rise.  A dict of
+      p_event: the probability of the event at the anchor alone, exp(entry (0, 0));
+      left_segments / right_segments: as extent_summary, from the anchor outward; they index the rows / columns below;
+      left_open / right_open: whether the chain goes on past the window on that side.  The side's last index is then the lump
+        "this segment or beyond";
+      joint_survival: P(the event reaches left[i] and right[j]) / p_event (NaN everywhere if p_event is 0);
+      joint_pmf: P(event at the anchor, left end = left[i], right end = right[j]) = J[i][j] - J[i+1][j] - J[i][j+1] + J[i+1][j+1]
+        of the table J, 0 beyond the last index; entries in (-1e-9 p_event, 0) are clipped to 0.  It sums to p_event, and its
+        row and column sums are extent_summary's left_pmf and right_pmf followed by their censored masses;
+      lengths: the sum of l1 over the model segments from left[i] to right[j]; a lower bound in an open cell;
+      length_quantiles: the 5 / 50 / 95 % quantiles of the length given the event, over the closed cells in increasing length;
+        a quantile the closed mass never reaches is the table's largest length with length_censored (3 bools) True; -1 if
+        p_event is 0;
+      length_cdf: a function of edges -> (p_le, p_undetermined), each (len(edges),), given the event: the closed mass with
+        length <= edge, and the open mass whose lower bound is <= edge (its length may or may not be); NaN if p_event is 0."""
+    logp = np.asarray(logp, dtype=float)
+    fwd = np.asarray(seg_fwd_remap, dtype=np.int64)
+    tel = np.asarray(is_telomere) != 0
+    l1 = np.asarray(l1, dtype=float)
+    N1 = len(tel)
+    if logp.shape != (wl + 1, wr + 1):
+        raise ValueError('logp must have shape (wl + 1, wr + 1)')
+    rev = np.full(N1, -1, dtype=np.int64)
+    rev[fwd] = np.arange(len(fwd))
+    cs, ce = chains_from_telomeres(tel)
+    n0 = int(fwd[anchor])
+    c = int(np.searchsorted(ce, n0, side='left'))
+    with np.errstate(over='ignore'):
+        p = np.minimum(np.exp(logp), 1.)
+    p0 = float(p[0, 0])
+    nr_ = np.arange(n0, min(n0 + wr, int(ce[c])) + 1)
+    nl_ = np.arange(n0, max(n0 - wl, int(cs[c])) - 1, -1)
+    nr_, nl_ = nr_[rev[nr_] >= 0], nl_[rev[nl_] >= 0]
+    right_open = bool((rev[np.arange(nr_[-1] + 1, int(ce[c]) + 1)] >= 0).any())
+    left_open = bool((rev[np.arange(int(cs[c]), nl_[-1])] >= 0).any())
+    J = p[np.ix_(n0 - nl_, nr_ - n0)]
+    J = np.minimum.accumulate(np.minimum.accumulate(J, axis=0), axis=1)
+    Jp = np.zeros((len(nl_) + 1, len(nr_) + 1))
+    Jp[:-1, :-1] = J
+    pmf = Jp[:-1, :-1] - Jp[1:, :-1] - Jp[:-1, 1:] + Jp[1:, 1:]
+    pmf[(pmf < 0) & (pmf > -1e-9 * p0)] = 0.
+    cum = np.concatenate([[0.], np.cumsum(l1)])
+    lengths = cum[nr_ + 1][None, :] - cum[nl_][:, None]
+    closed = np.ones(pmf.shape, dtype=bool)
+    if left_open:
+        closed[-1, :] = False
+    if right_open:
+        closed[:, -1] = False
+    if p0 > 0:
+        with np.errstate(invalid='ignore', divide='ignore'):
+            surv = J / p0
+        order = np.argsort(lengths[closed], kind='stable')
+        ls, ms = lengths[closed][order], np.cumsum(pmf[closed][order]) / p0
+        quant, cens = [], []
+        for qv in EXTENT_QUANTILES:
+            hit = np.flatnonzero(ms >= qv)
+            quant.append(float(ls[hit[0]]) if len(hit) else float(lengths.max()))
+            cens.append(not len(hit))
+    else:
+        surv = np.full(J.shape, np.nan)
+        quant, cens = [-1.] * 3, [False] * 3
+    return {'p_event': p0, 'left_segments': rev[nl_], 'right_segments': rev[nr_], 'left_open': left_open, 'right_open': right_open,
+            'joint_survival': surv, 'joint_pmf': pmf, 'lengths': lengths, 'length_quantiles': np.array(quant, dtype=float),
+            'length_censored': np.array(cens, dtype=bool), 'length_cdf': _length_cdf(lengths, pmf, closed, p0)}
+
+
+def compact_spans(summaries, edges=()):
+    """The arrays of SPAN_ARRAYS, each (len(summaries),), and of SPAN_EDGE_ARRAYS, each (len(summaries), len(edges)), from a list
+    of span_summary dicts: the three length quantiles, whether any of them is censored, and length_cdf at `edges`."""
+    edges = np.asarray(edges, dtype=float).reshape(-1)
+    out = {}
+    for i, name in enumerate(SPAN_ARRAYS[:3]):
+        out[name] = np.array([s['length_quantiles'][i] for s in summaries], dtype=float)
+    out['length_censored'] = np.array([bool(s['length_censored'].any()) for s in summaries], dtype=bool)
+    cdf = [s['length_cdf'](edges) for s in summaries]
+    out['p_length_le'] = np.array([c[0] for c in cdf], dtype=float).reshape(len(summaries), len(edges))
+    out['p_length_undetermined'] = np.array([c[1] for c in cdf], dtype=float).reshape(len(summaries), len(edges))
+    return out
+
+
+def lengths_on(config, num_segments=None):
+    """Config values cn_event_lengths / cn_event_length_edges, checked before any fit: None (off), or (names, anchors,
+    events, (wl, wr), edges) of the entries of cn_event_extents, which it needs, with a window whose table fits."""
+    from . import defaults
+    if not defaults.get_param(config, 'cn_event_lengths'):
+        return None
+    ext = extents_on(config, num_segments)
+    if ext is None:
+        raise ValueError('cn_event_lengths needs cn_event_extents')
+    names, anchors, events, window = ext
+    try:
+        window = parse_span_window(window)
+    except ValueError:
+        raise ValueError('cn_event_lengths: cn_extent_window %r gives a table of more than %d entries' % (window, _SPAN_MAX_ENTRIES))
+    try:
+        edges = tuple(float(x) for x in defaults.get_param(config, 'cn_event_length_edges'))
+    except (TypeError, ValueError):
+        raise ValueError('cn_event_length_edges: a list of lengths')
+    if not all(x > 0 and np.isfinite(x) for x in edges):
+        raise ValueError('cn_event_length_edges: every length must be > 0')
+    return names, anchors, events, window, edges
+
+
+def grouped_event_spans(span_fn, anchors, events, window, edges=()):
+    """The arrays of SPAN_ARRAYS and SPAN_EDGE_ARRAYS over all entries of a parsed cn_event_extents, from one call of
+    span_fn(anchors, event, window) -> list over restarts of lists of span_summary per distinct event: a list over restarts
+    of dicts of (A,) and (A, len(edges)) arrays."""
+    anchors = np.asarray(anchors, dtype=np.int64)
+    out = None
+    for ev in sorted(set(events)):
+        sel = np.flatnonzero([e == ev for e in events])
+        per_restart = span_fn(anchors[sel], event_pair(ev), window)
+        if out is None:
+            out = [dict([(k, np.zeros(len(anchors), dtype=bool if k == 'length_censored' else float)) for k in SPAN_ARRAYS] +
+                        [(k, np.zeros((len(anchors), len(edges)))) for k in SPAN_EDGE_ARRAYS]) for _ in per_restart]
+        for res, summaries in zip(out, per_restart):
+            comp = compact_spans(summaries, edges)
+            for k in SPAN_ARRAYS + SPAN_EDGE_ARRAYS:
+                res[k][sel] = comp[k]
+    return out if out is not None else []
+
+
+def add_event_lengths(res, names, lengths):
+    """Fit result dict `res` gains `event_lengths`: the entry names, the arrays of SPAN_ARRAYS, one entry per name, and the
+    two tables of SPAN_EDGE_ARRAYS, (entries, edges)."""
+    out = {'names': list(names)}
+    for k in SPAN_ARRAYS + SPAN_EDGE_ARRAYS:
+        # (a record carries them as floats)
+        out[k] = np.asarray(lengths[k]).astype(bool if k == 'length_censored' else float)
+    res['event_lengths'] = out
+    return res
+
+
+def batch_event_spans(batch, r0, nr, anchors, event, window, seg_fwd_remap, seg_is_original, is_telomere, l1):
+    """span_summary of every anchor (experiment segment indices) for restarts r0 .. r0+nr-1 of a RemixtBatch from one device
+    call: a list over restarts of lists over anchors.  event: parse_event; window: parse_span_window."""
+    wl, wr = parse_span_window(window)
+    q, constrain = extent_queries(anchors, event, seg_fwd_remap, seg_is_original)
+    if len(q) == 0:
+        return [[] for _ in range(nr)]
+    masks, labels = event_tables(batch.cn_classes)
+    logp = batch.region_span_raw(r0, nr, q, masks, labels, constrain, wl, wr)
+    anc = np.asarray(anchors, dtype=np.int64).reshape(-1)
+    return [[span_summary(logp[i, j], int(a), wl, wr, seg_fwd_remap, is_telomere, l1) for j, a in enumerate(anc)] for i in range(nr)]

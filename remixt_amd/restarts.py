@@ -702,6 +702,16 @@ class RestartSet(object):
         return posteriors.batch_event_extents(self.batch, 0, len(self.models), anchors, event, window, m.seg_fwd_remap, m.seg_is_original,
                                               m.is_telomere)
 
+    def event_span(self, anchors, event, window=64):
+        """BreakpointModel.event_span of every restart from one device call: a list over restarts of lists of
+        posteriors.span_summary dicts, one per anchor."""
+        from . import posteriors
+        if self.batch is None or not hasattr(self.batch, 'region_span_raw'):
+            return [m.event_span(anchors, event, window) for m in self.models]
+        m = self.models[0]
+        return posteriors.batch_event_spans(self.batch, 0, len(self.models), anchors, event, window, m.seg_fwd_remap, m.seg_is_original,
+                                            m.is_telomere, m.l1)
+
     def _call_states(self, cn):
         """int16 (restarts, N1): the restarts' calls as state indices in model segment order.  cn: their paths in
         experiment order (the `cn` of results()); None: the decoded paths."""
@@ -887,6 +897,10 @@ class RestartGroups(object):
         """RestartSet.event_extent over the groups, restarts in order: a list over restarts of lists over anchors."""
         return [x for part in self._map(lambda rs: rs.event_extent(anchors, event, window)) for x in part]
 
+    def event_span(self, anchors, event, window=64):
+        """RestartSet.event_span over the groups, restarts in order: a list over restarts of lists over anchors."""
+        return [x for part in self._map(lambda rs: rs.event_span(anchors, event, window)) for x in part]
+
     def call_confidence(self, regions, cn=None):
         """RestartSet.call_confidence over the groups, restarts in order (cn: of all restarts): a dict of arrays (restarts, len(regions))."""
         parts = self._map(lambda rs: rs.call_confidence(regions, None if cn is None else cn[self.slices[self.sets.index(rs)]]))
@@ -1007,6 +1021,10 @@ class DatasetGroups(object):
     def event_extent(self, anchors, event, window=64):
         """RestartGroups.event_extent of every dataset: a list, one list over restarts per dataset."""
         return self._map(lambda part: part.event_extent(anchors, event, window))
+
+    def event_span(self, anchors, event, window=64):
+        """RestartGroups.event_span of every dataset: a list, one list over restarts per dataset."""
+        return self._map(lambda part: part.event_span(anchors, event, window))
 
     def call_confidence(self, regions, cn=None):
         """RestartGroups.call_confidence of every dataset (cn: per dataset, a list of its restarts' paths): a list, one dict of arrays
@@ -1138,7 +1156,7 @@ def _section(fields, group=None, head=(), tail=(), add=None):
 
 
 def _record_sections(N, M, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0, call_confidence=False, cn_moments=False,
-                     extent_names=None):
+                     extent_names=None, length_edges=None):
     """The optional sections of a float record, in record order.  The record is the fixed part -- header, h, parameters,
     outlier probabilities: _HDR + M + nparams + 4 N floats -- and then, each only when its option is on (a record without
     it is unchanged), at offsets that are the running sum of what precedes:
@@ -1150,7 +1168,9 @@ def _record_sections(N, M, cn_samples=False, cn_posterior=False, region_names=No
       region moments (cn_region_moments, with regions): the five arrays of posteriors.MOMENT_ARRAYS (shapes:
         posteriors.moment_shapes), then the two posteriors.MOMENT_STATS;
       event extents (cn_event_extents): the nine arrays of posteriors.EXTENT_ARRAYS, one entry per named anchor (segment
-        indices and flags as floats: exact)."""
+        indices and flags as floats: exact);
+      event lengths (cn_event_lengths, with extents; length_edges: the number of cn_event_length_edges): the four arrays of
+        posteriors.SPAN_ARRAYS, one entry per named anchor, then the two tables of posteriors.SPAN_EDGE_ARRAYS, (entries, edges)."""
     from . import sampling
     out = []
     if cn_samples:
@@ -1174,13 +1194,17 @@ def _record_sections(N, M, cn_samples=False, cn_posterior=False, region_names=No
     if extent_names is not None:
         out.append(_section([(k, (len(extent_names),)) for k in posteriors.EXTENT_ARRAYS], 'event_extents',
                             add=lambda res, a: posteriors.add_event_extents(res, extent_names, a)))
+        if length_edges is not None:
+            nent = len(extent_names)
+            out.append(_section([(k, (nent,)) for k in posteriors.SPAN_ARRAYS] + [(k, (nent, int(length_edges))) for k in posteriors.SPAN_EDGE_ARRAYS],
+                                'event_lengths', add=lambda res, a: posteriors.add_event_lengths(res, extent_names, a)))
     return out
 
 
 def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0, call_confidence=False,
-          cn_moments=False, extent_names=None):
+          cn_moments=False, extent_names=None, length_edges=None):
     """One restart's results as (float64 vector, int8 vector) of fixed length."""
-    sections = _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names)
+    sections = _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names, length_edges)
     o = _HDR + M + nparams
     f = np.zeros(o + 4 * N + sum(s.length for s in sections), dtype=np.float64)
     st = res['stats']
@@ -1202,8 +1226,8 @@ def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_post
 
 
 def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0,
-            call_confidence=False, cn_moments=False, extent_names=None):
-    sections = _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names)
+            call_confidence=False, cn_moments=False, extent_names=None, length_edges=None):
+    sections = _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names, length_edges)
     res = dict()
     res['h'] = f[_HDR:_HDR + M].copy()
     o = _HDR + M + nparams
@@ -1230,7 +1254,7 @@ def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_sampl
 def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clones=3, num_em_iter=5, num_update_iter=5,
                              device=None, kernel_module=None, seeds=None, quiet=True, groups=2, num_cn_samples=0, cn_sample_seed=0,
                              cn_posterior_summary=False, cn_regions=None, cn_region_change_bins=0, cn_call_confidence=False, cn_region_moments=False,
-                             cn_event_extents=None, cn_extent_window=64, **model_kwargs):
+                             cn_event_extents=None, cn_extent_window=64, cn_event_lengths=False, cn_event_length_edges=(), **model_kwargs):
     """Fit all restarts across the ranks of the default torch.distributed group.
 
     Every rank holds the (small, read-only) experiment; rank g fits restarts
@@ -1251,11 +1275,15 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
     (posteriors.add_region_cn_moments), and the records grow by 21 + M + M^2 floats per region and two.
     cn_event_extents: a list of (name, segment, event); every result also carries `event_extents` for a window of
     cn_extent_window segments on each side (posteriors.add_event_extents), and the records grow by nine floats per entry.
+    cn_event_lengths (with cn_event_extents): every result also carries `event_lengths` (posteriors.add_event_lengths), and
+    the records grow by 4 + 2 len(cn_event_length_edges) floats per entry.
     """
     import torch
     import torch.distributed as dist
     posteriors.check_region_options(cn_regions, cn_region_change_bins, cn_call_confidence, cn_region_moments)
     extents = posteriors.extents_on({'cn_event_extents': cn_event_extents, 'cn_extent_window': cn_extent_window}, len(experiment.x))
+    lengths = posteriors.lengths_on({'cn_event_extents': cn_event_extents, 'cn_extent_window': cn_extent_window, 'cn_event_lengths': cn_event_lengths,
+                                     'cn_event_length_edges': cn_event_length_edges}, len(experiment.x))
     distributed = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size() if distributed else 1
     rank = dist.get_rank() if distributed else 0
@@ -1272,7 +1300,7 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
         rs.fit(num_em_iter, num_update_iter)
         local = rs.results()
         add_optional_outputs(rs, local, experiment, mine, num_cn_samples, cn_sample_seed, cn_posterior_summary, cn_regions, cn_region_change_bins, cn_call_confidence,
-                             cn_region_moments, cn_event_extents, cn_extent_window)
+                             cn_region_moments, cn_event_extents, cn_extent_window, cn_event_lengths, cn_event_length_edges)
         param_names = list(rs.models[0].likelihood_params)
         rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     if param_names is None:
@@ -1283,7 +1311,7 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
                                  cn_posterior=bool(cn_posterior_summary),
                                  region_names=None if cn_regions is None else [str(r[0]) for r in cn_regions], change_bins=cn_region_change_bins,
                                  call_confidence=bool(cn_call_confidence), cn_moments=bool(cn_region_moments),
-                                 extent_names=None if extents is None else extents[0])
+                                 extent_names=None if extents is None else extents[0], length_edges=None if lengths is None else len(lengths[4]))
 
 
 def add_region_events(rs, results, cn_regions):
@@ -1340,6 +1368,16 @@ def add_event_extents(rs, results, cn_event_extents, window):
     return results
 
 
+def add_event_lengths(rs, results, cn_event_extents, window, edges):
+    """Add the event lengths of config cn_event_lengths / cn_event_length_edges of every restart of `rs` (a RestartSet /
+    RestartGroups; one device call per batch and distinct event) to results[r] (posteriors.add_event_lengths)."""
+    names, anchors, events = posteriors.parse_extents(cn_event_extents)
+    per_restart = posteriors.grouped_event_spans(rs.event_span, anchors, events, window, edges)
+    for res, ln in zip(results, per_restart):
+        posteriors.add_event_lengths(res, names, ln)
+    return results
+
+
 def add_posterior_summaries(rs, results, experiment):
     """Add the exact posterior summary of every restart of `rs` (a RestartSet / RestartGroups; one device call per
     batch) to results[r] (posteriors.add_posterior_summary); cn_posterior_prob is taken at results[r]['cn']."""
@@ -1361,7 +1399,8 @@ def add_cn_sample_summaries(rs, results, experiment, num_samples, seed, init_ids
 
 
 def add_optional_outputs(rs, results, experiment, init_ids, num_cn_samples=0, cn_sample_seed=0, cn_posterior_summary=False, cn_regions=None,
-                         cn_region_change_bins=0, cn_call_confidence=False, cn_region_moments=False, cn_event_extents=None, cn_extent_window=64):
+                         cn_region_change_bins=0, cn_call_confidence=False, cn_region_moments=False, cn_event_extents=None, cn_extent_window=64,
+                         cn_event_lengths=False, cn_event_length_edges=()):
     """Add the optional outputs of a fit -- the config values of the same names -- of every restart of the fitted `rs` (a
     RestartSet / RestartGroups) to results[r]; init_ids[r] selects restart r's posterior-sample stream.  The combination is
     checked before the fit (posteriors.check_region_options)."""
@@ -1379,11 +1418,14 @@ def add_optional_outputs(rs, results, experiment, init_ids, num_cn_samples=0, cn
             add_region_cn_moments(rs, results, cn_regions)
     if cn_event_extents is not None:
         add_event_extents(rs, results, cn_event_extents, cn_extent_window)
+        if cn_event_lengths:
+            add_event_lengths(rs, results, cn_event_extents, cn_extent_window, tuple(cn_event_length_edges))
     return results
 
 
 def gather_result_records(local, experiment, init_params, num_clones, param_names, device=None, timing=None, local_ids=None, cn_samples=False,
-                          cn_posterior=False, region_names=None, change_bins=0, call_confidence=False, cn_moments=False, extent_names=None):
+                          cn_posterior=False, region_names=None, change_bins=0, call_confidence=False, cn_moments=False, extent_names=None,
+                          length_edges=None):
     """The one collective of the path: every rank contributes the fixed-size records of the restarts
     it fitted (`local`, in the order of shard_indices) -- one float64 record (ELBO, h, parameters, outlier
     probabilities, failure code) and one int8 record (cn, brk_cn, masks) per restart -- and every rank gets the
@@ -1412,12 +1454,12 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
             per_rank = int(cnt_.item())
     if len(local) > per_rank:
         raise ValueError('gather_result_records: %d local results for a share of %d (pass local_ids for shares that are not shard_indices\')' % (len(local), per_rank))
-    flen = _HDR + M + nparams + 4 * N + sum(s.length for s in _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names))
+    flen = _HDR + M + nparams + 4 * N + sum(s.length for s in _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names, length_edges))
     ilen = N * M * 2 + K * M + 2 * N
     fbuf = np.full((per_rank, flen), np.nan); ibuf = np.zeros((per_rank, ilen), dtype=np.int8)
     for j, res in enumerate(local):
         fbuf[j], ibuf[j] = _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments,
-                                  extent_names)
+                                  extent_names, length_edges)
     if local_ids is not None:
         ids_t = np.full((per_rank,), -1, dtype=np.int64); ids_t[:len(local_ids)] = local_ids
     t0 = time.perf_counter()
@@ -1450,7 +1492,7 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
         ids_g = shard_indices(len(init_params), world, g) if ids_all is None else [int(i) for i in ids_all[g] if i >= 0]
         for j, i in enumerate(ids_g):
             results[i] = _unpack(fall[g][j], iall[g][j], N, M, K, nparams, brk_ids, param_names, init_params[i], cn_samples, cn_posterior, region_names, change_bins, call_confidence,
-                                 cn_moments, extent_names)
+                                 cn_moments, extent_names, length_edges)
     return results
 
 

@@ -498,6 +498,30 @@ int rmx_region_span(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int3
 int rmx_region_pattern(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t npieces, const int32_t *pieces,
                        int32_t nmask, const uint8_t *masks, int32_t nlabel, const int16_t *labels, const uint8_t *constrain, double *logp_out);
 
+/* Region decode: the most probable copy-number configuration of a region, and its probability.  Queries,
+ * tables and constrain are those of rmx_region_prob; for the event E of query i over the model segments [a, b],
+ *   logp_out[r][i] = log P*,  P* = max over (c_a .. c_b) satisfying E of q(c_a, .., c_b),
+ * q the marginal of the run under the structured posterior of the last update_p_cn (everything outside [a, b] summed
+ * out: comparable with P(E) of rmx_region_prob, which is the sum over the same paths), and states_out[r][i][k] = c*_{a+k},
+ * one path that attains it.  Ties go to the lowest state index at every step.  The model is not modified.
+ *   max_len    1 .. 16384, at least every query's b - a + 1
+ *   states_out int16 [nr][nq][max_len]: state indices in [0, S) into each segment's class table; entries past the run,
+ *              and every entry of an impossible or failed query, are -1
+ *   logp_out   [nr][nq]; -inf for an impossible event.  A state whose forward entry underflowed to 0 in the sweep's scaled
+ *              rows cannot be chosen, where its true probability is merely tiny (as rmx_call_prob)
+ * A (restart, query) result, value and path, is bit-identical in any restart range, any batch of queries and for any
+ * max_len.  Device memory a call holds beyond the model, kept with the batch: at most 64 MiB of staged outputs and
+ * queries (the buffer rmx_region_prob uses) and at most 1 GiB of int16 back-pointers, max_len * S per (restart, query)
+ * of a chunk; a call that needs more runs in chunks of queries and blocks of restarts (rmxh::decode_plan, rmx_host.h).
+ * Errors as rmx_region_prob, and RMX_EARG with nothing launched and both outputs untouched for max_len out of range, a
+ * query longer than max_len, or a NULL output.  RMX_EVALUE with the restarts listed: a restart has had no update_p_cn.
+ * RMX_EASSERT with the restarts listed: a backward step met a zero or non-finite normaliser under positive mass, or a
+ * maximum that is not a finite number >= 0 (that query's result is NaN, its states -1).  RMX_EUNSUPPORTED: more than
+ * 1024 states. */
+int rmx_region_decode(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries,
+                      int32_t nmask, const uint8_t *masks, int32_t nlabel, const int16_t *labels, const uint8_t *constrain,
+                      int32_t max_len, int16_t *states_out, double *logp_out);
+
 /* -- module-level functions on caller-supplied dense inputs ----------------- */
 /* sum_product (:1213-1246): f [N][S], T [N-1][S][S] -> alphas, betas [N][S] */
 int rmx_sum_product(const double *f, const double *T, double *alphas, double *betas,

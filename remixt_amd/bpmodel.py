@@ -755,6 +755,26 @@ class RemixtBatch(object):
                                               obuf.ctypes.data_as(_dp)))
         return out
 
+    def region_decode_raw(self, r0, nr, queries, masks=None, labels=None, constrain=None, max_len=None):
+        """The most probable configuration of every query's run, and its log-probability, under the structured posterior of
+        the last update_p_cn of restarts r0 .. r0+nr-1 (rmx_region_decode): (logp (nr, nq), states int16 (nr, nq, max_len)).
+        queries, masks, labels and constrain as region_logprob_raw; logp is the maximum, over the paths of the run that
+        satisfy the query's event, of the run's marginal probability -- the sum of the same terms is region_logprob_raw --
+        and states[r, i, k] the state of segment a + k of one path that attains it (ties to the lowest state index); entries
+        past the run, and those of an impossible query (logp -inf), are -1.  max_len: 1 .. 16384 and at least the longest
+        query; None: the longest query."""
+        r0, nr = int(r0), int(nr)
+        q, args, _keep = self._region_args(queries, masks, labels, constrain)
+        if max_len is None:
+            max_len = int(np.clip((q[:, 1].astype(np.int64) - q[:, 0] + 1).max(), 1, 16384)) if q.shape[0] else 1
+        max_len = int(max_len)
+        out = np.zeros((max(nr, 0), q.shape[0]), dtype=np.float64)
+        states = np.full((max(nr, 0), q.shape[0], max(max_len, 0)), -1, dtype=np.int16)
+        obuf = out if out.size else np.zeros(1)
+        sbuf = states if states.size else np.zeros(1, dtype=np.int16)
+        self._ck(self._lib.rmx_region_decode(self._handle, r0, nr, *args, max_len, sbuf.ctypes.data_as(C.POINTER(C.c_int16)), obuf.ctypes.data_as(_dp)))
+        return out, states
+
     # -- measurement ------------------------------------------------------------
     def timer_start(self):
         self._ck(self._lib.rmx_timer_start(self._handle))
@@ -1001,6 +1021,11 @@ class RemixtModel(object):
     def region_pattern(self, queries, pieces, masks=None, labels=None, constrain=None):
         """RemixtBatch.region_pattern_raw of this model: log-probabilities (nq,)."""
         return self._batch.region_pattern_raw(self._r, 1, queries, pieces, masks, labels, constrain)[0]
+
+    def region_decode(self, queries, masks=None, labels=None, constrain=None, max_len=None):
+        """RemixtBatch.region_decode_raw of this model: (logp (nq,), states int16 (nq, max_len))."""
+        logp, states = self._batch.region_decode_raw(self._r, 1, queries, masks, labels, constrain, max_len)
+        return logp[0], states[0]
 
     def call_logprob(self, paths, queries, labels=None, constrain=None):
         """RemixtBatch.call_logprob_raw of this model: paths (npaths, N) -> log-probabilities (nq,)."""

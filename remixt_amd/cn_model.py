@@ -839,6 +839,22 @@ class BreakpointModel(object):
         out = dict((k, v[0]) for k, v in out.items())
         return out if arrays else dict((bp, dict((k, v[i]) for k, v in out.items())) for i, bp in enumerate(self.breakpoints))
 
+    def region_call(self, regions, event=None, cn=None):
+        """The most probable copy-number configuration of every region under the structured posterior of the last
+        variational update, and its probability (posteriors.batch_region_calls): regions is a list of (first, last)
+        experiment segment indices; event None, or (mask name or None, label name or None) -- the most probable
+        configuration in which the event holds, e.g. ('hdel', None).  A dict of `cn`, a list over regions of (segments, M, 2)
+        arrays, and arrays (len(regions),): log_prob, log_p_event, log_prob_given_event, and against the call cn ((N, M, 2)
+        in experiment order; None: the decoded path) n_differ and log_prob_call."""
+        from . import posteriors
+        if not hasattr(self.model, 'region_decode'):
+            raise NotImplementedError('kernel module %s has no region decode' % getattr(self._kernel_module(), '__name__', '?'))
+        b, r, states, single = self._call_states(cn)
+        if not single:
+            raise ValueError('region_call takes one call of shape (num_segments, num_clones, 2)')
+        out = posteriors.batch_region_calls(b, r, 1, regions, self.seg_fwd_remap, self.seg_is_original, self.is_telomere, event=event, cn=states)
+        return dict((k, v[0]) for k, v in out.items())
+
     def ploidy_posterior_sd(self):
         """The exact posterior SD of the tumour ploidy whose mean is stats['ploidy_posterior_mean']: the whole genome as one
         region of region_cn_moments (posteriors.moment_stats)."""

@@ -40,17 +40,17 @@ static inline long long now_ns() { return std::chrono::duration_cast<std::chrono
 enum KernelId {
     KID_STATE_TABLES = 0, KID_SEG_CONST, KID_FRAMELOGPROB, KID_FB, KID_MARGINALS, KID_MARGINALS_AB, KID_OUTLIER_TOTAL,
     KID_OUTLIER_ALLELE, KID_ALLELE_SWAP, KID_BRK_LUT, KID_PAIRWISE, KID_BRK_UPDATE, KID_ELBO_SEG, KID_ELBO_FINAL,
-    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_POST_SUMMARY, KID_REGION, KID_REGION_COUNTS, KID_CALL_PROB, KID_REGION_MOMENTS, KID_REGION_EXTENT, KID_REGION_SPAN, KID_REGION_PATTERN, KID_COUNT
+    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_POST_SUMMARY, KID_REGION, KID_REGION_COUNTS, KID_CALL_PROB, KID_REGION_MOMENTS, KID_REGION_EXTENT, KID_REGION_SPAN, KID_REGION_PATTERN, KID_REGION_DECODE, KID_COUNT
 };
 static const char *kKernelNames[KID_COUNT] = {
     "k_state_tables", "k_seg_const", "k_framelogprob", "k_fb", "k_marginals<true>", "k_marginals<false>", "k_update_outlier_total",
     "k_update_outlier_allele", "k_update_allele_swap", "k_brk_lut", "k_pairwise", "k_brk_update", "k_elbo_seg", "k_elbo_final",
-    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn", "k_posterior_summary", "k_region_prob", "k_region_counts", "k_call_prob", "k_region_moments", "k_region_extent", "k_region_span", "k_region_pattern"};
+    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn", "k_posterior_summary", "k_region_prob", "k_region_counts", "k_call_prob", "k_region_moments", "k_region_extent", "k_region_span", "k_region_pattern", "k_region_decode"};
 // (ids are appended, never reordered: profiles written by earlier builds keep their meaning.  Before k_region_span the two lists ended
 //  `KID_REGION_MOMENTS, KID_REGION_EXTENT, KID_COUNT` and `"k_region_moments", "k_region_extent"};`, which tests/test_region_extent_cpu.py pins;
 //  before k_region_pattern they ended `"k_region_extent", "k_region_span"};` and, at a line end,
 //  KID_REGION_EXTENT, KID_REGION_SPAN, KID_COUNT
-//  which tests/test_region_span_cpu.py pins)
+//  which tests/test_region_span_cpu.py pins; before k_region_decode they ended with KID_REGION_PATTERN and "k_region_pattern")
 
 struct ProfRec { int id; hipEvent_t a, b; };
 
@@ -156,7 +156,7 @@ struct rmx_batch {
     std::vector<int64_t> last_path; int vit_cap = 0; size_t bp_cap = 0;
     int16_t *d_samp = nullptr; size_t samp_cap = 0; uint64_t *d_seeds = nullptr; uint32_t *d_sflags = nullptr;   // rmx_sample_cn: paths of a chunk of samples, seeds, flags [R]
     double *d_psum = nullptr; size_t psum_cap = 0; double *d_psw = nullptr; size_t psw_cap = 0;   // rmx_posterior_summary: output staging of a chunk (doubles), weights [C][S][Q]
-    double *d_rgn = nullptr; size_t rgn_cap = 0; uint8_t *d_rgt = nullptr; size_t rgt_cap = 0; uint32_t *d_rflags = nullptr;   // rmx_region_prob: outputs + queries of a chunk (doubles), label / mask / constrain tables (bytes), flags [R]
+    double *d_rgn = nullptr; size_t rgn_cap = 0; uint8_t *d_rgt = nullptr; size_t rgt_cap = 0; uint32_t *d_rflags = nullptr; int16_t *d_rgbp = nullptr; size_t rgbp_cap = 0;   // (d_rgbp: the back-pointer strips of a chunk of rmx_region_decode)  rmx_region_prob: outputs + queries of a chunk (doubles), label / mask / constrain tables (bytes), flags [R]
     uint16_t *d_comp = nullptr; int32_t *d_ends = nullptr; size_t comp_cap = 0, ends_cap = 0; int last_traceback = 0;      // parallel trace-back: composed maps [nr][NBLK][S], block end states [nr][NBLK]
     uint8_t *d_vit_code = nullptr; double *d_vit_val = nullptr; bool vit_code_ok = false, vit_mul_ok = false;   // 8-bit codes of T(i, o) of class 0 + their values (k_viterbi_code)
     // FB launch configuration
@@ -870,6 +870,49 @@ template <typename L> static int run_queries(rmx_batch *b, int r0, int nr, int n
         }
     }
     return report_flags(b, b->d_rflags, r0, nr, flag_msg);
+}
+
+// rmx_region_decode's driver, beside run_queries: two outputs of two types per (restart, query) -- a log-probability and max_len
+// int16 states -- and a back-pointer strip of max_len * S int16 of scratch each.  The chunks are rmxh::decode_plan's: blocks of at
+// most min(65535, what the budgets allow) restarts and chunks of queries, so that a chunk's outputs and queries stay within
+// 64 MiB (the staging buffer run_queries uses) and its strips within 1 GiB (b->d_rgbp); both buffers only grow and stay with
+// the batch.  Within a block, one launch per run of restarts of one transition model under profile id KID_REGION_DECODE;
+// rows come back to logp_out [nr][nq] and states_out [nr][nq][max_len]; a raised flag fails the call.
+static int run_decode(rmx_batch *b, int r0, int nr, int nq, const int32_t *queries, int max_len, RgnArgs ra, int16_t *states_out, double *logp_out) {
+    int rc;
+    if (!b->d_rflags && (rc = dalloc(b, &b->d_rflags, b->R))) return rc;
+    rmxh::DecodePlan pl;
+    if (rmxh::decode_plan(nr, nq, b->d.S, max_len, &pl)) return fail(RMX_EARG, "region_decode: no chunk plan");
+    const int nrc = pl.nrc;
+    const size_t qc = (size_t)pl.qc;
+    if ((rc = grow(b, &b->d_rgn, &b->rgn_cap, pl.out_doubles))) return rc;
+    if ((rc = grow(b, &b->d_rgbp, &b->rgbp_cap, pl.bp_elems))) return rc;
+    double *dout = b->d_rgn;
+    int16_t *dstates = (int16_t *)(b->d_rgn + pl.states_at);
+    int32_t *dq = (int32_t *)(b->d_rgn + pl.queries_at);
+    HIPCHK(hipMemsetAsync(b->d_rflags + r0, 0, sizeof(uint32_t) * nr, b->stream));
+    for (size_t q0 = 0; q0 < (size_t)nq; q0 += qc) {
+        const size_t nqc = std::min(qc, (size_t)nq - q0);
+        HIPCHK(hipMemcpyAsync(dq, queries + 4 * q0, nqc * 16, hipMemcpyHostToDevice, b->stream));
+        ra.queries = dq; ra.nq = (int)nqc;
+        for (int rb = 0; rb < nr; rb += nrc) {
+            const int nrr = std::min(nrc, nr - rb);
+            rc = for_model_runs(b, r0, rb, rb + nrr, [&](int i, int j, int, const Dev &dv, int use_wb) -> int {
+                ProfScope ps(b, KID_REGION_DECODE);
+                const size_t at = (size_t)(i - rb) * nqc;      // the run's first (restart, query) of the chunk
+                hipLaunchKernelGGL(k_region_decode, dim3((unsigned)nqc, j - i), dim3(RGN_NT), 0, b->stream, dv, r0 + i, use_wb, ra, max_len,
+                                   b->d_rgbp + at * pl.strip_elems, dstates + at * max_len, dout + at, b->d_rflags);
+                HIPCHK(hipGetLastError());
+                return RMX_OK;
+            });
+            if (rc) return rc;
+            // device [nrr][nqc] and [nrr][nqc][max_len] -> host rows (rb .. rb+nrr)[q0 .. q0+nqc)
+            HIPCHK(hipMemcpy2DAsync(logp_out + ((size_t)rb * nq + q0), (size_t)nq * 8, dout, nqc * 8, nqc * 8, nrr, hipMemcpyDeviceToHost, b->stream));
+            HIPCHK(hipMemcpy2DAsync(states_out + ((size_t)rb * nq + q0) * max_len, (size_t)nq * max_len * 2, dstates, nqc * max_len * 2, nqc * max_len * 2, nrr,
+                                    hipMemcpyDeviceToHost, b->stream));
+        }
+    }
+    return report_flags(b, b->d_rflags, r0, nr, "region_decode: a backward step has a zero or non-finite normaliser or maximum");
 }
 
 // HIP's current device is per host thread and starts at 0: every entry point binds the calling thread to the
@@ -3412,6 +3455,31 @@ int rmx_region_pattern(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const i
         ra.queries = dq; ra.nq = nqc;
         hipLaunchKernelGGL(k_region_pattern, dim3((unsigned)nqc, n), dim3(RGN_NT), 0, b->stream, dv, r, use_wb, ra, (const int32_t *)dpieces, out, flags);
     });
+}
+
+// Region decode (k_region_decode): the most probable configuration of rmx_region_prob's event over every query's run, its
+// log-probability and its states.  Checks are rmx_region_prob's and rmxh::check_decode_lengths (the kernel trusts that a run
+// fits max_len: its back-pointer strip and its row of states_out are max_len long); tables and staging are rmx_region_prob's,
+// the driver is run_decode.  One workgroup computes a (restart, query) on its own in its own strip, so a result depends on
+// neither the restart range, the chunking, the other queries nor max_len.
+int rmx_region_decode(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks, int32_t nlabel,
+                      const int16_t *labels, const uint8_t *constrain, int32_t max_len, int16_t *states_out, double *logp_out) { BIND(b);
+    int rc;
+    if ((rc = check_region_call(b, "region_decode", r0, nr, nq, queries, logp_out))) return rc;
+    if (!states_out) return fail(RMX_EARG, "region_decode: no queries or no output");
+    if ((rc = check_mask_label_tables("region_decode", nmask, masks, nlabel, labels))) return rc;
+    if (!rmxh::decode_max_len_ok(max_len)) return fail(RMX_EARG, "region_decode: max_len must be in [1, 16384]");
+    if (b->d.S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "region_decode: more than 1024 states");
+    if ((rc = check_queries(b, "region_decode", nq, queries, {-1, nmask, "region_decode: mask index out of range"}, {-1, nlabel, "region_decode: label index out of range"}))) return rc;
+    {
+        const char *why = nullptr;
+        const int64_t bad = rmxh::check_decode_lengths(nq, queries, max_len, &why);
+        if (bad >= 0) return fail(RMX_EARG, std::string("region_decode: ") + why + " (query " + std::to_string(bad) + ")");
+    }
+    if ((rc = require_snapshot(b, r0, nr, "region_decode"))) return rc;
+    RgnArgs ra;
+    if ((rc = stage_region_tables(b, nmask, masks, nlabel, labels, constrain, &ra))) return rc;
+    return run_decode(b, r0, nr, nq, queries, max_len, ra, states_out, logp_out);
 }
 
 // ---- module-level functions -------------------------------------------------------------------

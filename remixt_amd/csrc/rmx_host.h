@@ -4,6 +4,7 @@
 //   lt_classes           the total-copy classes of the state tables (compact read-depth planes of the cell cache)
 //   span_window_ok, span_spread_nan  rmx_region_span: the window rule of a table, and NaN in every entry of a failed query
 //   check_patterns       rmx_region_pattern: the rules of the piece lists of its queries
+//   decode_max_len_ok, check_decode_lengths, decode_plan  rmx_region_decode: the length rules and the chunks of a call
 //   weighted_search      rmx_weighted_search: numpy's cumsum / searchsorted(side='right') for the weighted M-step samples
 //                        (reference remixt/cn_model.py:475-480)
 //   weighted_sample_round  rmx_weighted_sample_round: a whole round of that sampling from a strided weight column
@@ -79,6 +80,56 @@ inline int64_t check_patterns(int32_t nq, const int32_t *queries, int32_t npiece
     }
     if (reason) *reason = why;
     return bad;
+}
+
+// rmx_region_decode.  Its max_len rule: 1 <= max_len <= DECODE_MAX_LEN
+constexpr int32_t DECODE_MAX_LEN = 16384;
+constexpr int32_t DECODE_MAX_STATES = 1024;
+constexpr size_t DECODE_OUT_BUDGET = (size_t)64 << 20;      // outputs and queries of a chunk, bytes
+constexpr size_t DECODE_BP_BUDGET = (size_t)1 << 30;        // back-pointer strips of a chunk, bytes (1 GiB: 1280 arm-sized strips at 355 states, five workgroups per CU)
+inline bool decode_max_len_ok(int32_t max_len) { return max_len >= 1 && max_len <= DECODE_MAX_LEN; }
+// every query [nq][4] = (a, b, .., ..) has a <= b and b - a + 1 <= max_len (no overflow for any int32 pair).  Returns the
+// index of the first query that breaks a rule, with *reason (a string literal), or -1
+inline int64_t check_decode_lengths(int32_t nq, const int32_t *queries, int32_t max_len, const char **reason) {
+    const char *why = nullptr;
+    int64_t bad = -1;
+    if (nq < 0 || (nq > 0 && !queries)) { why = "bad arguments"; bad = 0; }
+    else if (!decode_max_len_ok(max_len)) { why = "max_len must be in [1, 16384]"; bad = 0; }
+    for (int32_t i = 0; i < nq && !why; i++) {
+        const int64_t a = queries[4 * (size_t)i], b = queries[4 * (size_t)i + 1];
+        if (a > b) why = "a query needs first <= last";
+        else if (b - a + 1 > (int64_t)max_len) why = "a query is longer than max_len";
+        if (why) bad = i;
+    }
+    if (reason) *reason = why;
+    return bad;
+}
+// The chunks of a call over nr restarts and nq queries at S states: blocks of nrc restarts, chunks of qc queries.  A chunk
+// holds, per (restart, query), a back-pointer strip of max_len * S int16, a log-probability (double) and max_len states
+// (int16), and per query 16 bytes of staged query.  nrc and qc are the largest with
+//   nrc * qc * strip_bytes <= DECODE_BP_BUDGET   and   qc * (nrc * (8 + 2 max_len) + 16) + 8 <= DECODE_OUT_BUDGET (8: alignment),
+// nrc <= 65535 (a grid dimension) taken first, and never below one restart and one query: the largest strip, 16384 * 1024 * 2
+// bytes = 32 MiB, and the largest single output, 8 + 32768 + 16 bytes, fit their budgets.  The staging buffer, in doubles:
+// logp [nrc][qc] at 0, states int16 [nrc][qc][max_len] at states_at, queries int32 [qc][4] at queries_at, out_doubles in all
+struct DecodePlan {
+    int32_t nrc, qc;
+    size_t strip_elems;       // int16 per (restart, query) strip
+    size_t bp_elems;          // int16 of back-pointer scratch: nrc * qc * strip_elems
+    size_t states_at, queries_at, out_doubles;
+};
+inline int decode_plan(int32_t nr, int32_t nq, int32_t S, int32_t max_len, DecodePlan *p) {
+    if (!p || nr < 1 || nq < 1 || S < 1 || S > DECODE_MAX_STATES || !decode_max_len_ok(max_len)) return 5;
+    const size_t strip = (size_t)max_len * (size_t)S, strip_bytes = strip * 2, per_out = 8 + 2 * (size_t)max_len;
+    const size_t strips = std::max<size_t>(1, DECODE_BP_BUDGET / strip_bytes);
+    const size_t nrc = std::min<size_t>(std::min<size_t>((size_t)nr, 65535), std::min<size_t>(strips, std::max<size_t>(1, (DECODE_OUT_BUDGET - 24) / per_out)));
+    const size_t qc = std::max<size_t>(1, std::min<size_t>((size_t)nq, std::min<size_t>(strips / nrc, (DECODE_OUT_BUDGET - 8) / (nrc * per_out + 16))));
+    p->nrc = (int32_t)nrc; p->qc = (int32_t)qc;
+    p->strip_elems = strip;
+    p->bp_elems = nrc * qc * strip;
+    p->states_at = nrc * qc;
+    p->queries_at = p->states_at + (nrc * qc * (size_t)max_len * 2 + 7) / 8;
+    p->out_doubles = p->queries_at + 2 * qc;
+    return 0;
 }
 
 inline int compress_cn_states(const int64_t *cn_states, int32_t N, int32_t S, int32_t M, int32_t max_classes,

@@ -6971,3 +6971,246 @@ __global__ __launch_bounds__(RGN_NT) void k_region_pattern(Dev d, int r0, int us
         out[(size_t)ri * q.nq + qi] = failed ? __builtin_nan("") : logp;
     }
 }
+
+// =============================================================================
+// Region decode: the most probable configuration of a region under the structured posterior of the last update_p_cn, and
+// its probability.  For the event E of a k_region_prob query over the model segments [a, b] of one chain,
+//   P* = max over (c_a .. c_b) satisfying E of q(c_a, .., c_b),   q = post_b(c_b) prod_n fa_n(c_n) W_n(c_n, c_n+1) / D_n(c_n+1),
+// the marginal of the run (everything outside [a, b] summed out).  It is k_region_prob's recursion in the max semiring: the
+// chain and the normaliser pass D(s') -- a SUM -- are the same, the second pass takes a maximum with its arg-maximum,
+//   g_b(s) = [mask] post_b(s),   h(s') = g_n+1(s') / D_n(s'),
+//   g_n(s) = [mask] fa_n(s) max_s' [label(s) == label(s')] W_n(s, s') h(s'),   bp_n(s) = the first s' that attains it,
+// P* = max_s g_a(s), c_a* the first s that attains it, c_n+1* = bp_n(c_n*).  g is divided by its maximum after every step
+// and the logarithms of the maxima are added up; every arg-maximum is taken on the values before that division, and every
+// tie goes to the lowest state index, so a (restart, query) result -- value and path -- does not depend on the launch.
+// A state whose fa entry underflowed to 0 in the sweep's scaled rows cannot be chosen (k_call_prob's caveat).
+// One workgroup of 256 threads per (restart, query), lane mappings as k_region_prob:
+//   Wb: D(s') for the compacted s' with 16 lanes per s' and the butterfly; then the thread owns s and walks the compacted s'
+//     in state order: a multiply, a compare and two selects per pair, "strictly greater replaces" keeps the first maximum,
+//     no cross-lane reduction, off-label weights not loaded;
+//   exp(trans_value): the thread owns s' in the D pass; 16 lanes per s stride s' in the max pass, each lane keeps its first
+//     maximum and the butterfly combines (value, index) pairs: the greater value wins, at equal value the lower index.
+// Back-pointers are int16 rows [S] of the workgroup's own strip of global scratch, bp[((ri * nq + query) * max_len + n - a) * S + s],
+// written by consecutive threads.  After the last step every wave waits for its stores, a barrier publishes them to the
+// workgroup, and thread 0 walks a -> b through the strip and writes the states; entries past the run are -1.
+// A D(s') that is 0 or not finite under g(s') > 0, or a step maximum that is not a finite number >= 0 (a NaN in g counts as one), sets
+// RGD_ERR_DENOM in flags[r] and gives NaN and states -1; a maximum of exactly 0 (an impossible event) gives -inf and states -1.
+// grid (queries, restarts), block RGN_NT; out[ri * nq + query], states[(ri * nq + query) * max_len + k].
+// =============================================================================
+#define RGD_ERR_DENOM 1u
+// maximum over the workgroup; every thread gets it (the barriers also publish what the callers wrote to LDS)
+__device__ inline double rgd_block_max(double v, double *red) {
+    v = group_max(v, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = red[0];
+#pragma unroll
+    for (int i = 1; i < RGN_NT / 64; i++) t = fmax(t, red[i]);
+    return t;
+}
+// minimum over the workgroup of an int; every thread gets it (once per query: not a hot path)
+__device__ inline int rgd_block_min(int v, int *ired) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) ired[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int t = ired[0];
+#pragma unroll
+    for (int i = 1; i < RGN_NT / 64; i++) t = min(t, ired[i]);
+    return t;
+}
+// one butterfly step of the (value, index) maximum over 16 lanes: the greater value wins, at equal value the lower index
+template <int CTRL> __device__ __forceinline__ void rgd_argmax_step(double &v, int &i) {
+    const double ov = dpp_mov_f64<CTRL>(v);
+    const int oi = __builtin_amdgcn_update_dpp(i, i, CTRL, 0xf, 0xf, false);
+    const bool take = ov > v || (ov == v && oi < i);
+    v = take ? ov : v;
+    i = take ? oi : i;
+}
+// takes the maximum M of a step: a bad D(s') of the step, or an M that is not a finite number >= 0, fails the query;
+// M == 0 makes logp -inf; else log M is added and the caller divides by M (returns true)
+__device__ __forceinline__ bool rgd_take_max(double M, bool bad, double &logp, bool &failed) {
+    if (bad || !(M >= 0. && M < INFINITY)) failed = true;
+    else if (M == 0.) logp = -INFINITY;
+    else {
+        logp += log(M);
+        return true;
+    }
+    return false;
+}
+__global__ __launch_bounds__(RGN_NT) void k_region_decode(Dev d, int r0, int use_wb, RgnArgs q, int max_len, int16_t *bp_all, int16_t *states, double *out,
+                                                          uint32_t *flags) {
+    __shared__ double g[RGN_MAXS], h[RGN_MAXS], fas[RGN_MAXS];
+    __shared__ double red[RGN_NT / 64];
+    __shared__ int16_t lab[2][RGN_MAXS], idx[RGN_MAXS];      // (idx: the compacted list on Wb; the step's back-pointers on exp(trans_value), which has no list)
+    __shared__ int ired[RGN_NT / 64];
+    __shared__ int nact, s_bad;
+    const int qi = blockIdx.x, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x;
+    const int grp = tid / RGN_GL, gl = tid % RGN_GL;
+    const int S = d.S;
+    const int a = q.queries[4 * qi], b = q.queries[4 * qi + 1], mi = q.queries[4 * qi + 2], li = q.queries[4 * qi + 3];
+    int16_t *bp = bp_all + ((size_t)ri * q.nq + qi) * (size_t)max_len * S;      // row n - a: the back-pointers of segment n
+    int16_t *path = states + ((size_t)ri * q.nq + qi) * (size_t)max_len;
+    if (tid == 0) s_bad = 0;
+    int cur = 0;              // lab[cur]: the labels of segment n + 1
+    double logp = 0.;
+    bool failed = false;
+    int first = -1;           // c_a*
+    // ---- start: g_b = [mask] post_b ---------------------------------------------------------------------
+    {
+        const double *post = d.post + rs_off(d, r, b);
+        const auto [mk, lb] = rgn_tabs(d, q, b, mi, li);
+        double part = 0.;
+        bool nan = false;
+        for (int s = tid; s < S; s += RGN_NT) {
+            const double v = (!mk || mk[s]) ? post[s] : 0.;
+            g[s] = v; part = fmax(part, v); nan |= v != v;
+            if (lb) lab[cur][s] = lb[s];
+        }
+        if (nan) part = INFINITY;      // (fmax drops a NaN: an infinite maximum fails the query)
+        const double M = rgd_block_max(part, red);
+        if (rgd_take_max(M, false, logp, failed)) {
+            if (a == b) {
+                int c = 0x7fffffff;
+                for (int s = tid; s < S; s += RGN_NT) if (g[s] == M) c = min(c, s);
+                first = rgd_block_min(c, ired);
+            }
+            for (int s = tid; s < S; s += RGN_NT) g[s] = g[s] / M;
+        }
+    }
+    for (int n = b - 1; n >= a && !failed && logp > -INFINITY; n--) {
+        const auto [wb, Wt, pd] = rgn_adj(d, r, n, use_wb);
+        const double *fa = d.fa + rs_off(d, r, n);
+        const auto [mk, lb] = rgn_tabs(d, q, n, mi, li);
+        const int16_t *lab1 = lab[cur];
+        int16_t *lab0 = lab[cur ^ 1];
+        int16_t *bpn = bp + (size_t)(n - a) * S;
+        for (int s = tid; s < S; s += RGN_NT) {
+            fas[s] = fa[s];
+            if (lb) lab0[s] = lb[s];
+        }
+        __syncthreads();
+        if (wb) {
+            // the states s' with g(s') > 0, in state order
+            const int na = rgn_compact(S, idx, nact, [&](int s) { return g[s] > 0.; });
+            // D(s') and h(s') = g(s') / D(s'): 16 lanes per s'
+            for (int j0 = 0; j0 < na; j0 += RGN_NT / RGN_GL) {
+                const int j = j0 + grp;
+                const bool ok = j < na;
+                const int sp = ok ? idx[j] : 0;
+                double p = 0.;
+                if (ok) {
+                    const double *wr = Wt + (size_t)sp * S;
+                    for (int s = gl; s < S; s += RGN_GL) p = fma(fas[s], wr[s], p);
+                }
+                const double D = group_sum(p, RGN_GL);
+                if (ok && gl == 0) {
+                    if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                    h[j] = g[sp] / D;
+                }
+            }
+            __syncthreads();
+            // g(s) and bp(s): the thread owns s and walks the s' in state order; strictly greater replaces
+            for (int s = tid; s < S; s += RGN_NT) {
+                double best = 0.;
+                int arg = 0;
+                if (!mk || mk[s]) {
+                    const int ls = lb ? lab0[s] : 0;
+                    const double *wc = Wt + s;
+#pragma unroll 4
+                    for (int j = 0; j < na; j++) {
+                        const int sp = idx[j];
+                        if (!lb || lab1[sp] == ls) {      // (off-label weights are not loaded)
+                            const double v = wc[(size_t)sp * S] * h[j];
+                            const bool up = v > best;
+                            best = up ? v : best;
+                            arg = up ? sp : arg;
+                        }
+                    }
+                    best *= fas[s];
+                }
+                g[s] = best;
+                bpn[s] = (int16_t)arg;
+            }
+        } else {
+            // D(s') and h(s'): the thread owns s'
+            for (int sp = tid; sp < S; sp += RGN_NT) {
+                const double gv = g[sp];
+                double hv = 0.;
+                if (gv > 0.) {
+                    const double D = rgn_D_exp(d, n, sp, fas, pd);
+                    if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                    hv = gv / D;
+                }
+                h[sp] = hv;
+            }
+            __syncthreads();
+            // g(s) and bp(s): 16 lanes per s, each keeps its first maximum; the butterfly breaks ties to the lower index
+            for (int s0 = 0; s0 < S; s0 += RGN_NT / RGN_GL) {
+                const int s = s0 + grp;
+                const bool ok = s < S && (!mk || mk[s]) && fas[s] != 0.;
+                double best = 0.;
+                int arg = 0;
+                if (ok) {
+                    const int ls = lb ? lab0[s] : 0;
+                    for (int sp = gl; sp < S; sp += RGN_GL) {
+                        const double hv = h[sp];
+                        if (hv != 0. && (!lb || lab1[sp] == ls)) {
+                            const double v = exp(trans_value(d, n, s, sp, pd)) * hv;
+                            const bool up = v > best;
+                            best = up ? v : best;
+                            arg = up ? sp : arg;
+                        }
+                    }
+                }
+                rgd_argmax_step<0xB1>(best, arg);       // xor 1
+                rgd_argmax_step<0x4E>(best, arg);       // xor 2
+                rgd_argmax_step<0x141>(best, arg);      // xor 4 (row_half_mirror on quad-uniform pairs)
+                rgd_argmax_step<0x140>(best, arg);      // xor 8 (row_mirror on half-row-uniform pairs)
+                if (s < S && gl == 0) {
+                    g[s] = ok ? best * fas[s] : 0.;
+                    idx[s] = (int16_t)(ok ? arg : 0);
+                }
+            }
+        }
+        __syncthreads();
+        double part = 0.;
+        bool nan = false;
+        for (int s = tid; s < S; s += RGN_NT) {
+            const double v = g[s];
+            part = fmax(part, v); nan |= v != v;
+            if (!wb) bpn[s] = idx[s];
+        }
+        if (nan) part = INFINITY;
+        const double M = rgd_block_max(part, red);
+        if (rgd_take_max(M, s_bad != 0, logp, failed)) {
+            if (n == a) {
+                int c = 0x7fffffff;
+                for (int s = tid; s < S; s += RGN_NT) if (g[s] == M) c = min(c, s);
+                first = rgd_block_min(c, ired);
+            }
+            for (int s = tid; s < S; s += RGN_NT) g[s] = g[s] / M;
+        }
+        cur ^= 1;
+    }
+    // ---- trace a -> b through the workgroup's own strip --------------------------------------------------
+    const bool have = !failed && logp > -INFINITY;
+    const int L = have ? b - a + 1 : 0;
+    for (int k = L + tid; k < max_len; k += RGN_NT) path[k] = -1;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's back-pointer stores have landed
+    __syncthreads();
+    if (tid == 0) {
+        if (have) {
+            int c = first;
+            path[0] = (int16_t)c;
+            for (int k = 0; k + 1 < L; k++) {
+                c = bp[(size_t)k * S + c];
+                path[k + 1] = (int16_t)c;
+            }
+        }
+        if (failed) atomicOr(&flags[r], RGD_ERR_DENOM);
+        out[(size_t)ri * q.nq + qi] = failed ? __builtin_nan("") : logp;
+    }
+}

@@ -71,6 +71,13 @@ cn_event_length_edges = ()
 # in the order of the experiment's `breakpoints` (remixt_amd/posteriors.py batch_breakend_changes).  False: off
 cn_breakend_changes = False
 
+# The most probable copy-number configuration of every region of cn_regions and its probability (rmx_region_decode, DESIGN
+# 4.17): every fit result also carries `region_calls` -- names, log_prob (the log-probability of the region's most probable
+# configuration under the structured posterior), log_prob_call (that of the result's own `cn` over the region) and n_differ
+# (the number of the region's segments where the two differ).  The configurations themselves come from region_call of the
+# model and restart classes.  Needs cn_regions.  False: off (results, records and stores unchanged)
+cn_region_calls = False
+
 
 def get_param(config, name):
     if config is not None and name in config:

@@ -1197,3 +1197,112 @@ def add_breakend_changes(res, changes):
     for k in BREAKEND_ARRAYS:
         res[k] = np.asarray(changes[k], dtype=float)
     return res
+
+
+# ---- the most probable configuration of a region, and its probability (rmx_region_decode) ----------------
+# the arrays of region_calls that go into fit results, records and stores (config cn_region_calls)
+REGION_CALL_ARRAYS = ('log_prob', 'log_prob_call', 'n_differ')
+
+
+def parse_call_event(event):
+    """event of region_call: None, or (mask name or None, label name or None) over MASK_NAMES / LABEL_NAMES -> the
+    (mask index or -1, label index or -1) of a region query."""
+    if event is None:
+        return -1, -1
+    mask, label = event
+    if mask is not None and mask not in MASK_NAMES:
+        raise ValueError('unknown mask %r: one of %s' % (mask, ', '.join(MASK_NAMES)))
+    if label is not None and label not in LABEL_NAMES:
+        raise ValueError('unknown label %r: one of %s' % (label, ', '.join(LABEL_NAMES)))
+    return (-1 if mask is None else MASK_NAMES.index(mask)), (-1 if label is None else LABEL_NAMES.index(label))
+
+
+def batch_region_calls(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, event=None, cn=None):
+    """The most probable copy-number configuration of every region under the structured posterior, and its probability,
+    for restarts r0 .. r0+nr-1 of a RemixtBatch from one device call per kernel (rmx_region_decode; rmx_region_prob with
+    an event; rmx_call_prob with a call).  regions: (first, last) or (name, first, last) experiment segment indices, split
+    at chain ends into pieces as region_queries does it, with constrain = seg_is_original: a mask binds real segments
+    only, a label every adjacency of a run.  event: None, or (mask name or None, label name or None): the configuration is
+    then the most probable one in which the event holds.  A dict of
+      cn                    a list over restarts of lists over regions of int arrays (segments of the region, M, 2): the
+                            copy numbers of the region's segments through the state tables, its pieces in different chains
+                            concatenated (-1 everywhere where the event is impossible);
+      log_prob              (nr, R) the log-probability of that configuration of the region's model segments -- the zero-length
+                            segments inserted inside it included --, summed over the pieces: chains are independent;
+      log_p_event           (nr, R) log P(event) over the same pieces, 0 without an event;
+      log_prob_given_event  (nr, R) log_prob - log_p_event, at most 0;
+    and, with a call cn -- int (nr, N1) state indices in model segment order, as states_in_model_order gives them --,
+      n_differ              int (nr, R) the number of the region's segments where the configuration differs from the call
+                            (-1 where the event is impossible);
+      log_prob_call         (nr, R) the log-probability that the path takes the call's states at every segment of the region
+                            (batch_call_confidence's p_call as a logarithm; inserted segments are marginalised there, so it
+                            can exceed log_prob where a region holds some)."""
+    mi, li = parse_call_event(event)
+    reg = np.array([[int(r[-2]), int(r[-1])] for r in regions], dtype=np.int64).reshape(-1, 2)
+    masks, labels = event_tables(batch.cn_classes)
+    cs, ce = chains_from_telomeres(is_telomere)
+    runs, piece_region, constrain = region_queries(reg, seg_fwd_remap, seg_is_original, cs, ce)
+    P, R = len(runs), len(reg)
+    fwd = np.asarray(seg_fwd_remap, dtype=np.int64)
+    classes, seg_class = np.asarray(batch.cn_classes), np.asarray(batch.seg_class)
+    out = {'cn': [[] for _ in range(nr)], 'log_prob': np.zeros((nr, R)), 'log_p_event': np.zeros((nr, R)), 'log_prob_given_event': np.zeros((nr, R))}
+    if cn is not None:
+        out['n_differ'] = np.zeros((nr, R), dtype=np.int64)
+        out['log_prob_call'] = np.zeros((nr, R))
+    if P == 0:
+        return out
+    q = np.zeros((P, 4), dtype=np.int32)
+    q[:, :2], q[:, 2], q[:, 3] = runs, mi, li
+    logp, states = batch.region_decode_raw(r0, nr, q, masks, labels, constrain)
+    with np.errstate(invalid='ignore'):
+        out['log_prob'] = combine(logp, piece_region, R)
+        if event is not None:
+            out['log_p_event'] = np.minimum(combine(batch.region_logprob_raw(r0, nr, q, masks, labels, constrain), piece_region, R), 0.)
+        # (-inf - -inf: an impossible event has no conditional; a maximum is not above the sum, up to rounding)
+        given = out['log_prob'] - out['log_p_event']
+    out['log_prob_given_event'] = np.where(np.isnan(given), np.nan, np.minimum(given, 0.))
+    call = None
+    if cn is not None:
+        call = np.asarray(cn).reshape(nr, -1)
+        qc = q.copy()
+        qc[:, 2], qc[:, 3] = LABEL_NAMES.index('state'), 0
+        lpc = batch.call_logprob_raw(r0, nr, call[:, None], qc, labels, constrain)
+        out['log_prob_call'] = np.minimum(combine(lpc, piece_region, R), 0.)
+    # states of a region's pieces -> model segment order -> the region's own segments
+    full = np.full(len(seg_class), -1, dtype=np.int64)
+    for r in range(nr):
+        for k in range(R):
+            seg = fwd[reg[k, 0]:reg[k, 1] + 1]
+            full[seg] = -1
+            ok = True
+            for p in np.flatnonzero(piece_region == k):
+                a, b = int(runs[p, 0]), int(runs[p, 1])
+                full[a:b + 1] = states[r, p, :b - a + 1]
+                ok = ok and np.isfinite(logp[r, p])
+            st = full[seg]
+            ok = ok and (st >= 0).all()
+            out['cn'][r].append(classes[seg_class[seg], st] if ok else np.full((len(seg),) + classes.shape[2:], -1, dtype=classes.dtype))
+            if call is not None:
+                out['n_differ'][r, k] = int((st != call[r, seg]).sum()) if ok else -1
+    return out
+
+
+def add_region_calls(res, names, calls):
+    """Fit result dict `res` gains `region_calls` (config cn_region_calls): the region names and the three arrays of
+    REGION_CALL_ARRAYS, (len(names),) each: the log-probability of the region's most probable configuration, that of the
+    result's own call over the region, and the number of segments where the two differ.  (The configurations themselves
+    come from region_call.)"""
+    out = {'names': list(names)}
+    for k in REGION_CALL_ARRAYS:
+        out[k] = np.asarray(calls[k], dtype=float)
+    res['region_calls'] = out
+    return res
+
+
+def region_calls_on(config):
+    """Config value cn_region_calls, checked: it needs cn_regions."""
+    from . import defaults
+    on = bool(defaults.get_param(config, 'cn_region_calls'))
+    if on and defaults.get_param(config, 'cn_regions') is None:
+        raise ValueError('cn_region_calls needs cn_regions')
+    return on

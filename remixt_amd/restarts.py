@@ -749,6 +749,18 @@ class RestartSet(object):
             out = posteriors.batch_breakend_changes(self.batch, 0, len(self.models), m.breakpoint_idx, m.num_breakpoints, m.is_telomere, m.seg_is_original)
         return out if arrays else dict((bp, dict((k, v[:, i]) for k, v in out.items())) for i, bp in enumerate(m.breakpoints))
 
+    def region_call(self, regions, event=None, cn=None):
+        """BreakpointModel.region_call of every restart from one device call per kernel: `cn` a list over restarts of lists over
+        regions, the arrays (restarts, len(regions)).  cn: the restarts' calls in experiment order (the `cn` of results());
+        None: the decoded paths."""
+        from . import posteriors
+        if self.batch is None or not hasattr(self.batch, 'region_decode_raw'):
+            per = [m.region_call(regions, event, None if cn is None else cn[r]) for r, m in enumerate(self.models)]
+            return dict((k, [p[k] for p in per] if k == 'cn' else np.stack([p[k] for p in per])) for k in per[0])
+        m = self.models[0]
+        return posteriors.batch_region_calls(self.batch, 0, len(self.models), regions, m.seg_fwd_remap, m.seg_is_original, m.is_telomere,
+                                             event=event, cn=self._call_states(cn))
+
     def _call_states(self, cn):
         """int16 (restarts, N1): the restarts' calls as state indices in model segment order.  cn: their paths in
         experiment order (the `cn` of results()); None: the decoded paths."""
@@ -956,6 +968,11 @@ class RestartGroups(object):
         out = dict((k, np.concatenate([p[k] for p in parts])) for k in parts[0])
         return out if arrays else dict((bp, dict((k, v[:, i]) for k, v in out.items())) for i, bp in enumerate(self.sets[0].models[0].breakpoints))
 
+    def region_call(self, regions, event=None, cn=None):
+        """RestartSet.region_call over the groups, restarts in order (cn: of all restarts)."""
+        parts = self._map(lambda rs: rs.region_call(regions, event, None if cn is None else cn[self.slices[self.sets.index(rs)]]))
+        return dict((k, [x for p in parts for x in p[k]] if k == 'cn' else np.concatenate([p[k] for p in parts])) for k in parts[0])
+
     def call_confidence(self, regions, cn=None):
         """RestartSet.call_confidence over the groups, restarts in order (cn: of all restarts): a dict of arrays (restarts, len(regions))."""
         parts = self._map(lambda rs: rs.call_confidence(regions, None if cn is None else cn[self.slices[self.sets.index(rs)]]))
@@ -1093,6 +1110,10 @@ class DatasetGroups(object):
         """RestartGroups.breakend_changes of every dataset: a list, one dict per dataset."""
         return self._map(lambda part: part.breakend_changes(arrays))
 
+    def region_call(self, regions, event=None):
+        """RestartGroups.region_call of every dataset: a list, one dict per dataset."""
+        return self._map(lambda part: part.region_call(regions, event))
+
     def call_confidence(self, regions, cn=None):
         """RestartGroups.call_confidence of every dataset (cn: per dataset, a list of its restarts' paths): a list, one dict of arrays
         (restarts, len(regions)) per dataset."""
@@ -1223,7 +1244,7 @@ def _section(fields, group=None, head=(), tail=(), add=None):
 
 
 def _record_sections(N, M, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0, call_confidence=False, cn_moments=False,
-                     extent_names=None, length_edges=None, breakend_k=None):
+                     extent_names=None, length_edges=None, breakend_k=None, region_calls=False):
     """The optional sections of a float record, in record order.  The record is the fixed part -- header, h, parameters,
     outlier probabilities: _HDR + M + nparams + 4 N floats -- and then, each only when its option is on (a record without
     it is unchanged), at offsets that are the running sum of what precedes:
@@ -1239,7 +1260,9 @@ def _record_sections(N, M, cn_samples=False, cn_posterior=False, region_names=No
       event lengths (cn_event_lengths, with extents; length_edges: the number of cn_event_length_edges): the four arrays of
         posteriors.SPAN_ARRAYS, one entry per named anchor, then the two tables of posteriors.SPAN_EDGE_ARRAYS, (entries, edges);
       breakend changes (cn_breakend_changes; breakend_k: the number of breakpoints K): the five arrays of
-        posteriors.BREAKEND_ARRAYS, p_change (K, 2) and four (K,): 6 K floats."""
+        posteriors.BREAKEND_ARRAYS, p_change (K, 2) and four (K,): 6 K floats;
+      region calls (cn_region_calls, with regions): the three arrays of posteriors.REGION_CALL_ARRAYS, one entry per region
+        (n_differ as a float: exact)."""
     from . import sampling
     out = []
     if cn_samples:
@@ -1269,14 +1292,17 @@ def _record_sections(N, M, cn_samples=False, cn_posterior=False, region_names=No
                                 'event_lengths', add=lambda res, a: posteriors.add_event_lengths(res, extent_names, a)))
     if breakend_k is not None:
         out.append(_section([(k, (int(breakend_k), 2) if k == 'p_change' else (int(breakend_k),)) for k in posteriors.BREAKEND_ARRAYS]))
+    if region_calls and region_names is not None:
+        out.append(_section([(k, (len(region_names),)) for k in posteriors.REGION_CALL_ARRAYS], 'region_calls',
+                            add=lambda res, a: posteriors.add_region_calls(res, region_names, a)))
     return out
 
 
 def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0, call_confidence=False,
-          cn_moments=False, extent_names=None, length_edges=None, breakend_changes=False):
+          cn_moments=False, extent_names=None, length_edges=None, breakend_changes=False, region_calls=False):
     """One restart's results as (float64 vector, int8 vector) of fixed length."""
     sections = _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names, length_edges,
-                                K if breakend_changes else None)
+                                K if breakend_changes else None, region_calls)
     o = _HDR + M + nparams
     f = np.zeros(o + 4 * N + sum(s.length for s in sections), dtype=np.float64)
     st = res['stats']
@@ -1298,9 +1324,9 @@ def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_post
 
 
 def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0,
-            call_confidence=False, cn_moments=False, extent_names=None, length_edges=None, breakend_changes=False):
+            call_confidence=False, cn_moments=False, extent_names=None, length_edges=None, breakend_changes=False, region_calls=False):
     sections = _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names, length_edges,
-                                K if breakend_changes else None)
+                                K if breakend_changes else None, region_calls)
     res = dict()
     res['h'] = f[_HDR:_HDR + M].copy()
     o = _HDR + M + nparams
@@ -1328,7 +1354,7 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
                              device=None, kernel_module=None, seeds=None, quiet=True, groups=2, num_cn_samples=0, cn_sample_seed=0,
                              cn_posterior_summary=False, cn_regions=None, cn_region_change_bins=0, cn_call_confidence=False, cn_region_moments=False,
                              cn_event_extents=None, cn_extent_window=64, cn_event_lengths=False, cn_event_length_edges=(), cn_breakend_changes=False,
-                             **model_kwargs):
+                             cn_region_calls=False, **model_kwargs):
     """Fit all restarts across the ranks of the default torch.distributed group.
 
     Every rank holds the (small, read-only) experiment; rank g fits restarts
@@ -1353,10 +1379,14 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
     the records grow by 4 + 2 len(cn_event_length_edges) floats per entry.
     cn_breakend_changes: every result also carries the five arrays of posteriors.BREAKEND_ARRAYS over the breakpoints
     (posteriors.add_breakend_changes), and the records grow by six floats per breakpoint.
+    cn_region_calls (with cn_regions): every result also carries `region_calls` (posteriors.add_region_calls), and the
+    records grow by three floats per region.
     """
     import torch
     import torch.distributed as dist
     posteriors.check_region_options(cn_regions, cn_region_change_bins, cn_call_confidence, cn_region_moments)
+    if cn_region_calls and cn_regions is None:
+        raise ValueError('cn_region_calls needs cn_regions')
     extents = posteriors.extents_on({'cn_event_extents': cn_event_extents, 'cn_extent_window': cn_extent_window}, len(experiment.x))
     lengths = posteriors.lengths_on({'cn_event_extents': cn_event_extents, 'cn_extent_window': cn_extent_window, 'cn_event_lengths': cn_event_lengths,
                                      'cn_event_length_edges': cn_event_length_edges}, len(experiment.x))
@@ -1376,7 +1406,7 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
         rs.fit(num_em_iter, num_update_iter)
         local = rs.results()
         add_optional_outputs(rs, local, experiment, mine, num_cn_samples, cn_sample_seed, cn_posterior_summary, cn_regions, cn_region_change_bins, cn_call_confidence,
-                             cn_region_moments, cn_event_extents, cn_extent_window, cn_event_lengths, cn_event_length_edges, cn_breakend_changes)
+                             cn_region_moments, cn_event_extents, cn_extent_window, cn_event_lengths, cn_event_length_edges, cn_breakend_changes, cn_region_calls)
         param_names = list(rs.models[0].likelihood_params)
         rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     if param_names is None:
@@ -1388,7 +1418,7 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
                                  region_names=None if cn_regions is None else [str(r[0]) for r in cn_regions], change_bins=cn_region_change_bins,
                                  call_confidence=bool(cn_call_confidence), cn_moments=bool(cn_region_moments),
                                  extent_names=None if extents is None else extents[0], length_edges=None if lengths is None else len(lengths[4]),
-                                 breakend_changes=bool(cn_breakend_changes))
+                                 breakend_changes=bool(cn_breakend_changes), region_calls=bool(cn_region_calls))
 
 
 def add_region_events(rs, results, cn_regions):
@@ -1464,6 +1494,16 @@ def add_breakend_changes(rs, results):
     return results
 
 
+def add_region_calls(rs, results, cn_regions):
+    """Add the region calls of config cn_regions / cn_region_calls of every restart of `rs` (a RestartSet / RestartGroups; one
+    device call per batch and kernel), against results[r]['cn'], to results[r] (posteriors.add_region_calls)."""
+    names, regions = posteriors.parse_regions(cn_regions)
+    calls = rs.region_call(regions, None, [res['cn'] for res in results])
+    for r, res in enumerate(results):
+        posteriors.add_region_calls(res, names, dict((k, calls[k][r]) for k in posteriors.REGION_CALL_ARRAYS))
+    return results
+
+
 def add_posterior_summaries(rs, results, experiment):
     """Add the exact posterior summary of every restart of `rs` (a RestartSet / RestartGroups; one device call per
     batch) to results[r] (posteriors.add_posterior_summary); cn_posterior_prob is taken at results[r]['cn']."""
@@ -1486,7 +1526,7 @@ def add_cn_sample_summaries(rs, results, experiment, num_samples, seed, init_ids
 
 def add_optional_outputs(rs, results, experiment, init_ids, num_cn_samples=0, cn_sample_seed=0, cn_posterior_summary=False, cn_regions=None,
                          cn_region_change_bins=0, cn_call_confidence=False, cn_region_moments=False, cn_event_extents=None, cn_extent_window=64,
-                         cn_event_lengths=False, cn_event_length_edges=(), cn_breakend_changes=False):
+                         cn_event_lengths=False, cn_event_length_edges=(), cn_breakend_changes=False, cn_region_calls=False):
     """Add the optional outputs of a fit -- the config values of the same names -- of every restart of the fitted `rs` (a
     RestartSet / RestartGroups) to results[r]; init_ids[r] selects restart r's posterior-sample stream.  The combination is
     checked before the fit (posteriors.check_region_options)."""
@@ -1508,12 +1548,14 @@ def add_optional_outputs(rs, results, experiment, init_ids, num_cn_samples=0, cn
             add_event_lengths(rs, results, cn_event_extents, cn_extent_window, tuple(cn_event_length_edges))
     if cn_breakend_changes:
         add_breakend_changes(rs, results)
+    if cn_region_calls and cn_regions is not None:
+        add_region_calls(rs, results, cn_regions)
     return results
 
 
 def gather_result_records(local, experiment, init_params, num_clones, param_names, device=None, timing=None, local_ids=None, cn_samples=False,
                           cn_posterior=False, region_names=None, change_bins=0, call_confidence=False, cn_moments=False, extent_names=None,
-                          length_edges=None, breakend_changes=False):
+                          length_edges=None, breakend_changes=False, region_calls=False):
     """The one collective of the path: every rank contributes the fixed-size records of the restarts
     it fitted (`local`, in the order of shard_indices) -- one float64 record (ELBO, h, parameters, outlier
     probabilities, failure code) and one int8 record (cn, brk_cn, masks) per restart -- and every rank gets the
@@ -1542,12 +1584,12 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
             per_rank = int(cnt_.item())
     if len(local) > per_rank:
         raise ValueError('gather_result_records: %d local results for a share of %d (pass local_ids for shares that are not shard_indices\')' % (len(local), per_rank))
-    flen = _HDR + M + nparams + 4 * N + sum(s.length for s in _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names, length_edges, K if breakend_changes else None))
+    flen = _HDR + M + nparams + 4 * N + sum(s.length for s in _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names, length_edges, K if breakend_changes else None, region_calls))
     ilen = N * M * 2 + K * M + 2 * N
     fbuf = np.full((per_rank, flen), np.nan); ibuf = np.zeros((per_rank, ilen), dtype=np.int8)
     for j, res in enumerate(local):
         fbuf[j], ibuf[j] = _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments,
-                                  extent_names, length_edges, breakend_changes)
+                                  extent_names, length_edges, breakend_changes, region_calls)
     if local_ids is not None:
         ids_t = np.full((per_rank,), -1, dtype=np.int64); ids_t[:len(local_ids)] = local_ids
     t0 = time.perf_counter()
@@ -1580,7 +1622,7 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
         ids_g = shard_indices(len(init_params), world, g) if ids_all is None else [int(i) for i in ids_all[g] if i >= 0]
         for j, i in enumerate(ids_g):
             results[i] = _unpack(fall[g][j], iall[g][j], N, M, K, nparams, brk_ids, param_names, init_params[i], cn_samples, cn_posterior, region_names, change_bins, call_confidence,
-                                 cn_moments, extent_names, length_edges, breakend_changes)
+                                 cn_moments, extent_names, length_edges, breakend_changes, region_calls)
     return results
 
 

@@ -394,6 +394,25 @@ int rmx_region_prob(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int3
 int rmx_region_counts(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
                       int32_t nlabel, const int16_t *labels, const uint8_t *constrain, int32_t nbins, double *logp_out);
 
+/* -- region extremes (no reference counterpart) -------------------------------- */
+/* log-probabilities that a per-state integer level stays at or below each of ncol nested thresholds over runs of model
+ * segments: the CDF of a region's peak copy number, or, with a reflected level table, of its lowest.
+ * Queries, masks and constrain are those of rmx_region_prob, but field 3 of a query is a level index (>= 0) and there is no
+ * label constraint.  Column j of query i is
+ *   log P(c_n in mask and level(c_n) <= j at every n in [a, b] with constrain[n] != 0),   j = 0 .. ncol-1;
+ * a state whose level is ncol or more is in no column, and neither mask nor level binds where constrain[n] is 0.  In
+ * real arithmetic the columns do not decrease in j.  One walk of the run serves every column.  The model is not modified.
+ *   levels    int16 [C][nlevel][S], every entry >= 0, one table per state class
+ *   ncol      1 .. 16
+ *   logp_out  [nr][nq][ncol]; -inf for a column that cannot happen.  Every column carries its own scale: a column is
+ *             not lost below 1e-308 of another (rmx_region_counts' bins are)
+ * A (restart, query) result is bit-identical in any restart range and any batch of queries.  Errors as rmx_region_prob,
+ * and RMX_EARG with nothing launched for ncol outside [1, 16], a level index outside [0, nlevel) or a negative level
+ * entry.  RMX_EASSERT: every column of the failing query is NaN.  RMX_EUNSUPPORTED: more than 1024 states (the bound of
+ * the kernel's LDS plan: 140 bytes per state rounded up to 16 states). */
+int rmx_region_extremes(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
+                        int32_t nlevel, const int16_t *levels, const uint8_t *constrain, int32_t ncol, double *logp_out);
+
 /* -- call probabilities (no reference counterpart) ---------------------------- */
 /* log-probabilities that the copy-number path agrees with a reference path over runs of model segments, under the
  * structured posterior q of the last update_p_cn of restarts r0 .. r0+nr-1.  Query i = (a, b, label index or

@@ -38,6 +38,7 @@ def fit(experiment, init_params, config, device=0, quiet=False, init_id=0):
     extents = posteriors.extents_on(config, len(experiment.x))
     lengths = posteriors.lengths_on(config, len(experiment.x))
     region_calls = posteriors.region_calls_on(config)
+    region_extremes = posteriors.region_extremes_on(config)
     h_init = np.array([
         init_params['h_normal'],
         init_params['h_tumour'] * init_params['mix_frac'],
@@ -85,6 +86,8 @@ def fit(experiment, init_params, config, device=0, quiet=False, init_id=0):
             posteriors.add_region_cn_moments(res, names, model.region_cn_moments(posteriors.genome_region(regions, len(res['cn']))))
         if region_calls:
             posteriors.add_region_calls(res, names, model.region_call(regions, None, res['cn']))
+        if region_extremes:
+            posteriors.add_region_cn_extremes(res, names, model.region_clone_extremes(regions, posteriors.EXTREME_BINS))
     if extents is not None:
         names, anchors, events, window = extents
         one = posteriors.grouped_event_extents(lambda a, ev, w: [model.event_extent(a, ev, w)], anchors, events, window)
@@ -129,6 +132,7 @@ def fit_restarts(experiment, init_params_by_id, config, device=0, quiet=True, se
     posteriors.extents_on(config, len(experiment.x))
     lengths = posteriors.lengths_on(config, len(experiment.x))
     region_calls = posteriors.region_calls_on(config)
+    region_extremes = posteriors.region_extremes_on(config)
     ids = sorted(init_params_by_id)
     params = [init_params_by_id[i] for i in ids]
     max_cn = defaults.get_param(config, 'max_copy_number')
@@ -143,7 +147,8 @@ def fit_restarts(experiment, init_params_by_id, config, device=0, quiet=True, se
     results = add_optional_outputs(rs, rs.results(), experiment, ids, defaults.get_param(config, 'num_cn_samples'), defaults.get_param(config, 'cn_sample_seed'),
                                    defaults.get_param(config, 'cn_posterior_summary'), defaults.get_param(config, 'cn_regions'), bins, call_conf, moments,
                                    defaults.get_param(config, 'cn_event_extents'), defaults.get_param(config, 'cn_extent_window'),
-                                   lengths is not None, () if lengths is None else lengths[4], defaults.get_param(config, 'cn_breakend_changes'), region_calls)
+                                   lengths is not None, () if lengths is None else lengths[4], defaults.get_param(config, 'cn_breakend_changes'), region_calls,
+                                   region_extremes)
     out = dict(zip(ids, results))
     rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     return out
@@ -317,6 +322,10 @@ def store_fit_results(store, experiment, fit_results, key_prefix):
     if 'region_calls' in fit_results:             # (config cn_region_calls)
         for k in posteriors.REGION_CALL_ARRAYS:
             store[key_prefix + '/region_call_' + k] = pd.Series(np.asarray(fit_results['region_calls'][k]))
+    if 'region_cn_extremes' in fit_results:       # (config cn_region_extremes: a row per region, the clones' bins side by side)
+        for k in posteriors.EXTREME_ARRAYS:
+            v = np.asarray(fit_results['region_cn_extremes'][k])
+            store[key_prefix + '/region_' + k] = pd.DataFrame(v.reshape(len(v), -1))
     if 'p_change_both' in fit_results:            # (config cn_breakend_changes)
         store[key_prefix + '/breakend_p_change'] = pd.DataFrame(np.asarray(fit_results['p_change']))
         for k in posteriors.BREAKEND_ARRAYS[1:]:

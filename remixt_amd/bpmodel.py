@@ -650,6 +650,20 @@ class RemixtBatch(object):
         self._ck(self._lib.rmx_region_counts(self._handle, r0, nr, *args, nbins, obuf.ctypes.data_as(_dp)))
         return out
 
+    def region_extremes_raw(self, r0, nr, queries, masks, levels, constrain, ncol):
+        """log-probabilities (nr, nq, ncol) that a per-state integer level stays at or below each of ncol nested
+        thresholds over runs of model segments, under the structured posterior of the last update_p_cn of restarts
+        r0 .. r0+nr-1 (rmx_region_extremes).  queries and masks as region_logprob_raw, but field 3 of a query is a level
+        index; levels int (C, nlevel, S), every entry >= 0; constrain (N,), whether mask and level bind at the segment
+        (None: everywhere).  Column j of a query is log P(state in mask and level(state) <= j at every constrained segment
+        of the run); -inf for a column that cannot happen.  Every column has its own scale.  ncol in 1 .. 16."""
+        r0, nr, ncol = int(r0), int(nr), int(ncol)
+        q, args, _keep = self._region_args(queries, masks, levels, constrain)
+        out = np.zeros((max(nr, 0), q.shape[0], max(ncol, 0)), dtype=np.float64)
+        obuf = out if out.size else np.zeros(1)
+        self._ck(self._lib.rmx_region_extremes(self._handle, r0, nr, *args, ncol, obuf.ctypes.data_as(_dp)))
+        return out
+
     def call_logprob_raw(self, r0, nr, paths, queries, labels=None, constrain=None):
         """log-probabilities (nr, nq) that the copy-number path agrees with a reference path over runs of model segments,
         under the structured posterior of the last update_p_cn of restarts r0 .. r0+nr-1 (rmx_call_prob).  paths int
@@ -1005,6 +1019,10 @@ class RemixtModel(object):
     def region_counts(self, queries, masks, labels, constrain, nbins):
         """RemixtBatch.region_counts_raw of this model: log-probabilities (nq, nbins)."""
         return self._batch.region_counts_raw(self._r, 1, queries, masks, labels, constrain, nbins)[0]
+
+    def region_extremes(self, queries, masks, levels, constrain, ncol):
+        """RemixtBatch.region_extremes_raw of this model: log-probabilities (nq, ncol)."""
+        return self._batch.region_extremes_raw(self._r, 1, queries, masks, levels, constrain, ncol)[0]
 
     def region_moments(self, queries, features, weights, nf):
         """RemixtBatch.region_moments_raw of this model: means and covariances (nq, nf + nf (nf + 1) / 2)."""

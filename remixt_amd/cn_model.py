@@ -763,6 +763,32 @@ class BreakpointModel(object):
                                                     self.is_telomere, bins=bins)
         return dict((k, v[0]) for k, v in out.items())
 
+    def region_cn_extremes(self, regions, quantity='total', clone='any', bins=16, first_level=0):
+        """Exact posterior distribution, under the structured posterior of the last variational update, of the highest and of
+        the lowest copy number inside regions ((first, last) experiment segment indices): is the region amplified, how high
+        does it go, how deep is its deepest loss.  quantity: 'total', 'major' or 'minor'; clone: a tumour clone 1 .. M-1 or
+        'any'; the window of copy numbers is first_level .. first_level + bins - 1.  A dict of `bins`, `first_level`, arrays
+        (len(regions), bins) `peak_cdf`, `peak_pmf`, `floor_cdf` (P(lowest >= k)) and `floor_pmf`, and int arrays
+        (len(regions),) `peak_q05/q50/q95` and `floor_q05/q50/q95` (posteriors.batch_region_cn_extremes;
+        posteriors.amplification_prob gives P(peak >= threshold))."""
+        from . import posteriors
+        if not hasattr(self.model, 'region_extremes'):
+            raise NotImplementedError('kernel module %s has no region extremes' % getattr(self._kernel_module(), '__name__', '?'))
+        out = posteriors.batch_region_cn_extremes(self.model._batch, self.model._r, 1, regions, self.seg_fwd_remap, self.seg_is_original,
+                                                  self.is_telomere, quantity=quantity, clone=clone, bins=bins, first_level=first_level)
+        return dict((k, v[0] if isinstance(v, np.ndarray) else v) for k, v in out.items())
+
+    def region_clone_extremes(self, regions, bins=16):
+        """The distributions of the peak and of the lowest total copy number of every tumour clone over regions, from one
+        device call: a dict of `peak_total_pmf` and `floor_total_pmf`, (len(regions), M - 1, bins) each, window 0 .. bins - 1
+        (what config cn_region_extremes adds to a fit result)."""
+        from . import posteriors
+        if not hasattr(self.model, 'region_extremes'):
+            raise NotImplementedError('kernel module %s has no region extremes' % getattr(self._kernel_module(), '__name__', '?'))
+        out = posteriors.batch_clone_extremes(self.model._batch, self.model._r, 1, regions, self.seg_fwd_remap, self.seg_is_original,
+                                              self.is_telomere, bins=bins)
+        return dict((k, v[0]) for k, v in out.items())
+
     def region_cn_moments(self, regions):
         """Exact posterior mean and covariance, under the structured posterior of the last variational update, of copy
         number over regions ((first, last) experiment segment indices): a dict of `length` (R,), `total_cn_mean` (R, M) and

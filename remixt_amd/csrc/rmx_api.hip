@@ -40,17 +40,18 @@ static inline long long now_ns() { return std::chrono::duration_cast<std::chrono
 enum KernelId {
     KID_STATE_TABLES = 0, KID_SEG_CONST, KID_FRAMELOGPROB, KID_FB, KID_MARGINALS, KID_MARGINALS_AB, KID_OUTLIER_TOTAL,
     KID_OUTLIER_ALLELE, KID_ALLELE_SWAP, KID_BRK_LUT, KID_PAIRWISE, KID_BRK_UPDATE, KID_ELBO_SEG, KID_ELBO_FINAL,
-    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_POST_SUMMARY, KID_REGION, KID_REGION_COUNTS, KID_CALL_PROB, KID_REGION_MOMENTS, KID_REGION_EXTENT, KID_REGION_SPAN, KID_REGION_PATTERN, KID_REGION_DECODE, KID_COUNT
+    KID_ELL_LIST, KID_ELL_FINAL, KID_ELL_FULL, KID_VITERBI, KID_BACKTRACE, KID_OTHER, KID_SAMPLE, KID_POST_SUMMARY, KID_REGION, KID_REGION_COUNTS, KID_CALL_PROB, KID_REGION_MOMENTS, KID_REGION_EXTENT, KID_REGION_SPAN, KID_REGION_PATTERN, KID_REGION_DECODE, KID_REGION_EXTREMES, KID_COUNT
 };
 static const char *kKernelNames[KID_COUNT] = {
     "k_state_tables", "k_seg_const", "k_framelogprob", "k_fb", "k_marginals<true>", "k_marginals<false>", "k_update_outlier_total",
     "k_update_outlier_allele", "k_update_allele_swap", "k_brk_lut", "k_pairwise", "k_brk_update", "k_elbo_seg", "k_elbo_final",
-    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn", "k_posterior_summary", "k_region_prob", "k_region_counts", "k_call_prob", "k_region_moments", "k_region_extent", "k_region_span", "k_region_pattern", "k_region_decode"};
+    "k_ell_list", "k_ell_final", "k_ell_full", "k_viterbi", "k_backtrace", "other", "k_sample_cn", "k_posterior_summary", "k_region_prob", "k_region_counts", "k_call_prob", "k_region_moments", "k_region_extent", "k_region_span", "k_region_pattern", "k_region_decode", "k_region_extremes"};
 // (ids are appended, never reordered: profiles written by earlier builds keep their meaning.  Before k_region_span the two lists ended
 //  `KID_REGION_MOMENTS, KID_REGION_EXTENT, KID_COUNT` and `"k_region_moments", "k_region_extent"};`, which tests/test_region_extent_cpu.py pins;
 //  before k_region_pattern they ended `"k_region_extent", "k_region_span"};` and, at a line end,
 //  KID_REGION_EXTENT, KID_REGION_SPAN, KID_COUNT
-//  which tests/test_region_span_cpu.py pins; before k_region_decode they ended with KID_REGION_PATTERN and "k_region_pattern")
+//  which tests/test_region_span_cpu.py pins; before k_region_decode they ended with KID_REGION_PATTERN and "k_region_pattern";
+//  before k_region_extremes with KID_REGION_DECODE and "k_region_decode", which tests/test_region_decode_cpu.py pins as the entry after k_region_pattern)
 
 struct ProfRec { int id; hipEvent_t a, b; };
 
@@ -3270,6 +3271,34 @@ int rmx_region_counts(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const in
                        [&](const Dev &dv, int r, int n, int, int use_wb, const int32_t *dq, int nqc, double *out, uint32_t *flags) {
         ra.queries = dq; ra.nq = nqc;
         hipLaunchKernelGGL(kf, dim3((unsigned)nqc, n), dim3(RGN_NT), lds, b->stream, dv, r, use_wb, ra, (int)nbins, out, flags);
+    });
+}
+
+// Region extremes (k_region_extremes): rmx_region_prob's mask event intersected with "level <= j at every bound segment" for the
+// ncol nested thresholds j, one walk for all of them and a scale per column.  Field 3 of a query names a level table; the
+// tables travel where the label tables of the siblings do (RgnArgs.labels / nlabel).  No entry of a level table may be negative
+// (rmxh::check_levels): a negative level would be admitted by every column.
+int rmx_region_extremes(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
+                        int32_t nlevel, const int16_t *levels, const uint8_t *constrain, int32_t ncol, double *logp_out) { BIND(b);
+    int rc;
+    if ((rc = check_region_call(b, "region_extremes", r0, nr, nq, queries, logp_out))) return rc;
+    if (!rmxh::extremes_ncol_ok(ncol)) return fail(RMX_EARG, "region_extremes: the number of columns must be in [1, 16]");
+    if ((rc = check_mask_label_tables("region_extremes", nmask, masks, nlevel, levels))) return rc;
+    if (b->d.S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "region_extremes: more than 1024 states");
+    if ((rc = check_queries(b, "region_extremes", nq, queries, {-1, nmask, "region_extremes: mask index out of range"},
+                            {0, nlevel, "region_extremes: a query needs a level index in [0, nlevel)"}))) return rc;
+    if (rmxh::check_levels(b->d.C, nlevel, b->d.S, levels) != -1) return fail(RMX_EARG, "region_extremes: a level entry is negative");
+    if ((rc = require_snapshot(b, r0, nr, "region_extremes"))) return rc;
+    RgnArgs ra;
+    if ((rc = stage_region_tables(b, nmask, masks, nlevel, levels, constrain, &ra))) return rc;
+    const size_t lds = rgx_lds_bytes(b->d.S);
+    const int tpw = tiles_per_wave(b->d.S);
+    auto kf = tpw == 3 ? k_region_extremes<3> : (tpw == 8 ? k_region_extremes<8> : k_region_extremes<16>);
+    if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return run_queries(b, r0, nr, nq, queries, ncol, KID_REGION_EXTREMES, "region_extremes: a backward step has a zero or non-finite normaliser", logp_out,
+                       [&](const Dev &dv, int r, int n, int, int use_wb, const int32_t *dq, int nqc, double *out, uint32_t *flags) {
+        ra.queries = dq; ra.nq = nqc;
+        hipLaunchKernelGGL(kf, dim3((unsigned)nqc, n), dim3(RGN_NT), lds, b->stream, dv, r, use_wb, ra, (int)ncol, out, flags);
     });
 }
 

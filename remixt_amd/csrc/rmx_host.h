@@ -5,6 +5,7 @@
 //   span_window_ok, span_spread_nan  rmx_region_span: the window rule of a table, and NaN in every entry of a failed query
 //   check_patterns       rmx_region_pattern: the rules of the piece lists of its queries
 //   decode_max_len_ok, check_decode_lengths, decode_plan  rmx_region_decode: the length rules and the chunks of a call
+//   extremes_ncol_ok, check_levels  rmx_region_extremes: the column rule, and that no level entry is negative
 //   weighted_search      rmx_weighted_search: numpy's cumsum / searchsorted(side='right') for the weighted M-step samples
 //                        (reference remixt/cn_model.py:475-480)
 //   weighted_sample_round  rmx_weighted_sample_round: a whole round of that sampling from a strided weight column
@@ -130,6 +131,19 @@ inline int decode_plan(int32_t nr, int32_t nq, int32_t S, int32_t max_len, Decod
     p->queries_at = p->states_at + (nrc * qc * (size_t)max_len * 2 + 7) / 8;
     p->out_doubles = p->queries_at + 2 * qc;
     return 0;
+}
+
+// rmx_region_extremes.  Its column rule: 1 <= ncol <= EXTREMES_MAX_COL (the columns of the matrix instruction's B operand)
+constexpr int32_t EXTREMES_MAX_COL = 16;
+inline bool extremes_ncol_ok(int32_t ncol) { return ncol >= 1 && ncol <= EXTREMES_MAX_COL; }
+// the level tables [C][nlevel][S] of a call hold no negative entry.  Returns the index of the first entry that does, -1 if
+// there is none, or -2 for arguments that describe no table (a negative extent, or entries without a pointer)
+inline int64_t check_levels(int64_t C, int64_t nlevel, int64_t S, const int16_t *levels) {
+    if (C < 0 || nlevel < 0 || S < 0) return -2;
+    const uint64_t n = (uint64_t)C * (uint64_t)nlevel * (uint64_t)S;      // (each extent is below 2^31 in a batch; the caller's are int32)
+    if (n > 0 && !levels) return -2;
+    for (uint64_t i = 0; i < n; i++) if (levels[i] < 0) return (int64_t)i;
+    return -1;
 }
 
 inline int compress_cn_states(const int64_t *cn_states, int32_t N, int32_t S, int32_t M, int32_t max_classes,

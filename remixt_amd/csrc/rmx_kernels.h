@@ -5868,6 +5868,211 @@ __global__ __launch_bounds__(RGN_NT) void k_region_counts(Dev d, int r0, int use
 }
 
 // =============================================================================
+// Region extremes: for a query (a, b, mask, level) over the model segments [a, b] of one chain and K <= 16 columns,
+//   F(j) = log P(c_n in mask and level(c_n) <= j at every constrained n of the run),   j = 0 .. K - 1,
+// level = a per-state integer >= 0 under the state class of n (a clone's total copy number, say): column j is the event
+// "the peak of the level over the run is <= j", a family of K nested k_region_prob events over one run.  With
+// G_b(s, j) = [mask and level_b(s) <= j] post_b(s) and H(s', j) = G_n+1(s', j) / D_n(s'),
+//   G_n(s, j) = [mask and level_n(s) <= j] fa_n(s) sum_s' W_n(s, s') H(s', j),   F(j) = log sum_s G_a(s, j);
+// at an unconstrained n the bracket is 1.  There is no label constraint.  EVERY COLUMN is divided by its own sum after every
+// step, the start included, and keeps its own running logarithm (k_region_counts has one total for all bins: a bin below
+// 1e-308 of it is lost, and here "peak <= 1" can be e^-1000 beside "peak <= 6" ~ 1).  A column whose sum is exactly 0 is -inf
+// from there on and stays all zeros; the walk ends once every column is.  Nothing of the model is written.
+// One workgroup of 256 threads per (restart, query).  G lives in LDS as [S rounded up to 16][16 columns]; a step is
+//   1. the states s' with mass in any column, compacted in state order by a ballot;
+//   2. one D(s') for those, shared by the columns and written as in k_region_counts; lane j divides column j in place;
+//   3. G_n on v_mfma_f64_16x16x4_f64 with k_region_counts' lane map, ONE instruction per (row tile, four s'):
+//      A = W(s0 + i, s'_k) from the Wb row (or exp(trans_value)), selected to 0 on a row no column admits, B = H(s'_k, j);
+//   4. the row factor [mask and level_n(s) <= j] fa_n(s) on the accumulators in registers (lev: the level row of n in LDS,
+//      0 where n does not bind and 0x7fff on a masked row or s >= S);
+//   5. the column sums in a fixed order: over the lane's rows, over the four lane groups, over the four waves through LDS;
+//      every thread takes the sum of its column (lane & 15) and G is written divided by it.
+// q.labels / q.nlabel carry the level tables; field 3 of a query is the level index (the host checked it).
+// Every sum has one order, fixed by S alone: a (restart, query) result does not depend on the launch, and a column does
+// not depend on the others beyond the zero terms their states add.  Only columns s < S of fa / post are read (clamped
+// address and select).  A D(s') that is 0 or not finite under mass, or a column sum that is not a finite number >= 0, sets
+// RGN_ERR_DENOM in flags[r] and gives NaN in every column.
+// grid (queries, restarts), block RGN_NT, dynamic LDS rgx_lds_bytes(S); out[(ri * nq + query) * K + j].
+// =============================================================================
+static inline size_t rgx_lds_bytes(int S) { const size_t SR = ((size_t)S + 15) & ~(size_t)15; return SR * (RGN_KB * 8 + 8 + 2 * 2); }
+#define RGX_NOLEVEL 0x7fff
+// rgn_tabs with a level row in place of the label row: both bind only where constrain does.  lv: null where n does not bind
+struct RgxTabs {
+    const uint8_t *mk;
+    const int16_t *lv;
+};
+__device__ __forceinline__ RgxTabs rgx_tabs(const Dev &d, const RgnArgs &q, int n, int mi, int vi) {
+    const int cls = d.seg_class[n];
+    const bool binds = !q.constrain || q.constrain[n];
+    RgxTabs t;
+    t.mk = (mi >= 0 && binds) ? q.masks + ((size_t)cls * q.nmask + mi) * d.S : nullptr;
+    t.lv = binds ? q.labels + ((size_t)cls * q.nlabel + vi) * d.S : nullptr;
+    return t;
+}
+// the level row of a segment -> lev[0 .. SR)
+__device__ __forceinline__ void rgx_level_row(const RgxTabs &t, int S, int SR, int16_t *lev) {
+    for (int s = threadIdx.x; s < SR; s += RGN_NT) {
+        const int sc = s < S ? s : S - 1;
+        const int lv = t.lv ? (int)t.lv[sc] : 0;
+        lev[s] = (int16_t)((s < S && (!t.mk || t.mk[sc])) ? lv : RGX_NOLEVEL);
+    }
+}
+// the partial sums of column (lane & 15) over the four lane groups of every wave -> redc, and every thread's column sum over
+// the waves (the barrier also ends every wave's reads of H and publishes s_bad)
+__device__ __forceinline__ double rgx_column_sum(double p, double (*redc)[RGN_KB]) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    p += __shfl_xor(p, 16, 64);
+    p += __shfl_xor(p, 32, 64);
+    if (lane < RGN_KB) redc[tid >> 6][lane] = p;
+    __syncthreads();
+    double t = 0.;
+#pragma unroll
+    for (int i = 0; i < RGN_NW; i++) t += redc[i][lane & 15];
+    return t;
+}
+// takes the sum Z of the thread's column: false if the step fails the query (a bad D(s'), or some column's Z is not a finite
+// number >= 0; uniform over the workgroup: every wave holds every column); Z == 0 makes the column -inf, else log Z is added
+__device__ __forceinline__ bool rgx_take_sum(double Z, bool bad, double &logp) {
+    if (bad || __ballot(!(Z >= 0. && Z < INFINITY)) != 0ull) return false;
+    if (Z == 0.) logp = -INFINITY;
+    else logp += log(Z);
+    return true;
+}
+template <int TPW>
+__global__ __launch_bounds__(RGN_NT) void k_region_extremes(Dev d, int r0, int use_wb, RgnArgs q, int K, double *out, uint32_t *flags) {
+    extern __shared__ double rgx_lds[];                 // G [SR][16], fas [SR], lev [SR] (int16), idx [SR] (int16)
+    __shared__ double redc[RGN_NW][RGN_KB];
+    __shared__ int nact, s_bad;
+    const int qi = blockIdx.x, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (uniform, and known to be: the matrix instructions sit under conditions on it)
+    const int grp = tid / RGN_GL, gl = tid % RGN_GL;
+    const int ai = lane & 15, kk = lane >> 4;
+    const int S = d.S, SR = (S + 15) & ~15;
+    double *G = rgx_lds, *fas = G + (size_t)SR * RGN_KB;
+    int16_t *lev = (int16_t *)(fas + SR), *idx = lev + SR;
+    const int a = q.queries[4 * qi], b = q.queries[4 * qi + 1], mi = q.queries[4 * qi + 2], vi = q.queries[4 * qi + 3];
+    if (tid == 0) s_bad = 0;
+    double logp = 0.;         // of column ai: the threads of a column carry the same value
+    bool failed = false;
+    // ---- start: G_b(s, j) = [mask and level <= j] post_b(s) ---------------------------------------------------
+    {
+        const double *post = d.post + rs_off(d, r, b);
+        rgx_level_row(rgx_tabs(d, q, b, mi, vi), S, SR, lev);
+        __syncthreads();
+        double part = 0.;
+        for (int e = tid; e < SR * RGN_KB; e += RGN_NT) {      // (e % 16 == ai: RGN_NT is a multiple of 16)
+            const int s = e / RGN_KB, sc = s < S ? s : S - 1;
+            const double pv = post[sc];
+            const double v = (ai < K && (int)lev[s] <= ai) ? pv : 0.;
+            G[e] = v;
+            part += v;
+        }
+        const double Z = rgx_column_sum(part, redc);
+        failed = !rgx_take_sum(Z, false, logp);
+        for (int e = tid; e < SR * RGN_KB; e += RGN_NT) G[e] = (!failed && Z > 0.) ? G[e] / Z : 0.;
+    }
+    for (int n = b - 1; n >= a && !failed && __ballot(logp > -INFINITY) != 0ull; n--) {
+        const auto [wb, Wt, pd] = rgn_adj(d, r, n, use_wb);
+        const double *fa = d.fa + rs_off(d, r, n);
+        rgx_level_row(rgx_tabs(d, q, n, mi, vi), S, SR, lev);
+        for (int s = tid; s < SR; s += RGN_NT) {
+            const int sc = s < S ? s : S - 1;
+            const double fv = fa[sc];
+            fas[s] = s < S ? fv : 0.;
+        }
+        // ---- 1. the states s' with mass in any column, in state order ------------------------------------------
+        __syncthreads();      // (G of the step before, or of the start, is complete)
+        const int na = __builtin_amdgcn_readfirstlane(rgn_compact(S, idx, nact, [&](int s) {
+            bool act = false;
+            for (int k = 0; k < K; k++) act = act || G[s * RGN_KB + k] > 0.;
+            return act;
+        }));
+        // ---- 2. D(s') and H = G / D in place ---------------------------------------------------------------------
+        if (wb) {
+            for (int j0 = 0; j0 < na; j0 += RGN_NT / RGN_GL) {
+                const int j = j0 + grp;
+                const bool ok = j < na;
+                const int sp = ok ? idx[j] : 0;
+                double p = 0.;
+                if (ok) {
+                    const double *wr = Wt + (size_t)sp * S;
+                    for (int s = gl; s < S; s += RGN_GL) p = fma(fas[s], wr[s], p);
+                }
+                const double D = group_sum(p, RGN_GL);
+                if (ok) {
+                    if (gl == 0 && !(D > 0. && D < INFINITY)) s_bad = 1;
+                    if (gl < K) G[sp * RGN_KB + gl] = G[sp * RGN_KB + gl] / D;
+                }
+            }
+        } else {
+            for (int j = tid; j < na; j += RGN_NT) {
+                const int sp = idx[j];
+                const double D = rgn_D_exp(d, n, sp, fas, pd);
+                if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                for (int k = 0; k < K; k++) G[sp * RGN_KB + k] = G[sp * RGN_KB + k] / D;
+            }
+        }
+        __syncthreads();
+        // ---- 3. G_n on the matrix cores: one instruction per (row tile, four s') ---------------------------------
+        psm_d4 acc[TPW];
+        bool rowlive[TPW];    // the lane's A row of tile u is in some column
+#pragma unroll
+        for (int u = 0; u < TPW; u++) {
+            acc[u] = psm_d4{0., 0., 0., 0.};
+            const int s = (wave + RGN_NW * u) * 16 + ai;
+            rowlive[u] = s < S && (int)lev[s < SR ? s : 0] < K;
+        }
+        for (int j0 = 0; j0 < na; j0 += 4) {
+            const int j = j0 + kk;
+            const bool ok = j < na;
+            const int sp = idx[ok ? j : 0];
+            const double hv = G[sp * RGN_KB + ai];
+            const double bv = (ok && ai < K) ? hv : 0.;
+#pragma unroll
+            for (int u = 0; u < TPW; u++) {
+                const int s0 = (wave + RGN_NW * u) * 16;
+                if (s0 < S) {         // (uniform over the wave)
+                    const int s = s0 + ai, sc = s < S ? s : S - 1;
+                    const bool live = ok && rowlive[u];
+                    double wv;
+                    if (wb) wv = Wt[(size_t)sp * S + sc];
+                    else wv = live ? exp(trans_value(d, n, sc, sp, pd)) : 0.;
+                    acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(live ? wv : 0., bv, acc[u], 0, 0, 0);
+                }
+            }
+        }
+        // ---- 4, 5. the row factor and the column sums, from the registers -------------------------------------
+        double part = 0.;
+#pragma unroll
+        for (int u = 0; u < TPW; u++) {
+            const int s0 = (wave + RGN_NW * u) * 16;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int s = s0 + kk + 4 * g;
+                const bool in = s < SR && (int)lev[s < SR ? s : 0] <= ai;
+                const double v = in ? fas[s < SR ? s : 0] * acc[u][g] : 0.;
+                acc[u][g] = v;
+                part += v;
+            }
+        }
+        const double Z = rgx_column_sum(part, redc);
+        failed = !rgx_take_sum(Z, s_bad != 0, logp);
+        const bool live = !failed && Z > 0.;
+#pragma unroll
+        for (int u = 0; u < TPW; u++) {
+            const int s0 = (wave + RGN_NW * u) * 16;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int s = s0 + kk + 4 * g;
+                if (s < SR) G[s * RGN_KB + ai] = live ? acc[u][g] / Z : 0.;
+            }
+        }
+    }
+    if (tid < K) out[((size_t)ri * q.nq + qi) * K + tid] = failed ? __builtin_nan("") : logp;
+    if (tid == 0 && failed) atomicOr(&flags[r], RGN_ERR_DENOM);
+}
+
+// =============================================================================
 // Call probabilities: log P(E) under the structured posterior of the last update_p_cn, for the event E of a query
 // (a, b, label, path) over the model segments [a, b] of one chain: c_n in A_n at every n of the run with constrain[n] set,
 // A_n = { s : label(s) == label(ref_n) } under the label table of n's state class, ref = the query's reference path

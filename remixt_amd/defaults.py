@@ -78,6 +78,14 @@ cn_breakend_changes = False
 # model and restart classes.  Needs cn_regions.  False: off (results, records and stores unchanged)
 cn_region_calls = False
 
+# The exact posterior distribution of the highest and of the lowest total copy number of every tumour clone over every region
+# of cn_regions (rmx_region_extremes): every fit result also carries `region_cn_extremes` -- names, bins (16),
+# peak_total_pmf and floor_total_pmf, (regions, M - 1, bins) each: entry k is the probability that the clone's highest (lowest)
+# total copy number over the region's segments is k, the last entry that of bins - 1 or more.  Other quantities, windows and
+# 'any clone' come from region_cn_extremes of the model and restart classes.  Needs cn_regions.  False: off (results,
+# records and stores unchanged)
+cn_region_extremes = False
+
 
 def get_param(config, name):
     if config is not None and name in config:

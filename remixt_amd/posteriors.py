@@ -1306,3 +1306,190 @@ def region_calls_on(config):
     if on and defaults.get_param(config, 'cn_regions') is None:
         raise ValueError('cn_region_calls needs cn_regions')
     return on
+
+
+# ---- distribution of a region's peak and lowest copy number (rmx_region_extremes) ------------------------
+LEVEL_QUANTITIES = ('total', 'major', 'minor')
+LEVEL_ORIENTATIONS = ('peak', 'floor')
+EXTREME_QUANTILES = (0.05, 0.5, 0.95)
+# the arrays of region_cn_extremes that go into fit results, records and stores (config cn_region_extremes): (regions, M - 1, bins) each
+EXTREME_ARRAYS = ('peak_total_pmf', 'floor_total_pmf')
+EXTREME_BINS = 16
+
+
+def _level_quantity(cn_classes, quantity):
+    """(C, S, M - 1): the quantity of every tumour clone."""
+    tum = np.asarray(cn_classes)[:, :, 1:, :].astype(np.int64)
+    if quantity == 'total':
+        return tum.sum(axis=-1)
+    if quantity == 'major':
+        return tum.max(axis=-1)
+    if quantity == 'minor':
+        return tum.min(axis=-1)
+    raise ValueError('unknown quantity %r: one of %s' % (quantity, ', '.join(LEVEL_QUANTITIES)))
+
+
+def level_name(orientation, quantity, clone):
+    """The name of a level table: '<peak|floor>_<total|major|minor>_<tumour clone 1 .. M-1, or any>'."""
+    if orientation not in LEVEL_ORIENTATIONS:
+        raise ValueError('unknown orientation %r: one of %s' % (orientation, ', '.join(LEVEL_ORIENTATIONS)))
+    if quantity not in LEVEL_QUANTITIES:
+        raise ValueError('unknown quantity %r: one of %s' % (quantity, ', '.join(LEVEL_QUANTITIES)))
+    return '%s_%s_%s' % (orientation, quantity, clone)
+
+
+def level_tables(cn_classes, ncol, first_level=0):
+    """Level tables of the region extremes: (levels int16 (C, T, S), names), T = 2 * 3 * M tables named by level_name, the
+    orientations outermost, then the quantities, then the tumour clones 1 .. M-1 and 'any'.  The quantities of a clone are
+    its total, major (the larger allele) and minor copy number; 'any' is the maximum over the tumour clones under 'peak' and
+    the minimum under 'floor'.  With q the quantity and w = clip(q - first_level, 0, ncol - 1),
+      peak   the level is w: column j of rmx_region_extremes is "q <= first_level + j throughout", and because of the clip the
+             last column is the mask-only event (the last bin means first_level + ncol - 1 or more);
+      floor  the level is ncol - 1 - w: column j is "q >= first_level + ncol - 1 - j throughout" (the bin of w = 0 means
+             first_level or less)."""
+    cn = np.asarray(cn_classes)
+    if cn.ndim != 4 or cn.shape[3] != 2 or cn.shape[2] < 2:
+        raise ValueError('cn_classes must have shape (num_classes, num_cn_states, num_clones >= 2, 2)')
+    ncol, first_level = int(ncol), int(first_level)
+    if not 1 <= ncol <= 16:
+        raise ValueError('ncol must be in 1 .. 16')
+    if first_level < 0:
+        raise ValueError('first_level must not be negative')
+    M = cn.shape[2]
+    tabs, names = [], []
+    for orient in LEVEL_ORIENTATIONS:
+        for quantity in LEVEL_QUANTITIES:
+            q = _level_quantity(cn, quantity)
+            cols = [q[:, :, m] for m in range(M - 1)] + [q.max(axis=-1) if orient == 'peak' else q.min(axis=-1)]
+            for clone, v in zip(list(range(1, M)) + ['any'], cols):
+                w = np.clip(v - first_level, 0, ncol - 1)
+                tabs.append(w if orient == 'peak' else ncol - 1 - w)
+                names.append(level_name(orient, quantity, clone))
+    return np.ascontiguousarray(np.stack(tabs, axis=1).astype(np.int16)), names
+
+
+def combine_columns(logp, piece_region, num_regions):
+    """Every region's columns from its pieces': logp (..., pieces, ncol) -> (..., num_regions, ncol), the pieces' logs added
+    per column.  Chains are independent under the structured posterior and "in the mask and at or below the threshold at
+    every segment" is a conjunction over segments, so column j of a region split at chain ends is the product of its pieces'
+    column j."""
+    return np.moveaxis(combine(np.moveaxis(np.asarray(logp, dtype=float), -1, -2), piece_region, num_regions), -1, -2)
+
+
+def _quantile_bins(cdf):
+    """cdf (..., bins), non-decreasing with last entry 1 -> int (..., 3): the first bin at which it reaches each of
+    EXTREME_QUANTILES (the last bin where rounding keeps it below)."""
+    out = np.zeros(cdf.shape[:-1] + (len(EXTREME_QUANTILES),), dtype=np.int64)
+    for i, qv in enumerate(EXTREME_QUANTILES):
+        reached = cdf >= qv
+        out[..., i] = np.where(reached.any(axis=-1), reached.argmax(axis=-1), cdf.shape[-1] - 1)
+    return out
+
+
+def extremes_summary(peak_logcdf, floor_logsurv, first_level=0):
+    """The arrays of region_cn_extremes from the two families of columns (..., bins): peak_logcdf[..., j] = log P(peak <=
+    first_level + j) (the last one the mask-only event), floor_logsurv[..., k] = log P(lowest >= first_level + k) (the first
+    one the mask-only event).  pmfs are differences of the exponentials, clipped to [0, 1]: a CDF that dips by an ulp gives
+    0, not a negative number.  Quantiles are copy numbers; a saturated bin is reported as its edge (first_level + bins - 1
+    for a peak of that or more, first_level for a lowest value of that or less)."""
+    with np.errstate(over='ignore'):
+        pc = np.clip(np.exp(np.minimum(np.asarray(peak_logcdf, dtype=float), 0.)), 0., 1.)
+        fs = np.clip(np.exp(np.minimum(np.asarray(floor_logsurv, dtype=float), 0.)), 0., 1.)
+    bins = pc.shape[-1]
+    zero = np.zeros(pc.shape[:-1] + (1,))
+    out = {'bins': bins, 'first_level': int(first_level), 'peak_cdf': pc, 'floor_cdf': fs,
+           'peak_pmf': np.clip(np.diff(np.concatenate([zero, pc], axis=-1), axis=-1), 0., 1.),
+           'floor_pmf': np.clip(-np.diff(np.concatenate([fs, zero], axis=-1), axis=-1), 0., 1.)}
+    # the lowest value's own CDF, P(lowest <= first_level + k) = 1 - P(lowest >= first_level + k + 1)
+    low = 1. - np.concatenate([fs[..., 1:], zero], axis=-1)
+    for name, cdf in (('peak', pc), ('floor', low)):
+        qb = _quantile_bins(cdf) + int(first_level)
+        for i, qv in enumerate(EXTREME_QUANTILES):
+            out['%s_q%02d' % (name, int(round(qv * 100)))] = qb[..., i]
+    return out
+
+
+def _extreme_columns(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, levels, bins):
+    """F (nr, T, R, bins): the columns of every region under each of the T level tables `levels` (C, T, S), no mask, from one device
+    call: one query per region piece and table, the pieces of a region joined per column."""
+    cs, ce = chains_from_telomeres(is_telomere)
+    runs, piece_region, constrain = region_queries(regions, seg_fwd_remap, seg_is_original, cs, ce)
+    P, R, T = len(runs), len(np.asarray(regions).reshape(-1, 2)), levels.shape[1]
+    if P == 0:
+        return np.zeros((nr, T, 0, bins))
+    q = np.zeros((T, P, 4), dtype=np.int32)
+    q[:, :, :2] = runs[None]
+    q[:, :, 2] = -1
+    q[:, :, 3] = np.arange(T)[:, None]
+    logp = batch.region_extremes_raw(r0, nr, q.reshape(-1, 4), None, levels, constrain, bins).reshape(nr, T, P, bins)
+    return combine_columns(logp, piece_region, R)
+
+
+def batch_region_cn_extremes(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, quantity='total', clone='any', bins=16, first_level=0):
+    """The exact posterior distribution of the highest and of the lowest copy number over regions, for restarts r0 ..
+    r0+nr-1 of a RemixtBatch from one device call (rmx_region_extremes).  quantity: 'total', 'major' or 'minor'; clone: a
+    tumour clone 1 .. M-1, or 'any' (the peak is then the highest over the tumour clones, the lowest value the lowest); the
+    window is first_level .. first_level + bins - 1, bins in 1 .. 16.  The extremes run over the region's real segments:
+    a zero-length segment inserted at a breakend does not count.  regions: (first, last) experiment segment indices.
+    A dict of `bins`, `first_level` and, per restart and region,
+      peak_cdf   (nr, R, bins)  P(peak <= first_level + k); the last entry is 1: that bin means first_level + bins - 1 or more
+      peak_pmf   (nr, R, bins)  its differences, clipped to [0, 1]
+      floor_cdf  (nr, R, bins)  P(lowest >= first_level + k); the first entry is 1: that bin means first_level or less
+      floor_pmf  (nr, R, bins)  P(lowest == first_level + k), from its differences
+      peak_q05, peak_q50, peak_q95, floor_q05, floor_q50, floor_q95   int (nr, R): quantiles as copy numbers, a saturated
+                 bin reported as its edge."""
+    bins = int(bins)
+    if not 1 <= bins <= 16:
+        raise ValueError('bins must be in 1 .. 16')
+    levels, names = level_tables(batch.cn_classes, bins, first_level)
+    M = np.asarray(batch.cn_classes).shape[2]
+    if clone != 'any' and not (isinstance(clone, (int, np.integer)) and 1 <= clone < M):
+        raise ValueError('clone must be a tumour clone 1 .. %d or \'any\'' % (M - 1))
+    pick = [names.index(level_name(o, quantity, clone)) for o in LEVEL_ORIENTATIONS]
+    F = _extreme_columns(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, levels[:, pick], bins)
+    # floor column j is "lowest >= first_level + bins - 1 - j": reversed, entry k is "lowest >= first_level + k"
+    return extremes_summary(F[:, 0], F[:, 1, :, ::-1], first_level)
+
+
+def amplification_prob(extremes, threshold):
+    """P(peak >= threshold) of a batch_region_cn_extremes result: 1 - P(peak <= threshold - 1).  The threshold has to lie in
+    the window's resolved part, first_level + 1 .. first_level + bins - 1 (or at most 0: certain)."""
+    k = int(threshold) - int(extremes['first_level'])
+    cdf = np.asarray(extremes['peak_cdf'])
+    if int(threshold) <= 0:
+        return np.ones(cdf.shape[:-1])
+    if not 1 <= k <= cdf.shape[-1] - 1:
+        raise ValueError('threshold outside first_level + 1 .. first_level + bins - 1: slide the window with first_level')
+    return np.clip(1. - cdf[..., k - 1], 0., 1.)
+
+
+def add_region_cn_extremes(res, names, extremes):
+    """Fit result dict `res` gains `region_cn_extremes` (config cn_region_extremes): the region names, the number of bins and
+    the arrays of EXTREME_ARRAYS, (len(names), M - 1, bins) each, one row per tumour clone: the distributions of the peak and
+    of the lowest total copy number of the clone over the region, from 0 (the last bin: bins - 1 or more)."""
+    out = {'names': list(names), 'bins': int(np.asarray(extremes[EXTREME_ARRAYS[0]]).shape[-1])}
+    for k in EXTREME_ARRAYS:
+        out[k] = np.asarray(extremes[k], dtype=float)
+    res['region_cn_extremes'] = out
+    return res
+
+
+def batch_clone_extremes(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, bins=EXTREME_BINS):
+    """The arrays of EXTREME_ARRAYS, (nr, R, M - 1, bins) each, from one device call: batch_region_cn_extremes' peak_pmf and
+    floor_pmf of the total copy number of every tumour clone, window 0 .. bins - 1."""
+    levels, names = level_tables(batch.cn_classes, bins, 0)
+    M = np.asarray(batch.cn_classes).shape[2]
+    pick = [names.index(level_name(o, 'total', m)) for o in LEVEL_ORIENTATIONS for m in range(1, M)]
+    F = _extreme_columns(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, levels[:, pick], bins)
+    F = F.reshape(nr, 2, M - 1, F.shape[2], bins)
+    s = extremes_summary(F[:, 0], F[:, 1, ..., ::-1], 0)
+    return {'peak_total_pmf': np.moveaxis(s['peak_pmf'], 1, 2), 'floor_total_pmf': np.moveaxis(s['floor_pmf'], 1, 2)}
+
+
+def region_extremes_on(config):
+    """Config value cn_region_extremes, checked: it needs cn_regions."""
+    from . import defaults
+    on = bool(defaults.get_param(config, 'cn_region_extremes'))
+    if on and defaults.get_param(config, 'cn_regions') is None:
+        raise ValueError('cn_region_extremes needs cn_regions')
+    return on

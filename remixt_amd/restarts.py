@@ -682,6 +682,26 @@ class RestartSet(object):
         return posteriors.batch_region_change_counts(self.batch, 0, len(self.models), regions, m.seg_fwd_remap, m.seg_is_original, m.is_telomere,
                                                      bins=bins)
 
+    def region_cn_extremes(self, regions, quantity='total', clone='any', bins=16, first_level=0):
+        """BreakpointModel.region_cn_extremes of every restart from one device call: `bins`, `first_level` and arrays
+        (restarts, len(regions), ...)."""
+        from . import posteriors
+        if self.batch is None or not hasattr(self.batch, 'region_extremes_raw'):
+            per = [m.region_cn_extremes(regions, quantity, clone, bins, first_level) for m in self.models]
+            return dict((k, np.stack([p[k] for p in per]) if isinstance(v, np.ndarray) else v) for k, v in per[0].items())
+        m = self.models[0]
+        return posteriors.batch_region_cn_extremes(self.batch, 0, len(self.models), regions, m.seg_fwd_remap, m.seg_is_original, m.is_telomere,
+                                                   quantity=quantity, clone=clone, bins=bins, first_level=first_level)
+
+    def region_clone_extremes(self, regions, bins=16):
+        """BreakpointModel.region_clone_extremes of every restart from one device call: arrays (restarts, len(regions), M - 1, bins)."""
+        from . import posteriors
+        if self.batch is None or not hasattr(self.batch, 'region_extremes_raw'):
+            per = [m.region_clone_extremes(regions, bins) for m in self.models]
+            return dict((k, np.stack([p[k] for p in per])) for k in posteriors.EXTREME_ARRAYS)
+        m = self.models[0]
+        return posteriors.batch_clone_extremes(self.batch, 0, len(self.models), regions, m.seg_fwd_remap, m.seg_is_original, m.is_telomere, bins=bins)
+
     def region_cn_moments(self, regions):
         """BreakpointModel.region_cn_moments of every restart from one device call per feature group: a dict of `length`
         (len(regions),) and arrays (restarts, len(regions), ...)."""
@@ -937,6 +957,16 @@ class RestartGroups(object):
         parts = self._map(lambda rs: rs.region_change_counts(regions, bins))
         return dict((k, np.concatenate([p[k] for p in parts])) for k in parts[0])
 
+    def region_cn_extremes(self, regions, quantity='total', clone='any', bins=16, first_level=0):
+        """RestartSet.region_cn_extremes over the groups, restarts in order: `bins`, `first_level` and arrays (restarts, len(regions), ...)."""
+        parts = self._map(lambda rs: rs.region_cn_extremes(regions, quantity, clone, bins, first_level))
+        return dict((k, np.concatenate([p[k] for p in parts]) if isinstance(v, np.ndarray) else v) for k, v in parts[0].items())
+
+    def region_clone_extremes(self, regions, bins=16):
+        """RestartSet.region_clone_extremes over the groups, restarts in order: arrays (restarts, len(regions), M - 1, bins)."""
+        parts = self._map(lambda rs: rs.region_clone_extremes(regions, bins))
+        return dict((k, np.concatenate([p[k] for p in parts])) for k in parts[0])
+
     def region_cn_moments(self, regions):
         """RestartSet.region_cn_moments over the groups, restarts in order: `length` (len(regions),) and arrays (restarts, len(regions), ...)."""
         parts = self._map(lambda rs: rs.region_cn_moments(regions))
@@ -1110,6 +1140,14 @@ class DatasetGroups(object):
         """RestartGroups.breakend_changes of every dataset: a list, one dict per dataset."""
         return self._map(lambda part: part.breakend_changes(arrays))
 
+    def region_cn_extremes(self, regions, quantity='total', clone='any', bins=16, first_level=0):
+        """RestartGroups.region_cn_extremes of every dataset: a list, one dict per dataset."""
+        return self._map(lambda part: part.region_cn_extremes(regions, quantity, clone, bins, first_level))
+
+    def region_clone_extremes(self, regions, bins=16):
+        """RestartGroups.region_clone_extremes of every dataset: a list, one dict per dataset."""
+        return self._map(lambda part: part.region_clone_extremes(regions, bins))
+
     def region_call(self, regions, event=None):
         """RestartGroups.region_call of every dataset: a list, one dict per dataset."""
         return self._map(lambda part: part.region_call(regions, event))
@@ -1244,7 +1282,7 @@ def _section(fields, group=None, head=(), tail=(), add=None):
 
 
 def _record_sections(N, M, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0, call_confidence=False, cn_moments=False,
-                     extent_names=None, length_edges=None, breakend_k=None, region_calls=False):
+                     extent_names=None, length_edges=None, breakend_k=None, region_calls=False, region_extremes=False):
     """The optional sections of a float record, in record order.  The record is the fixed part -- header, h, parameters,
     outlier probabilities: _HDR + M + nparams + 4 N floats -- and then, each only when its option is on (a record without
     it is unchanged), at offsets that are the running sum of what precedes:
@@ -1262,7 +1300,9 @@ def _record_sections(N, M, cn_samples=False, cn_posterior=False, region_names=No
       breakend changes (cn_breakend_changes; breakend_k: the number of breakpoints K): the five arrays of
         posteriors.BREAKEND_ARRAYS, p_change (K, 2) and four (K,): 6 K floats;
       region calls (cn_region_calls, with regions): the three arrays of posteriors.REGION_CALL_ARRAYS, one entry per region
-        (n_differ as a float: exact)."""
+        (n_differ as a float: exact);
+      region extremes (cn_region_extremes, with regions): the two arrays of posteriors.EXTREME_ARRAYS, (regions, M - 1,
+        posteriors.EXTREME_BINS) each: 2 (M - 1) bins floats per region, at the end of the record."""
     from . import sampling
     out = []
     if cn_samples:
@@ -1295,14 +1335,17 @@ def _record_sections(N, M, cn_samples=False, cn_posterior=False, region_names=No
     if region_calls and region_names is not None:
         out.append(_section([(k, (len(region_names),)) for k in posteriors.REGION_CALL_ARRAYS], 'region_calls',
                             add=lambda res, a: posteriors.add_region_calls(res, region_names, a)))
+    if region_extremes and region_names is not None:
+        out.append(_section([(k, (len(region_names), M - 1, posteriors.EXTREME_BINS)) for k in posteriors.EXTREME_ARRAYS], 'region_cn_extremes',
+                            add=lambda res, a: posteriors.add_region_cn_extremes(res, region_names, a)))
     return out
 
 
 def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0, call_confidence=False,
-          cn_moments=False, extent_names=None, length_edges=None, breakend_changes=False, region_calls=False):
+          cn_moments=False, extent_names=None, length_edges=None, breakend_changes=False, region_calls=False, region_extremes=False):
     """One restart's results as (float64 vector, int8 vector) of fixed length."""
     sections = _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names, length_edges,
-                                K if breakend_changes else None, region_calls)
+                                K if breakend_changes else None, region_calls, region_extremes)
     o = _HDR + M + nparams
     f = np.zeros(o + 4 * N + sum(s.length for s in sections), dtype=np.float64)
     st = res['stats']
@@ -1324,9 +1367,10 @@ def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_post
 
 
 def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0,
-            call_confidence=False, cn_moments=False, extent_names=None, length_edges=None, breakend_changes=False, region_calls=False):
+            call_confidence=False, cn_moments=False, extent_names=None, length_edges=None, breakend_changes=False, region_calls=False,
+            region_extremes=False):
     sections = _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names, length_edges,
-                                K if breakend_changes else None, region_calls)
+                                K if breakend_changes else None, region_calls, region_extremes)
     res = dict()
     res['h'] = f[_HDR:_HDR + M].copy()
     o = _HDR + M + nparams
@@ -1354,7 +1398,7 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
                              device=None, kernel_module=None, seeds=None, quiet=True, groups=2, num_cn_samples=0, cn_sample_seed=0,
                              cn_posterior_summary=False, cn_regions=None, cn_region_change_bins=0, cn_call_confidence=False, cn_region_moments=False,
                              cn_event_extents=None, cn_extent_window=64, cn_event_lengths=False, cn_event_length_edges=(), cn_breakend_changes=False,
-                             cn_region_calls=False, **model_kwargs):
+                             cn_region_calls=False, cn_region_extremes=False, **model_kwargs):
     """Fit all restarts across the ranks of the default torch.distributed group.
 
     Every rank holds the (small, read-only) experiment; rank g fits restarts
@@ -1381,12 +1425,16 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
     (posteriors.add_breakend_changes), and the records grow by six floats per breakpoint.
     cn_region_calls (with cn_regions): every result also carries `region_calls` (posteriors.add_region_calls), and the
     records grow by three floats per region.
+    cn_region_extremes (with cn_regions): every result also carries `region_cn_extremes` (posteriors.add_region_cn_extremes),
+    and the records grow, at their end, by 2 (M - 1) posteriors.EXTREME_BINS floats per region.
     """
     import torch
     import torch.distributed as dist
     posteriors.check_region_options(cn_regions, cn_region_change_bins, cn_call_confidence, cn_region_moments)
     if cn_region_calls and cn_regions is None:
         raise ValueError('cn_region_calls needs cn_regions')
+    if cn_region_extremes and cn_regions is None:
+        raise ValueError('cn_region_extremes needs cn_regions')
     extents = posteriors.extents_on({'cn_event_extents': cn_event_extents, 'cn_extent_window': cn_extent_window}, len(experiment.x))
     lengths = posteriors.lengths_on({'cn_event_extents': cn_event_extents, 'cn_extent_window': cn_extent_window, 'cn_event_lengths': cn_event_lengths,
                                      'cn_event_length_edges': cn_event_length_edges}, len(experiment.x))
@@ -1406,7 +1454,8 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
         rs.fit(num_em_iter, num_update_iter)
         local = rs.results()
         add_optional_outputs(rs, local, experiment, mine, num_cn_samples, cn_sample_seed, cn_posterior_summary, cn_regions, cn_region_change_bins, cn_call_confidence,
-                             cn_region_moments, cn_event_extents, cn_extent_window, cn_event_lengths, cn_event_length_edges, cn_breakend_changes, cn_region_calls)
+                             cn_region_moments, cn_event_extents, cn_extent_window, cn_event_lengths, cn_event_length_edges, cn_breakend_changes, cn_region_calls,
+                             cn_region_extremes)
         param_names = list(rs.models[0].likelihood_params)
         rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     if param_names is None:
@@ -1418,7 +1467,8 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
                                  region_names=None if cn_regions is None else [str(r[0]) for r in cn_regions], change_bins=cn_region_change_bins,
                                  call_confidence=bool(cn_call_confidence), cn_moments=bool(cn_region_moments),
                                  extent_names=None if extents is None else extents[0], length_edges=None if lengths is None else len(lengths[4]),
-                                 breakend_changes=bool(cn_breakend_changes), region_calls=bool(cn_region_calls))
+                                 breakend_changes=bool(cn_breakend_changes), region_calls=bool(cn_region_calls),
+                                 region_extremes=bool(cn_region_extremes))
 
 
 def add_region_events(rs, results, cn_regions):
@@ -1504,6 +1554,16 @@ def add_region_calls(rs, results, cn_regions):
     return results
 
 
+def add_region_cn_extremes(rs, results, cn_regions):
+    """Add the region extremes of config cn_regions / cn_region_extremes of every restart of `rs` (a RestartSet / RestartGroups;
+    one device call per batch) to results[r] (posteriors.add_region_cn_extremes)."""
+    names, regions = posteriors.parse_regions(cn_regions)
+    ext = rs.region_clone_extremes(regions, posteriors.EXTREME_BINS)
+    for r, res in enumerate(results):
+        posteriors.add_region_cn_extremes(res, names, dict((k, ext[k][r]) for k in posteriors.EXTREME_ARRAYS))
+    return results
+
+
 def add_posterior_summaries(rs, results, experiment):
     """Add the exact posterior summary of every restart of `rs` (a RestartSet / RestartGroups; one device call per
     batch) to results[r] (posteriors.add_posterior_summary); cn_posterior_prob is taken at results[r]['cn']."""
@@ -1526,7 +1586,8 @@ def add_cn_sample_summaries(rs, results, experiment, num_samples, seed, init_ids
 
 def add_optional_outputs(rs, results, experiment, init_ids, num_cn_samples=0, cn_sample_seed=0, cn_posterior_summary=False, cn_regions=None,
                          cn_region_change_bins=0, cn_call_confidence=False, cn_region_moments=False, cn_event_extents=None, cn_extent_window=64,
-                         cn_event_lengths=False, cn_event_length_edges=(), cn_breakend_changes=False, cn_region_calls=False):
+                         cn_event_lengths=False, cn_event_length_edges=(), cn_breakend_changes=False, cn_region_calls=False,
+                         cn_region_extremes=False):
     """Add the optional outputs of a fit -- the config values of the same names -- of every restart of the fitted `rs` (a
     RestartSet / RestartGroups) to results[r]; init_ids[r] selects restart r's posterior-sample stream.  The combination is
     checked before the fit (posteriors.check_region_options)."""
@@ -1550,12 +1611,14 @@ def add_optional_outputs(rs, results, experiment, init_ids, num_cn_samples=0, cn
         add_breakend_changes(rs, results)
     if cn_region_calls and cn_regions is not None:
         add_region_calls(rs, results, cn_regions)
+    if cn_region_extremes and cn_regions is not None:
+        add_region_cn_extremes(rs, results, cn_regions)
     return results
 
 
 def gather_result_records(local, experiment, init_params, num_clones, param_names, device=None, timing=None, local_ids=None, cn_samples=False,
                           cn_posterior=False, region_names=None, change_bins=0, call_confidence=False, cn_moments=False, extent_names=None,
-                          length_edges=None, breakend_changes=False, region_calls=False):
+                          length_edges=None, breakend_changes=False, region_calls=False, region_extremes=False):
     """The one collective of the path: every rank contributes the fixed-size records of the restarts
     it fitted (`local`, in the order of shard_indices) -- one float64 record (ELBO, h, parameters, outlier
     probabilities, failure code) and one int8 record (cn, brk_cn, masks) per restart -- and every rank gets the
@@ -1584,12 +1647,12 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
             per_rank = int(cnt_.item())
     if len(local) > per_rank:
         raise ValueError('gather_result_records: %d local results for a share of %d (pass local_ids for shares that are not shard_indices\')' % (len(local), per_rank))
-    flen = _HDR + M + nparams + 4 * N + sum(s.length for s in _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names, length_edges, K if breakend_changes else None, region_calls))
+    flen = _HDR + M + nparams + 4 * N + sum(s.length for s in _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names, length_edges, K if breakend_changes else None, region_calls, region_extremes))
     ilen = N * M * 2 + K * M + 2 * N
     fbuf = np.full((per_rank, flen), np.nan); ibuf = np.zeros((per_rank, ilen), dtype=np.int8)
     for j, res in enumerate(local):
         fbuf[j], ibuf[j] = _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments,
-                                  extent_names, length_edges, breakend_changes, region_calls)
+                                  extent_names, length_edges, breakend_changes, region_calls, region_extremes)
     if local_ids is not None:
         ids_t = np.full((per_rank,), -1, dtype=np.int64); ids_t[:len(local_ids)] = local_ids
     t0 = time.perf_counter()
@@ -1622,7 +1685,7 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
         ids_g = shard_indices(len(init_params), world, g) if ids_all is None else [int(i) for i in ids_all[g] if i >= 0]
         for j, i in enumerate(ids_g):
             results[i] = _unpack(fall[g][j], iall[g][j], N, M, K, nparams, brk_ids, param_names, init_params[i], cn_samples, cn_posterior, region_names, change_bins, call_confidence,
-                                 cn_moments, extent_names, length_edges, breakend_changes, region_calls)
+                                 cn_moments, extent_names, length_edges, breakend_changes, region_calls, region_extremes)
     return results
 
 

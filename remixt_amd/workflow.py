@@ -54,6 +54,7 @@ def fit_model(experiment_filename, results_filename, config, ref_data_dir=None, 
         cn_event_lengths=posteriors.lengths_on(config) is not None, cn_event_length_edges=get('cn_event_length_edges'),
         cn_breakend_changes=bool(get('cn_breakend_changes')),
         cn_region_calls=posteriors.region_calls_on(config),
+        cn_region_extremes=posteriors.region_extremes_on(config),
         **pipeline._model_kwargs(experiment, config))
     results = dict((ids[k], results[k]) for k in results)
     if _rank() != 0:

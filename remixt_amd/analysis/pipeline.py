@@ -6,9 +6,9 @@ import pickle
 
 import numpy as np
 
-from .. import defaults, posteriors, sampling
+from .. import defaults, outputs, posteriors, sampling
 from ..cn_model import BreakpointModel
-from ..restarts import RestartSet, add_call_confidence, add_cn_sample_summaries, add_optional_outputs, add_posterior_summaries, add_region_change_counts, add_region_cn_moments, add_region_events, collect_fit_results, fit_restarts_distributed, select_optimal  # noqa: F401
+from ..restarts import RestartSet, add_optional_outputs, collect_fit_results, select_optimal
 
 
 def _model_kwargs(experiment, config):
@@ -29,16 +29,39 @@ def _model_kwargs(experiment, config):
     )
 
 
+class _OneRestart(object):
+    """A fitted BreakpointModel under the query methods of restarts.RestartSet that the optional outputs use, as a set of
+    one restart: the model's own queries, their results under a leading axis of one (`length` of the moments belongs to the
+    regions, not to a restart)."""
+
+    def __init__(self, model):
+        self.model = model
+
+    def sample_cn(self, num_samples, seed=0, init_ids=None):
+        return [self.model.sample_cn(num_samples, sampling.restart_seed(seed, init_ids[0]))]
+
+    def posterior_summary(self, cn=None, marginals=False):
+        m, b = self.model, self.model.model._batch
+        states = posteriors.states_in_model_order(cn[0], b, m.seg_fwd_remap)[None]
+        s = posteriors.batch_summaries(b, m.model._r, 1, states=states)[0]
+        return [dict((k, v[m.seg_fwd_remap]) for k, v in s.items())]
+
+    def __getattr__(self, name):
+        """Every other query: the model's own (cn=: the one restart's path)."""
+        query = getattr(self.model, name)
+
+        def one(*args, **kwargs):
+            if kwargs.get('cn') is not None:
+                kwargs['cn'] = kwargs['cn'][0]
+            out = query(*args, **kwargs)
+            return dict((k, v if k == 'length' else [v]) for k, v in out.items()) if isinstance(out, dict) else [out]
+        return one
+
+
 def fit(experiment, init_params, config, device=0, quiet=False, init_id=0):
     """analysis/pipeline.py:127-228 (one restart).  init_id: the restart's id, which selects its posterior-sample stream
     when config num_cn_samples > 0."""
-    bins = posteriors.change_bins(config)      # (a bad combination fails before the fit, not after it)
-    call_conf = posteriors.call_confidence_on(config)
-    moments = posteriors.region_moments_on(config)
-    extents = posteriors.extents_on(config, len(experiment.x))
-    lengths = posteriors.lengths_on(config, len(experiment.x))
-    region_calls = posteriors.region_calls_on(config)
-    region_extremes = posteriors.region_extremes_on(config)
+    selection = outputs.resolve(config, len(experiment.x))      # (a bad combination fails before the fit, not after it)
     h_init = np.array([
         init_params['h_normal'],
         init_params['h_tumour'] * init_params['mix_frac'],
@@ -65,40 +88,7 @@ def fit(experiment, init_params, config, device=0, quiet=False, init_id=0):
     model.num_update_iter = defaults.get_param(config, 'num_update_iter')
     model.fit(h_init)
     res = collect_fit_results(model, experiment, init_params)
-    num_samples = defaults.get_param(config, 'num_cn_samples')
-    if num_samples > 0:
-        seed = sampling.restart_seed(defaults.get_param(config, 'cn_sample_seed'), init_id)
-        sampling.add_sample_summary(res, model.sample_cn(num_samples, seed), experiment.l)
-    if defaults.get_param(config, 'cn_posterior_summary'):
-        b = model.model._batch
-        states = posteriors.states_in_model_order(res['cn'], b, model.seg_fwd_remap)[None]
-        s = posteriors.batch_summaries(b, model.model._r, 1, states=states)[0]
-        posteriors.add_posterior_summary(res, dict((k, v[model.seg_fwd_remap]) for k, v in s.items()), experiment.l)
-    cn_regions = defaults.get_param(config, 'cn_regions')
-    if cn_regions is not None:
-        names, regions = posteriors.parse_regions(cn_regions)
-        posteriors.add_region_events(res, names, model.region_events(regions))
-        if bins:
-            posteriors.add_region_change_counts(res, names, bins, model.region_change_counts(regions, bins))
-        if call_conf:
-            posteriors.add_call_confidence(res, names, model.call_confidence(regions, res['cn']), model.cn_logprob(res['cn']))
-        if moments:
-            posteriors.add_region_cn_moments(res, names, model.region_cn_moments(posteriors.genome_region(regions, len(res['cn']))))
-        if region_calls:
-            posteriors.add_region_calls(res, names, model.region_call(regions, None, res['cn']))
-        if region_extremes:
-            posteriors.add_region_cn_extremes(res, names, model.region_clone_extremes(regions, posteriors.EXTREME_BINS))
-    if extents is not None:
-        names, anchors, events, window = extents
-        one = posteriors.grouped_event_extents(lambda a, ev, w: [model.event_extent(a, ev, w)], anchors, events, window)
-        posteriors.add_event_extents(res, names, one[0])
-    if lengths is not None:
-        names, anchors, events, window, edges = lengths
-        one = posteriors.grouped_event_spans(lambda a, ev, w: [model.event_span(a, ev, w)], anchors, events, window, edges)
-        posteriors.add_event_lengths(res, names, one[0])
-    if defaults.get_param(config, 'cn_breakend_changes'):
-        posteriors.add_breakend_changes(res, model.breakend_changes(arrays=True))
-    return res
+    return add_optional_outputs(_OneRestart(model), [res], experiment, [init_id], selection)[0]
 
 
 def fit_task(results_filename, experiment_filename, init_params, config, device=0, quiet=True, init_id=0):
@@ -126,13 +116,7 @@ def fit_restarts(experiment, init_params_by_id, config, device=0, quiet=True, se
     """All restarts of one GPU in lockstep; returns {init_id: fit_results} like one
     `fit_task` per init_id (workflow.py:329-340).  With per-restart seeds the restarts run as
     `groups` RestartSets on their own streams and host threads (same per-restart results)."""
-    bins = posteriors.change_bins(config)      # (a bad combination fails before the fit, not after it)
-    call_conf = posteriors.call_confidence_on(config)
-    moments = posteriors.region_moments_on(config)
-    posteriors.extents_on(config, len(experiment.x))
-    lengths = posteriors.lengths_on(config, len(experiment.x))
-    region_calls = posteriors.region_calls_on(config)
-    region_extremes = posteriors.region_extremes_on(config)
+    selection = outputs.resolve(config, len(experiment.x))      # (a bad combination fails before the fit, not after it)
     ids = sorted(init_params_by_id)
     params = [init_params_by_id[i] for i in ids]
     max_cn = defaults.get_param(config, 'max_copy_number')
@@ -144,11 +128,7 @@ def fit_restarts(experiment, init_params_by_id, config, device=0, quiet=True, se
         rs = RestartSet(experiment, params, max_cn, num_clones=3, device=device, quiet=quiet, seeds=seeds,
                         **_model_kwargs(experiment, config))
     rs.fit(defaults.get_param(config, 'num_em_iter'), defaults.get_param(config, 'num_update_iter'))
-    results = add_optional_outputs(rs, rs.results(), experiment, ids, defaults.get_param(config, 'num_cn_samples'), defaults.get_param(config, 'cn_sample_seed'),
-                                   defaults.get_param(config, 'cn_posterior_summary'), defaults.get_param(config, 'cn_regions'), bins, call_conf, moments,
-                                   defaults.get_param(config, 'cn_event_extents'), defaults.get_param(config, 'cn_extent_window'),
-                                   lengths is not None, () if lengths is None else lengths[4], defaults.get_param(config, 'cn_breakend_changes'), region_calls,
-                                   region_extremes)
+    results = add_optional_outputs(rs, rs.results(), experiment, ids, selection)
     out = dict(zip(ids, results))
     rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     return out
@@ -285,51 +265,8 @@ def store_fit_results(store, experiment, fit_results, key_prefix):
     store[key_prefix + '/cn'] = cn_table
     store[key_prefix + '/mix'] = pd.Series(h / h.sum(), index=range(len(h)))
     store[key_prefix + '/brk_cn'] = brk_cn_table
-    if 'cn_sample_agreement' in fit_results:      # (config num_cn_samples > 0)
-        store[key_prefix + '/cn_sample_agreement'] = pd.DataFrame(np.asarray(fit_results['cn_sample_agreement']))
-        store[key_prefix + '/cn_state_agreement'] = pd.Series(np.asarray(fit_results['cn_state_agreement']))
-    if 'cn_posterior_prob' in fit_results:        # (config cn_posterior_summary)
-        for k in posteriors.COMPACT_ARRAYS:
-            v = np.asarray(fit_results[k])
-            store[key_prefix + '/' + k] = pd.DataFrame(v) if v.ndim == 2 else pd.Series(v)
-    if 'region_events' in fit_results:            # (config cn_regions)
-        ev = fit_results['region_events']
-        store[key_prefix + '/region_names'] = pd.Series(list(ev['names']))
-        for k in posteriors.REGION_ARRAYS:
-            store[key_prefix + '/' + k] = pd.Series(np.asarray(ev[k]))
-    if 'region_change_counts' in fit_results:     # (config cn_region_change_bins)
-        for k in posteriors.COUNT_ARRAYS:
-            store[key_prefix + '/' + k] = pd.DataFrame(np.asarray(fit_results['region_change_counts'][k]))
-    if 'call_confidence' in fit_results:          # (config cn_call_confidence)
-        for k in posteriors.CALL_ARRAYS:
-            store[key_prefix + '/' + k] = pd.Series(np.asarray(fit_results['call_confidence'][k]))
-    if 'region_cn_moments' in fit_results:        # (config cn_region_moments; total_cn_mean is also a per-segment array: region_ in front)
-        for k in posteriors.MOMENT_ARRAYS:
-            v = np.asarray(fit_results['region_cn_moments'][k])
-            store[key_prefix + '/region_' + k] = pd.Series(v) if v.ndim == 1 else pd.DataFrame(v.reshape(len(v), -1))
-    if 'event_extents' in fit_results:            # (config cn_event_extents)
-        ext = fit_results['event_extents']
-        store[key_prefix + '/extent_names'] = pd.Series(list(ext['names']))
-        for k in posteriors.EXTENT_ARRAYS:
-            store[key_prefix + '/extent_' + k] = pd.Series(np.asarray(ext[k]))
-    if 'event_lengths' in fit_results:            # (config cn_event_lengths)
-        ln = fit_results['event_lengths']
-        store[key_prefix + '/span_names'] = pd.Series(list(ln['names']))
-        for k in posteriors.SPAN_ARRAYS:
-            store[key_prefix + '/span_' + k] = pd.Series(np.asarray(ln[k]))
-        for k in posteriors.SPAN_EDGE_ARRAYS:
-            store[key_prefix + '/span_' + k] = pd.DataFrame(np.asarray(ln[k]))
-    if 'region_calls' in fit_results:             # (config cn_region_calls)
-        for k in posteriors.REGION_CALL_ARRAYS:
-            store[key_prefix + '/region_call_' + k] = pd.Series(np.asarray(fit_results['region_calls'][k]))
-    if 'region_cn_extremes' in fit_results:       # (config cn_region_extremes: a row per region, the clones' bins side by side)
-        for k in posteriors.EXTREME_ARRAYS:
-            v = np.asarray(fit_results['region_cn_extremes'][k])
-            store[key_prefix + '/region_' + k] = pd.DataFrame(v.reshape(len(v), -1))
-    if 'p_change_both' in fit_results:            # (config cn_breakend_changes)
-        store[key_prefix + '/breakend_p_change'] = pd.DataFrame(np.asarray(fit_results['p_change']))
-        for k in posteriors.BREAKEND_ARRAYS[1:]:
-            store[key_prefix + '/breakend_' + k] = pd.Series(np.asarray(fit_results[k]))
+    for o in outputs.STORE_ORDER:      # (the optional outputs that the result carries)
+        o.store(lambda k, table: store.__setitem__(key_prefix + '/' + k, table), fit_results)
 
 
 def store_optimal_solution(stats, store, config):

@@ -8,13 +8,12 @@ update for all restarts) and restarts are sharded over GPUs, one process per
 GPU, with ONE gather of the per-restart results at the end (RCCL over xGMI via
 torch.distributed; no communication during EM).
 """
-import collections
 import os
 
 import numpy as np
 
 from .cn_model import BreakpointModel
-from . import posteriors, synthetic
+from . import outputs, posteriors, synthetic
 
 
 class SampleList(object):
@@ -820,6 +819,26 @@ class RestartSet(object):
         return posteriors.batch_change_prob(self.batch, 0, len(self.models), m.seg_fwd_remap, m.seg_is_original, m.is_telomere)
 
 
+def _join(parts, shared=(), extend=(), each=()):
+    """One query's results from several groups of restarts, as of all their restarts in order.  Lists over restarts are
+    strung together.  Of dicts, the arrays are concatenated along the restart axis, except the keys named in `shared` (the
+    same in every part: the first part's), in `extend` (lists over restarts: strung together) and in `each` (lists of arrays
+    with a restart axis: concatenated entry by entry)."""
+    if not isinstance(parts[0], dict):
+        return [x for part in parts for x in part]
+
+    def one(k):
+        values = [part[k] for part in parts]
+        if k in shared:
+            return values[0]
+        if k in extend:
+            return [x for v in values for x in v]
+        if k in each:
+            return [np.concatenate(v) for v in zip(*values)]
+        return np.concatenate(values)
+    return dict((k, one(k)) for k in parts[0])
+
+
 class RestartGroups(object):
     """The restarts of one GPU split into `groups` RestartSets, each with its own device batch
     (own HIP stream) and its own host thread.
@@ -936,81 +955,71 @@ class RestartGroups(object):
     def results(self):
         return [r for part in self._map(lambda rs: rs.results()) for r in part]
 
+    def _own(self, rs, values):
+        """Group `rs`'s share of a per-restart argument (`values`: of all restarts, in order); None stays None."""
+        return None if values is None else values[self.slices[self.sets.index(rs)]]
+
     def sample_cn(self, num_samples, seed=0, init_ids=None):
         """RestartSet.sample_cn over the groups, restarts in order (init_ids: of all restarts, default their index)."""
         ids = list(range(self.num_restarts)) if init_ids is None else list(init_ids)
-        return [x for part in self._map(lambda rs: rs.sample_cn(num_samples, seed, ids[self.slices[self.sets.index(rs)]]))
-                for x in part]
+        return _join(self._map(lambda rs: rs.sample_cn(num_samples, seed, self._own(rs, ids))))
 
     def posterior_summary(self, cn=None, marginals=False):
         """RestartSet.posterior_summary over the groups, restarts in order (cn: of all restarts)."""
-        return [x for part in self._map(lambda rs: rs.posterior_summary(None if cn is None else cn[self.slices[self.sets.index(rs)]], marginals))
-                for x in part]
+        return _join(self._map(lambda rs: rs.posterior_summary(self._own(rs, cn), marginals)))
 
     def region_events(self, regions):
         """RestartSet.region_events over the groups, restarts in order: a dict of arrays (restarts, len(regions))."""
-        parts = self._map(lambda rs: rs.region_events(regions))
-        return dict((k, np.concatenate([p[k] for p in parts])) for k in parts[0])
+        return _join(self._map(lambda rs: rs.region_events(regions)))
 
     def region_change_counts(self, regions, bins=8):
         """RestartSet.region_change_counts over the groups, restarts in order: a dict of arrays (restarts, len(regions), bins)."""
-        parts = self._map(lambda rs: rs.region_change_counts(regions, bins))
-        return dict((k, np.concatenate([p[k] for p in parts])) for k in parts[0])
+        return _join(self._map(lambda rs: rs.region_change_counts(regions, bins)))
 
     def region_cn_extremes(self, regions, quantity='total', clone='any', bins=16, first_level=0):
         """RestartSet.region_cn_extremes over the groups, restarts in order: `bins`, `first_level` and arrays (restarts, len(regions), ...)."""
-        parts = self._map(lambda rs: rs.region_cn_extremes(regions, quantity, clone, bins, first_level))
-        return dict((k, np.concatenate([p[k] for p in parts]) if isinstance(v, np.ndarray) else v) for k, v in parts[0].items())
+        return _join(self._map(lambda rs: rs.region_cn_extremes(regions, quantity, clone, bins, first_level)), shared=('bins', 'first_level'))
 
     def region_clone_extremes(self, regions, bins=16):
         """RestartSet.region_clone_extremes over the groups, restarts in order: arrays (restarts, len(regions), M - 1, bins)."""
-        parts = self._map(lambda rs: rs.region_clone_extremes(regions, bins))
-        return dict((k, np.concatenate([p[k] for p in parts])) for k in parts[0])
+        return _join(self._map(lambda rs: rs.region_clone_extremes(regions, bins)))
 
     def region_cn_moments(self, regions):
         """RestartSet.region_cn_moments over the groups, restarts in order: `length` (len(regions),) and arrays (restarts, len(regions), ...)."""
-        parts = self._map(lambda rs: rs.region_cn_moments(regions))
-        return dict((k, parts[0][k] if k == 'length' else np.concatenate([p[k] for p in parts])) for k in parts[0])
+        return _join(self._map(lambda rs: rs.region_cn_moments(regions)), shared=('length',))
 
     def event_extent(self, anchors, event, window=64):
         """RestartSet.event_extent over the groups, restarts in order: a list over restarts of lists over anchors."""
-        return [x for part in self._map(lambda rs: rs.event_extent(anchors, event, window)) for x in part]
+        return _join(self._map(lambda rs: rs.event_extent(anchors, event, window)))
 
     def event_span(self, anchors, event, window=64):
         """RestartSet.event_span over the groups, restarts in order: a list over restarts of lists over anchors."""
-        return [x for part in self._map(lambda rs: rs.event_span(anchors, event, window)) for x in part]
+        return _join(self._map(lambda rs: rs.event_span(anchors, event, window)))
 
     def event_joint(self, patterns):
         """RestartSet.event_joint over the groups, restarts in order."""
-        parts = self._map(lambda rs: rs.event_joint(patterns))
-        out = dict((k, np.concatenate([p[k] for p in parts])) for k in ('log_p_joint', 'p_joint', 'lift'))
-        out['p_parts'] = [np.concatenate([p['p_parts'][i] for p in parts]) for i in range(len(parts[0]['p_parts']))]
-        return out
+        return _join(self._map(lambda rs: rs.event_joint(patterns)), each=('p_parts',))
 
     def focal_events(self, regions, flank=1):
         """RestartSet.focal_events over the groups, restarts in order: a dict of arrays (restarts, len(regions))."""
-        parts = self._map(lambda rs: rs.focal_events(regions, flank))
-        return dict((k, np.concatenate([p[k] for p in parts])) for k in parts[0])
+        return _join(self._map(lambda rs: rs.focal_events(regions, flank)))
 
     def breakend_changes(self, arrays=False):
         """RestartSet.breakend_changes over the groups, restarts in order."""
-        parts = self._map(lambda rs: rs.breakend_changes(arrays=True))
-        out = dict((k, np.concatenate([p[k] for p in parts])) for k in parts[0])
+        out = _join(self._map(lambda rs: rs.breakend_changes(arrays=True)))
         return out if arrays else dict((bp, dict((k, v[:, i]) for k, v in out.items())) for i, bp in enumerate(self.sets[0].models[0].breakpoints))
 
     def region_call(self, regions, event=None, cn=None):
         """RestartSet.region_call over the groups, restarts in order (cn: of all restarts)."""
-        parts = self._map(lambda rs: rs.region_call(regions, event, None if cn is None else cn[self.slices[self.sets.index(rs)]]))
-        return dict((k, [x for p in parts for x in p[k]] if k == 'cn' else np.concatenate([p[k] for p in parts])) for k in parts[0])
+        return _join(self._map(lambda rs: rs.region_call(regions, event, self._own(rs, cn))), extend=('cn',))
 
     def call_confidence(self, regions, cn=None):
         """RestartSet.call_confidence over the groups, restarts in order (cn: of all restarts): a dict of arrays (restarts, len(regions))."""
-        parts = self._map(lambda rs: rs.call_confidence(regions, None if cn is None else cn[self.slices[self.sets.index(rs)]]))
-        return dict((k, np.concatenate([p[k] for p in parts])) for k in parts[0])
+        return _join(self._map(lambda rs: rs.call_confidence(regions, self._own(rs, cn))))
 
     def cn_logprob(self, cn=None):
         """RestartSet.cn_logprob over the groups, restarts in order (cn: of all restarts): (restarts,)."""
-        return np.concatenate(self._map(lambda rs: rs.cn_logprob(None if cn is None else cn[self.slices[self.sets.index(rs)]])))
+        return np.concatenate(self._map(lambda rs: rs.cn_logprob(self._own(rs, cn))))
 
     def cn_change_prob(self):
         """RestartSet.cn_change_prob over the groups, restarts in order: (restarts, N - 1)."""
@@ -1100,13 +1109,17 @@ class DatasetGroups(object):
                 out.append(r)
         return out
 
+    def _own(self, part, values):
+        """Dataset `part`'s entry of a per-dataset argument; None stays None."""
+        return None if values is None else values[self.parts.index(part)]
+
     def sample_cn(self, num_samples, seed=0):
         """RestartGroups.sample_cn of every dataset, dataset after dataset (restart indices within each dataset)."""
-        return [x for part in self._map(lambda part: part.sample_cn(num_samples, seed)) for x in part]
+        return _join(self._map(lambda part: part.sample_cn(num_samples, seed)))
 
     def posterior_summary(self, cn=None, marginals=False):
         """RestartGroups.posterior_summary of every dataset, dataset after dataset (cn: per dataset, a list of its restarts' paths)."""
-        return [x for part in self._map(lambda part: part.posterior_summary(None if cn is None else cn[self.parts.index(part)], marginals)) for x in part]
+        return _join(self._map(lambda part: part.posterior_summary(self._own(part, cn), marginals)))
 
     def region_events(self, regions):
         """RestartGroups.region_events of every dataset: a list, one dict of arrays (restarts, len(regions)) per dataset."""
@@ -1155,11 +1168,11 @@ class DatasetGroups(object):
     def call_confidence(self, regions, cn=None):
         """RestartGroups.call_confidence of every dataset (cn: per dataset, a list of its restarts' paths): a list, one dict of arrays
         (restarts, len(regions)) per dataset."""
-        return self._map(lambda part: part.call_confidence(regions, None if cn is None else cn[self.parts.index(part)]))
+        return self._map(lambda part: part.call_confidence(regions, self._own(part, cn)))
 
     def cn_logprob(self, cn=None):
         """RestartGroups.cn_logprob of every dataset (cn: per dataset, a list of its restarts' paths): a list of (restarts,) arrays."""
-        return self._map(lambda part: part.cn_logprob(None if cn is None else cn[self.parts.index(part)]))
+        return self._map(lambda part: part.cn_logprob(self._own(part, cn)))
 
     def cn_change_prob(self):
         """RestartGroups.cn_change_prob of every dataset: a list of (restarts, N - 1) arrays."""
@@ -1252,40 +1265,14 @@ def _failure_code(message):
     return 3
 
 
-_Section = collections.namedtuple('_Section', 'length pack unpack')      # pack(res, stats, view), unpack(view, res, stats)
-
-
-def _section(fields, group=None, head=(), tail=(), add=None):
-    """One optional section of a float record: the stats `head`, the arrays `fields` ((name, shape), read from res, or
-    from res[group]) and the stats `tail`.  Unpacking puts the arrays into res, or hands them, with the tail values, to
-    add(res, arrays, *tail values)."""
-    sizes = [int(np.prod(shape)) for _, shape in fields]
-
-    def pack(res, stats, view):
-        src = res if group is None else res[group]
-        view[:len(head)] = [stats[k] for k in head]
-        o = len(head)
-        for (k, _), n in zip(fields, sizes):
-            view[o:o + n] = np.asarray(src[k]).ravel(); o += n
-        view[o:] = [stats[k] for k in tail]
-
-    def unpack(view, res, stats):
-        stats.update((k, float(v)) for k, v in zip(head, view))
-        o = len(head); arrays = {}
-        for (k, shape), n in zip(fields, sizes):
-            arrays[k] = view[o:o + n].reshape(shape).copy(); o += n
-        if add is None:
-            res.update(arrays)
-        else:
-            add(res, arrays, *view[o:])
-    return _Section(len(head) + sum(sizes) + len(tail), pack, unpack)
-
-
-def _record_sections(N, M, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0, call_confidence=False, cn_moments=False,
-                     extent_names=None, length_edges=None, breakend_k=None, region_calls=False, region_extremes=False):
+def _record_sections(N, M, K, **switches):
     """The optional sections of a float record, in record order.  The record is the fixed part -- header, h, parameters,
     outlier probabilities: _HDR + M + nparams + 4 N floats -- and then, each only when its option is on (a record without
-    it is unchanged), at offsets that are the running sum of what precedes:
+    it is unchanged), at offsets that are the running sum of what precedes.  switches: the record switches of the table
+    outputs.OUTPUTS, whose entries build their own sections -- cn_samples, cn_posterior, region_names (the regions' names,
+    None: off), change_bins (the number of bins, 0: off), call_confidence, cn_moments, extent_names (the entries' names,
+    None: off), length_edges (the number of edges, None: off), breakend_changes, region_calls, region_extremes; those left
+    out are off.  In words:
       posterior samples (num_cn_samples > 0): the six sampling.SUMMARY_STATS, cn_sample_agreement (N, M), cn_state_agreement (N,);
       posterior summary (cn_posterior_summary): the two posteriors.SUMMARY_STATS, the arrays of posteriors.COMPACT_ARRAYS;
       region events (cn_regions): the seven arrays of posteriors.REGION_ARRAYS, one entry per region;
@@ -1297,55 +1284,22 @@ def _record_sections(N, M, cn_samples=False, cn_posterior=False, region_names=No
         indices and flags as floats: exact);
       event lengths (cn_event_lengths, with extents; length_edges: the number of cn_event_length_edges): the four arrays of
         posteriors.SPAN_ARRAYS, one entry per named anchor, then the two tables of posteriors.SPAN_EDGE_ARRAYS, (entries, edges);
-      breakend changes (cn_breakend_changes; breakend_k: the number of breakpoints K): the five arrays of
+      breakend changes (cn_breakend_changes; K: the number of breakpoints): the five arrays of
         posteriors.BREAKEND_ARRAYS, p_change (K, 2) and four (K,): 6 K floats;
       region calls (cn_region_calls, with regions): the three arrays of posteriors.REGION_CALL_ARRAYS, one entry per region
         (n_differ as a float: exact);
       region extremes (cn_region_extremes, with regions): the two arrays of posteriors.EXTREME_ARRAYS, (regions, M - 1,
         posteriors.EXTREME_BINS) each: 2 (M - 1) bins floats per region, at the end of the record."""
-    from . import sampling
-    out = []
-    if cn_samples:
-        out.append(_section([('cn_sample_agreement', (N, M)), ('cn_state_agreement', (N,))], head=sampling.SUMMARY_STATS))
-    if cn_posterior:
-        out.append(_section([(k, (N, M) if k.startswith('total_cn') else (N,)) for k in posteriors.COMPACT_ARRAYS], head=posteriors.SUMMARY_STATS))
-    if region_names is not None:
-        nreg = len(region_names)
-        out.append(_section([(k, (nreg,)) for k in posteriors.REGION_ARRAYS], 'region_events',
-                            add=lambda res, a: posteriors.add_region_events(res, region_names, a)))
-        if change_bins:
-            out.append(_section([(k, (nreg, int(change_bins))) for k in posteriors.COUNT_ARRAYS], 'region_change_counts',
-                                add=lambda res, a: posteriors.add_region_change_counts(res, region_names, change_bins, a)))
-        if call_confidence:
-            out.append(_section([(k, (nreg,)) for k in posteriors.CALL_ARRAYS], 'call_confidence', tail=('cn_logprob',),
-                                add=lambda res, a, logprob: posteriors.add_call_confidence(res, region_names, a, logprob)))
-        if cn_moments:
-            shapes = posteriors.moment_shapes(nreg, M)
-            out.append(_section([(k, shapes[k]) for k in posteriors.MOMENT_ARRAYS], 'region_cn_moments', tail=posteriors.MOMENT_STATS,
-                                add=lambda res, a, *sd: posteriors.add_region_cn_moments(res, region_names, a, sd)))
-    if extent_names is not None:
-        out.append(_section([(k, (len(extent_names),)) for k in posteriors.EXTENT_ARRAYS], 'event_extents',
-                            add=lambda res, a: posteriors.add_event_extents(res, extent_names, a)))
-        if length_edges is not None:
-            nent = len(extent_names)
-            out.append(_section([(k, (nent,)) for k in posteriors.SPAN_ARRAYS] + [(k, (nent, int(length_edges))) for k in posteriors.SPAN_EDGE_ARRAYS],
-                                'event_lengths', add=lambda res, a: posteriors.add_event_lengths(res, extent_names, a)))
-    if breakend_k is not None:
-        out.append(_section([(k, (int(breakend_k), 2) if k == 'p_change' else (int(breakend_k),)) for k in posteriors.BREAKEND_ARRAYS]))
-    if region_calls and region_names is not None:
-        out.append(_section([(k, (len(region_names),)) for k in posteriors.REGION_CALL_ARRAYS], 'region_calls',
-                            add=lambda res, a: posteriors.add_region_calls(res, region_names, a)))
-    if region_extremes and region_names is not None:
-        out.append(_section([(k, (len(region_names), M - 1, posteriors.EXTREME_BINS)) for k in posteriors.EXTREME_ARRAYS], 'region_cn_extremes',
-                            add=lambda res, a: posteriors.add_region_cn_extremes(res, region_names, a)))
-    return out
+    unknown = sorted(set(switches) - set(outputs.SWITCHES_OFF))
+    if unknown:
+        raise TypeError('unknown record switch %s: one of %s' % (', '.join(unknown), ', '.join(o.switch for o in outputs.OUTPUTS)))
+    sw = dict(outputs.SWITCHES_OFF, **switches)
+    return [s for s in (o.section(sw, N, M, int(K)) for o in outputs.OUTPUTS) if s is not None]
 
 
-def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0, call_confidence=False,
-          cn_moments=False, extent_names=None, length_edges=None, breakend_changes=False, region_calls=False, region_extremes=False):
-    """One restart's results as (float64 vector, int8 vector) of fixed length."""
-    sections = _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names, length_edges,
-                                K if breakend_changes else None, region_calls, region_extremes)
+def _pack(res, N, M, K, nparams, brk_ids, param_names, **switches):
+    """One restart's results as (float64 vector, int8 vector) of fixed length.  switches: _record_sections."""
+    sections = _record_sections(N, M, K, **switches)
     o = _HDR + M + nparams
     f = np.zeros(o + 4 * N + sum(s.length for s in sections), dtype=np.float64)
     st = res['stats']
@@ -1366,11 +1320,8 @@ def _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples=False, cn_post
     return f, i8
 
 
-def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_samples=False, cn_posterior=False, region_names=None, change_bins=0,
-            call_confidence=False, cn_moments=False, extent_names=None, length_edges=None, breakend_changes=False, region_calls=False,
-            region_extremes=False):
-    sections = _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names, length_edges,
-                                K if breakend_changes else None, region_calls, region_extremes)
+def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, **switches):
+    sections = _record_sections(N, M, K, **switches)
     res = dict()
     res['h'] = f[_HDR:_HDR + M].copy()
     o = _HDR + M + nparams
@@ -1395,49 +1346,27 @@ def _unpack(f, i8, N, M, K, nparams, brk_ids, param_names, init_params, cn_sampl
 
 
 def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clones=3, num_em_iter=5, num_update_iter=5,
-                             device=None, kernel_module=None, seeds=None, quiet=True, groups=2, num_cn_samples=0, cn_sample_seed=0,
-                             cn_posterior_summary=False, cn_regions=None, cn_region_change_bins=0, cn_call_confidence=False, cn_region_moments=False,
-                             cn_event_extents=None, cn_extent_window=64, cn_event_lengths=False, cn_event_length_edges=(), cn_breakend_changes=False,
-                             cn_region_calls=False, cn_region_extremes=False, **model_kwargs):
+                             device=None, kernel_module=None, seeds=None, quiet=True, groups=2, selection=None, **kwargs):
     """Fit all restarts across the ranks of the default torch.distributed group.
 
     Every rank holds the (small, read-only) experiment; rank g fits restarts
     g, g+G, g+2G, ... on its own GPU; one all-gather of fixed-size result records
     returns every restart's results to every rank (`collate` stores all of them,
     analysis/pipeline.py:289-291).  Works on one process without torch.distributed.
-    num_cn_samples > 0: every result also summarises that many posterior samples (restart i's stream:
-    restart_seed(cn_sample_seed, i)), and the records carry the summary.
-    cn_posterior_summary: every result also carries the exact posterior summaries of posteriors.COMPACT_ARRAYS and
-    the two *_posterior_mean stats, and the records grow by them.
-    cn_regions: a list of (name, first, last) experiment segment intervals; every result also carries `region_events`
-    (posteriors.add_region_events), and the records grow by seven floats per region.
-    cn_region_change_bins: K > 0 (with cn_regions): every result also carries `region_change_counts`
-    (posteriors.add_region_change_counts), and the records grow by 2 K floats per region.
-    cn_call_confidence (with cn_regions): every result also carries `call_confidence` and stats['cn_logprob'] for its own
-    `cn` (posteriors.add_call_confidence), and the records grow by three floats per region and one.
-    cn_region_moments (with cn_regions): every result also carries `region_cn_moments` and the two *_posterior_sd stats
-    (posteriors.add_region_cn_moments), and the records grow by 21 + M + M^2 floats per region and two.
-    cn_event_extents: a list of (name, segment, event); every result also carries `event_extents` for a window of
-    cn_extent_window segments on each side (posteriors.add_event_extents), and the records grow by nine floats per entry.
-    cn_event_lengths (with cn_event_extents): every result also carries `event_lengths` (posteriors.add_event_lengths), and
-    the records grow by 4 + 2 len(cn_event_length_edges) floats per entry.
-    cn_breakend_changes: every result also carries the five arrays of posteriors.BREAKEND_ARRAYS over the breakpoints
-    (posteriors.add_breakend_changes), and the records grow by six floats per breakpoint.
-    cn_region_calls (with cn_regions): every result also carries `region_calls` (posteriors.add_region_calls), and the
-    records grow by three floats per region.
-    cn_region_extremes (with cn_regions): every result also carries `region_cn_extremes` (posteriors.add_region_cn_extremes),
-    and the records grow, at their end, by 2 (M - 1) posteriors.EXTREME_BINS floats per region.
+    The optional outputs (remixt_amd/outputs.py): keywords with the names and meanings of their config keys
+    (remixt_amd/defaults.py: num_cn_samples, cn_sample_seed, cn_posterior_summary, cn_regions, ...) are checked as a config
+    before any fit (a ValueError for an output without what it needs); or `selection`, a config already resolved.  Every
+    result carries the outputs that are on, and the records grow by their sections (_record_sections).  The other keywords
+    go to the models.
     """
     import torch
     import torch.distributed as dist
-    posteriors.check_region_options(cn_regions, cn_region_change_bins, cn_call_confidence, cn_region_moments)
-    if cn_region_calls and cn_regions is None:
-        raise ValueError('cn_region_calls needs cn_regions')
-    if cn_region_extremes and cn_regions is None:
-        raise ValueError('cn_region_extremes needs cn_regions')
-    extents = posteriors.extents_on({'cn_event_extents': cn_event_extents, 'cn_extent_window': cn_extent_window}, len(experiment.x))
-    lengths = posteriors.lengths_on({'cn_event_extents': cn_event_extents, 'cn_extent_window': cn_extent_window, 'cn_event_lengths': cn_event_lengths,
-                                     'cn_event_length_edges': cn_event_length_edges}, len(experiment.x))
+    model_kwargs = dict((k, v) for k, v in kwargs.items() if k not in outputs.CONFIG_KEYS)
+    config = dict((k, v) for k, v in kwargs.items() if k in outputs.CONFIG_KEYS)
+    if selection is None:
+        selection = outputs.resolve(config, len(experiment.x))
+    elif config:
+        raise TypeError('selection= already says which outputs are on: no %s beside it' % ', '.join(sorted(config)))
     distributed = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size() if distributed else 1
     rank = dist.get_rank() if distributed else 0
@@ -1453,172 +1382,27 @@ def fit_restarts_distributed(experiment, init_params, max_copy_number, num_clone
                            **model_kwargs)
         rs.fit(num_em_iter, num_update_iter)
         local = rs.results()
-        add_optional_outputs(rs, local, experiment, mine, num_cn_samples, cn_sample_seed, cn_posterior_summary, cn_regions, cn_region_change_bins, cn_call_confidence,
-                             cn_region_moments, cn_event_extents, cn_extent_window, cn_event_lengths, cn_event_length_edges, cn_breakend_changes, cn_region_calls,
-                             cn_region_extremes)
+        add_optional_outputs(rs, local, experiment, mine, selection)
         param_names = list(rs.models[0].likelihood_params)
         rs.close()      # (the batches' device memory and streams now, not when the collector gets to them: DESIGN 4.6)
     if param_names is None:
         nc = model_kwargs.get('normal_contamination', True)
         param_names = ['negbin_r_0', 'negbin_r_1', 'betabin_M_0', 'betabin_M_1'] + (
             [] if nc else ['negbin_hdel_mu', 'negbin_hdel_r_0', 'negbin_hdel_r_1', 'betabin_loh_p', 'betabin_loh_M_0', 'betabin_loh_M_1'])
-    return gather_result_records(local, experiment, init_params, num_clones, param_names, device=device, cn_samples=num_cn_samples > 0,
-                                 cn_posterior=bool(cn_posterior_summary),
-                                 region_names=None if cn_regions is None else [str(r[0]) for r in cn_regions], change_bins=cn_region_change_bins,
-                                 call_confidence=bool(cn_call_confidence), cn_moments=bool(cn_region_moments),
-                                 extent_names=None if extents is None else extents[0], length_edges=None if lengths is None else len(lengths[4]),
-                                 breakend_changes=bool(cn_breakend_changes), region_calls=bool(cn_region_calls),
-                                 region_extremes=bool(cn_region_extremes))
+    return gather_result_records(local, experiment, init_params, num_clones, param_names, device=device, **selection.record_switches())
 
 
-def add_region_events(rs, results, cn_regions):
-    """Add the region event probabilities of config cn_regions, a list of (name, first, last), of every restart of `rs`
-    (a RestartSet / RestartGroups; one device call per batch) to results[r] (posteriors.add_region_events)."""
-    names, regions = posteriors.parse_regions(cn_regions)
-    events = rs.region_events(regions)
-    for r, res in enumerate(results):
-        posteriors.add_region_events(res, names, dict((k, v[r]) for k, v in events.items()))
+def add_optional_outputs(rs, results, experiment, init_ids, selection):
+    """Add the optional outputs of a fit that are on in `selection` (outputs.resolve: checked before the fit) of every restart
+    of the fitted `rs` -- a RestartSet / RestartGroups, or anything with their query methods -- to results[r]; init_ids[r]
+    selects restart r's posterior-sample stream."""
+    for o in outputs.OUTPUTS:
+        if selection[o.name] is not None:
+            o.compute(rs, results, experiment, init_ids, selection)
     return results
 
 
-def add_region_change_counts(rs, results, cn_regions, bins):
-    """Add the region change counts of config cn_regions / cn_region_change_bins of every restart of `rs` (a RestartSet /
-    RestartGroups; one device call per batch) to results[r] (posteriors.add_region_change_counts)."""
-    names, regions = posteriors.parse_regions(cn_regions)
-    counts = rs.region_change_counts(regions, bins)
-    for r, res in enumerate(results):
-        posteriors.add_region_change_counts(res, names, bins, dict((k, v[r]) for k, v in counts.items()))
-    return results
-
-
-def add_call_confidence(rs, results, cn_regions):
-    """Add the call confidence of config cn_regions / cn_call_confidence of every restart of `rs` (a RestartSet /
-    RestartGroups; one device call per batch and quantity) to results[r], each for its own `cn`
-    (posteriors.add_call_confidence)."""
-    names, regions = posteriors.parse_regions(cn_regions)
-    cn = [res['cn'] for res in results]
-    conf = rs.call_confidence(regions, cn)
-    logprob = rs.cn_logprob(cn)
-    for r, res in enumerate(results):
-        posteriors.add_call_confidence(res, names, dict((k, v[r]) for k, v in conf.items()), logprob[r])
-    return results
-
-
-def add_region_cn_moments(rs, results, cn_regions):
-    """Add the region moments of config cn_regions / cn_region_moments of every restart of `rs` (a RestartSet /
-    RestartGroups; the named regions and the whole genome in the same device call) to results[r], with the two
-    *_posterior_sd stats (posteriors.add_region_cn_moments)."""
-    names, regions = posteriors.parse_regions(cn_regions)
-    mom = rs.region_cn_moments(posteriors.genome_region(regions, len(results[0]['cn']) if results else 1))
-    for r, res in enumerate(results):
-        posteriors.add_region_cn_moments(res, names, dict((k, v if k == 'length' else v[r]) for k, v in mom.items()))
-    return results
-
-
-def add_event_extents(rs, results, cn_event_extents, window):
-    """Add the event extents of config cn_event_extents / cn_extent_window of every restart of `rs` (a RestartSet /
-    RestartGroups; one device call per batch and distinct event) to results[r] (posteriors.add_event_extents)."""
-    names, anchors, events = posteriors.parse_extents(cn_event_extents)
-    per_restart = posteriors.grouped_event_extents(rs.event_extent, anchors, events, window)
-    for res, ext in zip(results, per_restart):
-        posteriors.add_event_extents(res, names, ext)
-    return results
-
-
-def add_event_lengths(rs, results, cn_event_extents, window, edges):
-    """Add the event lengths of config cn_event_lengths / cn_event_length_edges of every restart of `rs` (a RestartSet /
-    RestartGroups; one device call per batch and distinct event) to results[r] (posteriors.add_event_lengths)."""
-    names, anchors, events = posteriors.parse_extents(cn_event_extents)
-    per_restart = posteriors.grouped_event_spans(rs.event_span, anchors, events, window, edges)
-    for res, ln in zip(results, per_restart):
-        posteriors.add_event_lengths(res, names, ln)
-    return results
-
-
-def add_breakend_changes(rs, results):
-    """Add the breakend changes of config cn_breakend_changes of every restart of `rs` (a RestartSet / RestartGroups; one device
-    call per batch and kernel) to results[r] (posteriors.add_breakend_changes)."""
-    ch = rs.breakend_changes(arrays=True)
-    for r, res in enumerate(results):
-        posteriors.add_breakend_changes(res, dict((k, ch[k][r]) for k in posteriors.BREAKEND_ARRAYS))
-    return results
-
-
-def add_region_calls(rs, results, cn_regions):
-    """Add the region calls of config cn_regions / cn_region_calls of every restart of `rs` (a RestartSet / RestartGroups; one
-    device call per batch and kernel), against results[r]['cn'], to results[r] (posteriors.add_region_calls)."""
-    names, regions = posteriors.parse_regions(cn_regions)
-    calls = rs.region_call(regions, None, [res['cn'] for res in results])
-    for r, res in enumerate(results):
-        posteriors.add_region_calls(res, names, dict((k, calls[k][r]) for k in posteriors.REGION_CALL_ARRAYS))
-    return results
-
-
-def add_region_cn_extremes(rs, results, cn_regions):
-    """Add the region extremes of config cn_regions / cn_region_extremes of every restart of `rs` (a RestartSet / RestartGroups;
-    one device call per batch) to results[r] (posteriors.add_region_cn_extremes)."""
-    names, regions = posteriors.parse_regions(cn_regions)
-    ext = rs.region_clone_extremes(regions, posteriors.EXTREME_BINS)
-    for r, res in enumerate(results):
-        posteriors.add_region_cn_extremes(res, names, dict((k, ext[k][r]) for k in posteriors.EXTREME_ARRAYS))
-    return results
-
-
-def add_posterior_summaries(rs, results, experiment):
-    """Add the exact posterior summary of every restart of `rs` (a RestartSet / RestartGroups; one device call per
-    batch) to results[r] (posteriors.add_posterior_summary); cn_posterior_prob is taken at results[r]['cn']."""
-    from .posteriors import add_posterior_summary
-    summaries = rs.posterior_summary(cn=[res['cn'] for res in results])
-    for res, s in zip(results, summaries):
-        add_posterior_summary(res, s, experiment.l)
-    return results
-
-
-def add_cn_sample_summaries(rs, results, experiment, num_samples, seed, init_ids):
-    """Draw `num_samples` posterior paths of every restart of `rs` (a RestartSet / RestartGroups; restart r's stream is
-    restart_seed(seed, init_ids[r])) and add their summary to results[r] (sampling.add_sample_summary)."""
-    from .sampling import add_sample_summary
-    samples = rs.sample_cn(num_samples, seed, init_ids=list(init_ids))
-    for res, smp in zip(results, samples):
-        add_sample_summary(res, smp, experiment.l)
-    return results
-
-
-def add_optional_outputs(rs, results, experiment, init_ids, num_cn_samples=0, cn_sample_seed=0, cn_posterior_summary=False, cn_regions=None,
-                         cn_region_change_bins=0, cn_call_confidence=False, cn_region_moments=False, cn_event_extents=None, cn_extent_window=64,
-                         cn_event_lengths=False, cn_event_length_edges=(), cn_breakend_changes=False, cn_region_calls=False,
-                         cn_region_extremes=False):
-    """Add the optional outputs of a fit -- the config values of the same names -- of every restart of the fitted `rs` (a
-    RestartSet / RestartGroups) to results[r]; init_ids[r] selects restart r's posterior-sample stream.  The combination is
-    checked before the fit (posteriors.check_region_options)."""
-    if num_cn_samples > 0:
-        add_cn_sample_summaries(rs, results, experiment, num_cn_samples, cn_sample_seed, init_ids)
-    if cn_posterior_summary:
-        add_posterior_summaries(rs, results, experiment)
-    if cn_regions is not None:
-        add_region_events(rs, results, cn_regions)
-        if cn_region_change_bins:
-            add_region_change_counts(rs, results, cn_regions, cn_region_change_bins)
-        if cn_call_confidence:
-            add_call_confidence(rs, results, cn_regions)
-        if cn_region_moments:
-            add_region_cn_moments(rs, results, cn_regions)
-    if cn_event_extents is not None:
-        add_event_extents(rs, results, cn_event_extents, cn_extent_window)
-        if cn_event_lengths:
-            add_event_lengths(rs, results, cn_event_extents, cn_extent_window, tuple(cn_event_length_edges))
-    if cn_breakend_changes:
-        add_breakend_changes(rs, results)
-    if cn_region_calls and cn_regions is not None:
-        add_region_calls(rs, results, cn_regions)
-    if cn_region_extremes and cn_regions is not None:
-        add_region_cn_extremes(rs, results, cn_regions)
-    return results
-
-
-def gather_result_records(local, experiment, init_params, num_clones, param_names, device=None, timing=None, local_ids=None, cn_samples=False,
-                          cn_posterior=False, region_names=None, change_bins=0, call_confidence=False, cn_moments=False, extent_names=None,
-                          length_edges=None, breakend_changes=False, region_calls=False, region_extremes=False):
+def gather_result_records(local, experiment, init_params, num_clones, param_names, device=None, timing=None, local_ids=None, **switches):
     """The one collective of the path: every rank contributes the fixed-size records of the restarts
     it fitted (`local`, in the order of shard_indices) -- one float64 record (ELBO, h, parameters, outlier
     probabilities, failure code) and one int8 record (cn, brk_cn, masks) per restart -- and every rank gets the
@@ -1626,7 +1410,8 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
     analysis/pipeline.py:289-291).  Two all_gathers (RCCL over xGMI with the nccl backend; gloo in the CPU tests); a
     process without a process group just repacks.  `timing`: a dict that receives the message size and the seconds
     spent in the collectives.  `local_ids`: the restart ids of `local` when the ranks' shares are not shard_indices'
-    (several datasets cut over the ranks as one list of units); they are gathered first (one small all_gather)."""
+    (several datasets cut over the ranks as one list of units); they are gathered first (one small all_gather).  `switches`: the
+    optional sections of the records (_record_sections)."""
     import time
     import torch
     import torch.distributed as dist
@@ -1647,12 +1432,11 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
             per_rank = int(cnt_.item())
     if len(local) > per_rank:
         raise ValueError('gather_result_records: %d local results for a share of %d (pass local_ids for shares that are not shard_indices\')' % (len(local), per_rank))
-    flen = _HDR + M + nparams + 4 * N + sum(s.length for s in _record_sections(N, M, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments, extent_names, length_edges, K if breakend_changes else None, region_calls, region_extremes))
+    flen = _HDR + M + nparams + 4 * N + sum(s.length for s in _record_sections(N, M, K, **switches))
     ilen = N * M * 2 + K * M + 2 * N
     fbuf = np.full((per_rank, flen), np.nan); ibuf = np.zeros((per_rank, ilen), dtype=np.int8)
     for j, res in enumerate(local):
-        fbuf[j], ibuf[j] = _pack(res, N, M, K, nparams, brk_ids, param_names, cn_samples, cn_posterior, region_names, change_bins, call_confidence, cn_moments,
-                                  extent_names, length_edges, breakend_changes, region_calls, region_extremes)
+        fbuf[j], ibuf[j] = _pack(res, N, M, K, nparams, brk_ids, param_names, **switches)
     if local_ids is not None:
         ids_t = np.full((per_rank,), -1, dtype=np.int64); ids_t[:len(local_ids)] = local_ids
     t0 = time.perf_counter()
@@ -1684,8 +1468,7 @@ def gather_result_records(local, experiment, init_params, num_clones, param_name
     for g in range(world):
         ids_g = shard_indices(len(init_params), world, g) if ids_all is None else [int(i) for i in ids_all[g] if i >= 0]
         for j, i in enumerate(ids_g):
-            results[i] = _unpack(fall[g][j], iall[g][j], N, M, K, nparams, brk_ids, param_names, init_params[i], cn_samples, cn_posterior, region_names, change_bins, call_confidence,
-                                 cn_moments, extent_names, length_edges, breakend_changes, region_calls, region_extremes)
+            results[i] = _unpack(fall[g][j], iall[g][j], N, M, K, nparams, brk_ids, param_names, init_params[i], **switches)
     return results
 
 

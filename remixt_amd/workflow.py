@@ -13,7 +13,7 @@ does what the pypeliner scheduler does with the reference's workflow object; `fi
 call as a function."""
 import pickle
 
-from . import defaults, posteriors
+from . import defaults, outputs
 from .analysis import pipeline
 from .restarts import fit_restarts_distributed
 
@@ -38,6 +38,7 @@ def fit_model(experiment_filename, results_filename, config, ref_data_dir=None, 
     config = defaults.get_sample_config(config, tumour_id)
     with open(experiment_filename, 'rb') as f:
         experiment = pickle.load(f)
+    selection = outputs.resolve(config, len(experiment.x))      # (a bad combination fails before anything is computed)
     init_params, read_depth, minor_modes = pipeline.generate_init_params(experiment, config)
     ids = sorted(init_params)
     if seeds is None:
@@ -46,16 +47,7 @@ def fit_model(experiment_filename, results_filename, config, ref_data_dir=None, 
     results = fit_restarts_distributed(
         experiment, [init_params[i] for i in ids], get('max_copy_number'), num_clones=3,
         num_em_iter=get('num_em_iter'), num_update_iter=get('num_update_iter'), device=device, kernel_module=kernel_module,
-        seeds=seeds, quiet=quiet, num_cn_samples=get('num_cn_samples'), cn_sample_seed=get('cn_sample_seed'),
-        cn_posterior_summary=get('cn_posterior_summary'), cn_regions=get('cn_regions'), cn_region_change_bins=posteriors.change_bins(config),
-        cn_call_confidence=posteriors.call_confidence_on(config),
-        cn_region_moments=posteriors.region_moments_on(config),
-        cn_event_extents=get('cn_event_extents'), cn_extent_window=get('cn_extent_window'),
-        cn_event_lengths=posteriors.lengths_on(config) is not None, cn_event_length_edges=get('cn_event_length_edges'),
-        cn_breakend_changes=bool(get('cn_breakend_changes')),
-        cn_region_calls=posteriors.region_calls_on(config),
-        cn_region_extremes=posteriors.region_extremes_on(config),
-        **pipeline._model_kwargs(experiment, config))
+        seeds=seeds, quiet=quiet, selection=selection, **pipeline._model_kwargs(experiment, config))
     results = dict((ids[k], results[k]) for k in results)
     if _rank() != 0:
         return None

@@ -413,6 +413,33 @@ int rmx_region_counts(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const in
 int rmx_region_extremes(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
                         int32_t nlevel, const int16_t *levels, const uint8_t *constrain, int32_t ncol, double *logp_out);
 
+/* -- restart overlap (no reference counterpart) -------------------------------- */
+/* The exact overlap of two restarts' structured posteriors q_A, q_B of their last update_p_cn over runs of model segments
+ * (DESIGN 4.19).  Both are the Markov chains the reference's forward-backward pass defines (remixt/bpmodel.pyx:1213-1246:
+ * alphas, betas and the pairwise posterior of neighbouring segments), so for a run [first, last] of one chain
+ *   Z = sum_x q_A(x_first .. x_last)^lam * q_B(pi x_first .. pi x_last)^mu
+ * is one backward recursion over the run.  mode 0: (lam, mu) = (1/2, 1/2), Z is the Bhattacharyya coefficient BC <= 1
+ * (squared Hellinger distance 1 - BC, Bhattacharyya distance -log BC); mode 1: (1, 1), Z is the probability that independent
+ * draws of the two posteriors coincide on the run (A = B: the collision probability; 1 / Z its effective number of
+ * configurations).  pi maps a state index of A to the state index of B it is compared with, per state class.
+ *   batch_a, batch_b  the batches of the A and the B side; batch_b may be batch_a.  Two batches must describe the same problem
+ *             on the same device (segments, states, classes, clones, transition classes, breakend slots, penalty and current
+ *             transition model); the call runs on batch_a's stream behind what batch_b's stream holds when it is made, and
+ *             neither batch may be updated while it runs
+ *   pairs     int32 [npairs][2]: restart of batch_a, restart of batch_b
+ *   queries   int32 [nq][4]: first segment, last segment (of one chain), permutation index, 0
+ *   perms     int16 [nperm][C][S]: every row a bijection of [0, S)
+ *   logz_out  [npairs][nq]: log Z; -inf where the two posteriors share no configuration
+ * A (pair, query) result is bit-identical in any list of pairs, any batch of queries and any chunking.  The models are not
+ * modified.  RMX_EARG, with nothing launched: a pair index out of range, a query that crosses a chain end, a permutation index
+ * out of range, a permutation row that is not a bijection, a mode other than 0 or 1, batches of different problems or devices.
+ * RMX_EVALUE, with nothing launched: a restart without update_p_cn (rmx_last_error_restarts lists them), or a pair whose two
+ * snapshots were taken under different transition models (the message names the pair).  RMX_EASSERT: a backward step had a
+ * zero or non-finite normaliser; the failing results are NaN and the message names the first such pair.  RMX_EUNSUPPORTED:
+ * more than 1024 states. */
+int rmx_restart_overlap(rmx_batch *batch_a, rmx_batch *batch_b, int32_t npairs, const int32_t *pairs, int32_t nq, const int32_t *queries,
+                        int32_t nperm, const int16_t *perms, int32_t mode, double *logz_out);
+
 /* -- call probabilities (no reference counterpart) ---------------------------- */
 /* log-probabilities that the copy-number path agrees with a reference path over runs of model segments, under the
  * structured posterior q of the last update_p_cn of restarts r0 .. r0+nr-1.  Query i = (a, b, label index or

@@ -100,6 +100,8 @@ SYMBOLS = {
                                     C.c_int32, C.POINTER(C.c_int16), C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_int16), _dp]),
     "rmx_region_extremes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_uint8),
                                       C.c_int32, C.POINTER(C.c_int16), C.POINTER(C.c_uint8), C.c_int32, _dp]),
+    "rmx_restart_overlap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32),
+                                      C.c_int32, C.POINTER(C.c_int16), C.c_int32, _dp]),
     "rmx_sum_product": (C.c_int, [_dp, _dp, _dp, _dp, C.c_int32, C.c_int32, C.c_int32]),
     "rmx_max_product": (C.c_int, [_dp, _dp, _ip, _dp, C.c_int32, C.c_int32, C.c_int32]),
     "rmx_timer_start": (C.c_int, [C.c_void_p]),

@@ -664,6 +664,37 @@ class RemixtBatch(object):
         self._ck(self._lib.rmx_region_extremes(self._handle, r0, nr, *args, ncol, obuf.ctypes.data_as(_dp)))
         return out
 
+    def restart_overlap_raw(self, other, pairs, queries, perms, mode):
+        """log Z (npairs, nq) of the structured posteriors of pairs of restarts over runs of model segments
+        (rmx_restart_overlap): Z = sum_x q_A(x)^lam q_B(pi x)^mu, mode 0 the Bhattacharyya overlap (lam = mu = 1/2), mode 1 the
+        probability that independent draws coincide (lam = mu = 1).  other: the batch of the B side (None: this one; another
+        batch must describe the same problem on the same device); pairs int (npairs, 2): restart of this batch, restart of
+        `other`; queries int (nq, 4): first segment, last segment (both of one chain), permutation index, 0; perms int
+        (nperm, C, S): per state class, the state of B that a state of A is compared with.  -inf where the two posteriors
+        share no configuration."""
+        other = self if other is None else other
+        S, C_ = self.num_cn_states, self.cn_classes.shape[0]
+        pr = np.asarray(pairs)
+        if pr.ndim != 2 or pr.shape[1] != 2:
+            raise ValueError('pairs must have shape (npairs, 2)')
+        q = np.asarray(queries)
+        if q.ndim != 2 or q.shape[1] != 4:
+            raise ValueError('queries must have shape (nq, 4)')
+        pm = np.asarray(perms)
+        if pm.ndim != 3 or pm.shape[1] != C_ or pm.shape[2] != S:
+            raise ValueError('perms must have shape (nperm, num_classes, num_cn_states)')
+        for arr, name, lo, hi in ((pr, 'pair', -2 ** 31, 2 ** 31), (q, 'query', -2 ** 31, 2 ** 31), (pm, 'permutation', -32768, 32768)):
+            if arr.size and (arr.min() < lo or arr.max() >= hi):
+                raise ValueError('%s entry out of range' % name)
+        pr, q, pm = (np.ascontiguousarray(pr, dtype=np.int32), np.ascontiguousarray(q, dtype=np.int32), np.ascontiguousarray(pm, dtype=np.int16))
+        out = np.zeros((pr.shape[0], q.shape[0]), dtype=np.float64)
+        i32p = C.POINTER(C.c_int32)
+        bufs = [x if x.size else np.zeros(4, dtype=x.dtype) for x in (pr, q, pm, out)]
+        self._ck(self._lib.rmx_restart_overlap(self._handle, other._handle, pr.shape[0], bufs[0].ctypes.data_as(i32p), q.shape[0],
+                                               bufs[1].ctypes.data_as(i32p), pm.shape[0], bufs[2].ctypes.data_as(C.POINTER(C.c_int16)), int(mode),
+                                               bufs[3].ctypes.data_as(_dp)))
+        return out
+
     def call_logprob_raw(self, r0, nr, paths, queries, labels=None, constrain=None):
         """log-probabilities (nr, nq) that the copy-number path agrees with a reference path over runs of model segments,
         under the structured posterior of the last update_p_cn of restarts r0 .. r0+nr-1 (rmx_call_prob).  paths int

@@ -52,6 +52,10 @@ static const char *kKernelNames[KID_COUNT] = {
 //  KID_REGION_EXTENT, KID_REGION_SPAN, KID_COUNT
 //  which tests/test_region_span_cpu.py pins; before k_region_decode they ended with KID_REGION_PATTERN and "k_region_pattern";
 //  before k_region_extremes with KID_REGION_DECODE and "k_region_decode", which tests/test_region_decode_cpu.py pins as the entry after k_region_pattern)
+// The kernels that read two batches continue the ids in a list of their own (tests/test_region_extremes_cpu.py pins k_region_extremes as the
+// last of the list above): rmx_num_kernels and rmx_kernel_name run over both, and a batch's profile keeps KID_ALL slots.
+enum PairKernelId { KID_RESTART_OVERLAP = KID_COUNT, KID_ALL };
+static const char *kPairKernelNames[KID_ALL - KID_COUNT] = {"k_restart_overlap"};
 
 struct ProfRec { int id; hipEvent_t a, b; };
 
@@ -158,6 +162,7 @@ struct rmx_batch {
     int16_t *d_samp = nullptr; size_t samp_cap = 0; uint64_t *d_seeds = nullptr; uint32_t *d_sflags = nullptr;   // rmx_sample_cn: paths of a chunk of samples, seeds, flags [R]
     double *d_psum = nullptr; size_t psum_cap = 0; double *d_psw = nullptr; size_t psw_cap = 0;   // rmx_posterior_summary: output staging of a chunk (doubles), weights [C][S][Q]
     double *d_rgn = nullptr; size_t rgn_cap = 0; uint8_t *d_rgt = nullptr; size_t rgt_cap = 0; uint32_t *d_rflags = nullptr; int16_t *d_rgbp = nullptr; size_t rgbp_cap = 0;   // (d_rgbp: the back-pointer strips of a chunk of rmx_region_decode)  rmx_region_prob: outputs + queries of a chunk (doubles), label / mask / constrain tables (bytes), flags [R]
+    double *d_ovr = nullptr; size_t ovr_cap = 0; uint32_t *d_ovf = nullptr; size_t ovf_cap = 0; hipEvent_t ev_ov = nullptr;   // rmx_restart_overlap: sqrt(Wb) [TC][S][S] (built per call), flags [R + R of the other batch], the other batch's stream has reached the call
     uint16_t *d_comp = nullptr; int32_t *d_ends = nullptr; size_t comp_cap = 0, ends_cap = 0; int last_traceback = 0;      // parallel trace-back: composed maps [nr][NBLK][S], block end states [nr][NBLK]
     uint8_t *d_vit_code = nullptr; double *d_vit_val = nullptr; bool vit_code_ok = false, vit_mul_ok = false;   // 8-bit codes of T(i, o) of class 0 + their values (k_viterbi_code)
     // FB launch configuration
@@ -192,8 +197,8 @@ struct rmx_batch {
     int prof = 0;     // 0 off, 1 all kernels, 2 variational-sweep kernels only
     std::vector<ProfRec> prof_pending;
     std::vector<hipEvent_t> ev_pool;
-    double prof_ms[KID_COUNT] = {0};
-    long long prof_n[KID_COUNT] = {0};
+    double prof_ms[KID_ALL] = {0};
+    long long prof_n[KID_ALL] = {0};
     hipEvent_t tm_a = nullptr, tm_b = nullptr;
     std::vector<hipEvent_t> done_ev;   // [R] completion marker of a restart's last queued read-back
     std::mutex mu;                     // guards the profiling lists and launch sequences of concurrent callers
@@ -1273,6 +1278,7 @@ int rmx_batch_destroy(rmx_batch *b) { BIND(b);
     for (auto e : b->done_ev) hipEventDestroy(e);
     if (b->stream2) { hipStreamSynchronize(b->stream2); if (b->pooled_stream2) pool_release(b->device, 1, b->stream2); else hipStreamDestroy(b->stream2); hipEventDestroy(b->ev_fb); hipEventDestroy(b->ev_brk); }
     if (b->ev_copy) hipEventDestroy(b->ev_copy);
+    if (b->ev_ov) hipEventDestroy(b->ev_ov);
     if (b->ev_pace) hipEventDestroy(b->ev_pace);
     if (b->h_ind) { hipHostUnregister(b->h_ind); free(b->h_ind); }
     if (b->own_stream && b->stream) { if (b->pooled_stream) pool_release(b->device, 0, b->stream); else hipStreamDestroy(b->stream); }
@@ -3302,6 +3308,144 @@ int rmx_region_extremes(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const 
     });
 }
 
+// Restart overlap (k_restart_overlap): log sum_x q_A(x)^lam q_B(pi x)^mu over runs of model segments for pairs of restarts, A of
+// batch a and B of batch bb (which may be a).  Everything the kernel indexes with is checked here, before anything is queued: the
+// pairs and the permutation rows (rmxh::check_pairs, rmxh::check_permutations), the runs (check_queries), and that two batches
+// describe one problem on one device -- the kernel reads A's shared tables for both sides and only fa, post and pd_lt of B.
+// A pair is launched with the Dev of its snapshots' transition model (Wb rows when that is the current one), so both snapshots
+// of a pair must be of one model.  With two batches the launches go to a's stream behind an event recorded on bb's.  Outputs
+// and queries go through a's staging buffer of at most 64 MiB, chunked over queries and over blocks of 65535 pairs; one
+// workgroup computes a (pair, query) on its own, so a result depends on neither the pair list nor the chunking.
+static bool same_problem(const rmx_batch *a, const rmx_batch *b) {
+    const Dev &x = a->d, &y = b->d;
+    return a->device == b->device && x.N == y.N && x.S == y.S && x.SP == y.SP && x.M == y.M && x.K == y.K && x.B == y.B && x.C == y.C && x.D == y.D &&
+           x.cn_max == y.cn_max && x.NC == y.NC && x.NBE == y.NBE && x.TC == y.TC && x.tmodel == y.tmodel && x.pen == y.pen &&
+           a->cn_classes == b->cn_classes && a->seg_class == b->seg_class && a->tclass == b->tclass && a->brk_slot == b->brk_slot &&
+           a->brk_idx == b->brk_idx && a->brk_orient == b->brk_orient && a->brk_states == b->brk_states && a->tc_pairs == b->tc_pairs;
+}
+int rmx_restart_overlap(rmx_batch *a, rmx_batch *bb, int32_t npairs, const int32_t *pairs, int32_t nq, const int32_t *queries,
+                        int32_t nperm, const int16_t *perms, int32_t mode, double *logz_out) { BIND(a);
+    int rc;
+    if (!a || !bb) return fail(RMX_EARG, "restart_overlap: no batch");
+    if (nq < 1 || !queries || !logz_out) return fail(RMX_EARG, "restart_overlap: no queries or no output");
+    if (mode != 0 && mode != 1) return fail(RMX_EARG, "restart_overlap: mode must be 0 (Bhattacharyya overlap) or 1 (coincidence)");
+    if (bb != a && !same_problem(a, bb)) return fail(RMX_EARG, "restart_overlap: the two batches describe different problems or devices");
+    if (a->d.S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "restart_overlap: more than 1024 states");
+    const int64_t badp = rmxh::check_pairs(npairs, pairs, a->R, bb->R);
+    if (badp == -2) return fail(RMX_EARG, "restart_overlap: no pairs");
+    if (badp >= 0) return fail(RMX_EARG, "restart_overlap: pair index out of range (pair " + std::to_string(badp) + ")");
+    const int64_t badr = rmxh::check_permutations(nperm, a->d.C, a->d.S, perms);
+    if (badr == -2) return fail(RMX_EARG, "restart_overlap: no permutation tables");
+    if (badr >= 0) return fail(RMX_EARG, "restart_overlap: a permutation row is not a bijection of the states (permutation " + std::to_string(badr / a->d.C) + ")");
+    if ((rc = check_queries(a, "restart_overlap", nq, queries, {0, nperm, "restart_overlap: permutation index out of range"},
+                            {0, 1, "restart_overlap: field 3 of a query must be 0"}))) return rc;
+    // no update_p_cn yet (reported as require_snapshot does; restarts of either batch by their own index), then the models of a pair
+    g_err_restarts.clear();
+    for (int i = 0; i < npairs; i++) {
+        const int ra = pairs[2 * i], rb = pairs[2 * i + 1];
+        if (!a->lt_valid[ra]) g_err_restarts.push_back(ra);
+        if (!bb->lt_valid[rb]) g_err_restarts.push_back(rb);
+    }
+    if (!g_err_restarts.empty()) {
+        char buf[160]; snprintf(buf, sizeof buf, "restart_overlap before update_p_cn (restart %d)", g_err_restarts[0]);
+        return fail_flagged(RMX_EVALUE, buf);
+    }
+    for (int i = 0; i < npairs; i++) {
+        const int ra = pairs[2 * i], rb = pairs[2 * i + 1];
+        if (a->lt_model[ra] != bb->lt_model[rb]) {
+            char buf[200]; snprintf(buf, sizeof buf, "restart_overlap: the snapshots of pair %d (restarts %d, %d) were taken under different transition models", i, ra, rb);
+            return fail(RMX_EVALUE, buf);
+        }
+    }
+    // ---- blocks of pairs; inside a block the pairs under the current model first: [ra, rb, row in the block, 0] --------
+    const int S = a->d.S, C_ = a->d.C, cur_model = a->d.tmodel;
+    const int npc = std::min<int>(npairs, 65535), nblk = (npairs + npc - 1) / npc;
+    std::vector<int32_t> st((size_t)npairs * 4);
+    std::vector<int> ncur(nblk, 0);
+    bool any_wb = false;
+    for (int k = 0; k < nblk; k++) {
+        const int base = k * npc, cnt = std::min(npc, npairs - base);
+        size_t at = (size_t)base * 4;
+        for (int pass = 0; pass < 2; pass++)
+            for (int i = base; i < base + cnt; i++) {
+                const bool is_cur = a->lt_model[pairs[2 * i]] == cur_model;
+                if (is_cur != (pass == 0)) continue;
+                st[at++] = pairs[2 * i]; st[at++] = pairs[2 * i + 1]; st[at++] = i - base; st[at++] = 0;
+                if (pass == 0) ncur[k]++;
+            }
+        any_wb |= ncur[k] > 0;
+    }
+    // ---- staging: permutations and pairs in the table buffer, outputs and queries in the query buffer, flags, roots ----
+    const size_t perm_bytes = ((size_t)nperm * C_ * S * 2 + 15) / 16 * 16, pair_bytes = (size_t)npairs * 16;
+    if ((rc = grow(a, &a->d_rgt, &a->rgt_cap, perm_bytes + pair_bytes))) return rc;
+    HIPCHK(hipMemcpyAsync(a->d_rgt, perms, (size_t)nperm * C_ * S * 2, hipMemcpyHostToDevice, a->stream));
+    HIPCHK(hipMemcpyAsync(a->d_rgt + perm_bytes, st.data(), pair_bytes, hipMemcpyHostToDevice, a->stream));
+    const size_t nflag = (size_t)a->R + bb->R;
+    if ((rc = grow(a, &a->d_ovf, &a->ovf_cap, nflag))) return rc;
+    HIPCHK(hipMemsetAsync(a->d_ovf, 0, nflag * 4, a->stream));
+    const size_t budget = (size_t)64 << 20;
+    const size_t qc = std::max<size_t>(1, std::min<size_t>((size_t)nq, budget / ((size_t)npc * 8 + 16)));
+    if ((rc = grow(a, &a->d_rgn, &a->rgn_cap, (size_t)npc * qc + 2 * qc))) return rc;
+    double *dout = a->d_rgn;
+    int32_t *dq = (int32_t *)(a->d_rgn + (size_t)npc * qc);
+    RovArgs ov;
+    ov.faB = bb->d.fa; ov.postB = bb->d.post; ov.pdB = bb->d.pd_lt;
+    ov.perms = (const int16_t *)a->d_rgt; ov.queries = dq; ov.Wr = nullptr; ov.RA = a->R;
+    if (mode == 0 && any_wb && a->d.TC > 0) {
+        const size_t nw = (size_t)a->d.TC * S * S;
+        if ((rc = grow(a, &a->d_ovr, &a->ovr_cap, nw))) return rc;
+        ProfScope ps(a, KID_OTHER);
+        hipLaunchKernelGGL(k_overlap_roots, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, a->stream, a->d.Wb, a->d_ovr, nw);
+        HIPCHK(hipGetLastError());
+        ov.Wr = a->d_ovr;
+    }
+    if (bb != a) {
+        if (!a->ev_ov) HIPCHK(hipEventCreateWithFlags(&a->ev_ov, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(a->ev_ov, bb->stream));
+        HIPCHK(hipStreamWaitEvent(a->stream, a->ev_ov, 0));
+    }
+    auto kf = mode == 0 ? k_restart_overlap<0> : k_restart_overlap<1>;
+    const Dev dcur = a->d, doth = dev_for_model(a, 1 - cur_model);
+    for (size_t q0 = 0; q0 < (size_t)nq; q0 += qc) {
+        const size_t nqc = std::min(qc, (size_t)nq - q0);
+        HIPCHK(hipMemcpyAsync(dq, queries + 4 * q0, nqc * 16, hipMemcpyHostToDevice, a->stream));
+        ov.nq = (int)nqc;
+        for (int k = 0; k < nblk; k++) {
+            const int base = k * npc, cnt = std::min(npc, npairs - base);
+            const int32_t *dp = (const int32_t *)(a->d_rgt + perm_bytes) + (size_t)base * 4;
+            if (ncur[k] > 0) {
+                ProfScope ps(a, KID_RESTART_OVERLAP);
+                ov.pairs = dp;
+                hipLaunchKernelGGL(kf, dim3((unsigned)nqc, ncur[k]), dim3(RGN_NT), 0, a->stream, dcur, 1, ov, dout, a->d_ovf);
+                HIPCHK(hipGetLastError());
+            }
+            if (cnt > ncur[k]) {
+                ProfScope ps(a, KID_RESTART_OVERLAP);
+                ov.pairs = dp + (size_t)ncur[k] * 4;
+                hipLaunchKernelGGL(kf, dim3((unsigned)nqc, cnt - ncur[k]), dim3(RGN_NT), 0, a->stream, doth, 0, ov, dout, a->d_ovf);
+                HIPCHK(hipGetLastError());
+            }
+            // device [cnt][nqc] -> host rows (base .. base+cnt)[q0 .. q0+nqc)
+            HIPCHK(hipMemcpy2DAsync(logz_out + ((size_t)base * nq + q0), (size_t)nq * 8, dout, nqc * 8, nqc * 8, cnt, hipMemcpyDeviceToHost, a->stream));
+        }
+    }
+    // the flags of both batches' restarts, once everything queued has run
+    std::vector<uint32_t> fl(nflag);
+    HIPCHK(hipMemcpyAsync(fl.data(), a->d_ovf, nflag * 4, hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(hipStreamSynchronize(a->stream));
+    for (int i = 0; i < npairs; i++) {
+        const int ra = pairs[2 * i], rb = pairs[2 * i + 1];
+        if (!(fl[ra] && fl[(size_t)a->R + rb])) continue;
+        bool nan = false;
+        for (int j = 0; j < nq && !nan; j++) nan = std::isnan(logz_out[(size_t)i * nq + j]);
+        if (!nan) continue;
+        g_err_restarts.push_back(ra); g_err_restarts.push_back(rb);
+        char buf[200]; snprintf(buf, sizeof buf, "restart_overlap: a backward step has a zero or non-finite normaliser (pair %d: restarts %d, %d)", i, ra, rb);
+        return fail_flagged(RMX_EASSERT, buf);
+    }
+    return RMX_OK;
+}
+
 // Call probabilities (k_call_prob): the log-probability that the path agrees with a reference path, up to a label, at every
 // bound segment of a run.  The reference paths of the call are checked here (the kernel indexes label tables and weight rows
 // with their entries) and staged whole beside the label tables; the rest is run_queries'.  One wave computes a (restart,
@@ -3562,14 +3706,14 @@ int rmx_timer_stop(rmx_batch *b, double *ms) { BIND(b);
 }
 int rmx_profile_enable(rmx_batch *b, int32_t on) { BIND(b); prof_collect(b); b->prof = on < 0 ? 0 : (on > 2 ? 1 : on); return RMX_OK; }
 int rmx_profile_get(rmx_batch *b, int32_t id, double *ms, int64_t *n) { BIND(b);
-    if (id < 0 || id >= KID_COUNT) return fail(RMX_EARG, "bad kernel id");
+    if (id < 0 || id >= KID_ALL) return fail(RMX_EARG, "bad kernel id");
     HIPCHK(hipStreamSynchronize(b->stream));
     prof_collect(b);
     *ms = b->prof_ms[id]; *n = b->prof_n[id];
     return RMX_OK;
 }
-int rmx_profile_reset(rmx_batch *b) { BIND(b); prof_collect(b); for (int i = 0; i < KID_COUNT; i++) { b->prof_ms[i] = 0; b->prof_n[i] = 0; } return RMX_OK; }
-const char *rmx_kernel_name(int32_t id) { return (id >= 0 && id < KID_COUNT) ? kKernelNames[id] : ""; }
-int rmx_num_kernels(void) { return KID_COUNT; }
+int rmx_profile_reset(rmx_batch *b) { BIND(b); prof_collect(b); for (int i = 0; i < KID_ALL; i++) { b->prof_ms[i] = 0; b->prof_n[i] = 0; } return RMX_OK; }
+const char *rmx_kernel_name(int32_t id) { return (id >= 0 && id < KID_COUNT) ? kKernelNames[id] : ((id >= KID_COUNT && id < KID_ALL) ? kPairKernelNames[id - KID_COUNT] : ""); }
+int rmx_num_kernels(void) { return KID_ALL; }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 //   check_patterns       rmx_region_pattern: the rules of the piece lists of its queries
 //   decode_max_len_ok, check_decode_lengths, decode_plan  rmx_region_decode: the length rules and the chunks of a call
 //   extremes_ncol_ok, check_levels  rmx_region_extremes: the column rule, and that no level entry is negative
+//   check_pairs, check_permutations  rmx_restart_overlap: the restart pairs lie inside the two batches, every permutation row is a bijection
 //   weighted_search      rmx_weighted_search: numpy's cumsum / searchsorted(side='right') for the weighted M-step samples
 //                        (reference remixt/cn_model.py:475-480)
 //   weighted_sample_round  rmx_weighted_sample_round: a whole round of that sampling from a strided weight column
@@ -143,6 +144,30 @@ inline int64_t check_levels(int64_t C, int64_t nlevel, int64_t S, const int16_t 
     const uint64_t n = (uint64_t)C * (uint64_t)nlevel * (uint64_t)S;      // (each extent is below 2^31 in a batch; the caller's are int32)
     if (n > 0 && !levels) return -2;
     for (uint64_t i = 0; i < n; i++) if (levels[i] < 0) return (int64_t)i;
+    return -1;
+}
+
+// rmx_restart_overlap.  Its pairs [npairs][2]: a restart of batch A in [0, RA) and one of batch B in [0, RB).  Returns the index
+// of the first pair outside, -1 if there is none, or -2 for arguments that describe no list (no pair, or pairs without a pointer)
+inline int64_t check_pairs(int64_t npairs, const int32_t *pairs, int64_t RA, int64_t RB) {
+    if (npairs < 1 || !pairs || RA < 0 || RB < 0) return -2;
+    for (int64_t i = 0; i < npairs; i++)
+        if (pairs[2 * i] < 0 || pairs[2 * i] >= RA || pairs[2 * i + 1] < 0 || pairs[2 * i + 1] >= RB) return i;
+    return -1;
+}
+// its state permutations [nperm][C][S]: every row is a bijection of [0, S).  Returns the index (p * C + c) of the first row that
+// is not -- an entry outside [0, S) or a repeated one --, -1 if there is none, or -2 for arguments that describe no table
+inline int64_t check_permutations(int64_t nperm, int64_t C, int64_t S, const int16_t *perms) {
+    if (nperm < 1 || C < 1 || S < 1 || S > 32767 || !perms) return -2;
+    std::vector<uint8_t> seen((size_t)S);
+    for (int64_t row = 0; row < nperm * C; row++) {
+        std::fill(seen.begin(), seen.end(), (uint8_t)0);
+        const int16_t *p = perms + (size_t)row * (size_t)S;
+        for (int64_t s = 0; s < S; s++) {
+            if (p[s] < 0 || p[s] >= S || seen[(size_t)p[s]]) return row;
+            seen[(size_t)p[s]] = 1;
+        }
+    }
     return -1;
 }
 

@@ -7419,3 +7419,175 @@ __global__ __launch_bounds__(RGN_NT) void k_region_decode(Dev d, int r0, int use
         out[(size_t)ri * q.nq + qi] = failed ? __builtin_nan("") : logp;
     }
 }
+
+// =============================================================================
+// Restart overlap: log Z of two restarts' structured posteriors over the model segments [a, b] of one chain,
+//   Z = sum_x q_A(x_a .. x_b)^lam q_B(pi x_a .. pi x_b)^mu,   (lam, mu) = (1/2, 1/2) (MODE 0: the Bhattacharyya overlap) or (1, 1)
+// (MODE 1: the probability that independent draws of the two coincide), pi a bijection of the states per state class.  Both
+// chains are Markov with k_region_prob's backward kernel, so with g_b(s) = post_A,b(s)^lam post_B,b(pi s)^mu and, for n = b - 1 .. a,
+//   h(s')  = g_n+1(s') / (D_A,n(s')^lam D_B,n(pi s')^mu),      D_X,n(t') = sum_t fa_X,n(t) W_X,n(t, t') in X's own indexing,
+//   g_n(s) = fa_A,n(s)^lam fa_B,n(pi s)^mu sum_s' W_A,n(s, s')^lam W_B,n(pi s, pi s')^mu h(s'),             Z = sum_s g_a(s);
+// g is divided by its sum after every step, the start included, and the logarithms of the sums are added up.  Nothing of
+// either model is written.  Roots are taken of factors, never of a product (a product of two weights near e^-650 is 0, each
+// root an ordinary number): sqrt(fa_A) sqrt(fa_B), sqrt(D_A) sqrt(D_B), on Wb rows the table of roots q.Wr, and for a log weight
+// exp(T_A / 2 + T_B / 2), the halves added before the one exponential.  In MODE 1 a product that underflows is a contribution
+// below 1e-300 and goes to 0.
+// One workgroup of RGN_NT threads per (pair, query); a step is k_region_prob's two passes with both restarts' rows in each:
+//   Wb (plain adjacency, both snapshots under the current model: the shared table serves both sides): D_A(s') and D_B(pi s') for
+//     the s' with g(s') > 0 (compacted in state order) take 16 lanes per s' striding the rows s' and pi s'; g(s) has the thread own
+//     s and walk the compacted s': the A operand is a run of consecutive s, the B operand is gathered at (pi s', pi s).
+//   exp(trans_value), each side with its own breakend table (or both with the plain table Tval of the other transition model):
+//     the thread owns s' in the D pass, 16 lanes per s stride s' in the g pass.
+// Every sum has one order, fixed by the state count alone, and there are no atomics on results: a (pair, query) result does not
+// depend on the launch.  Only columns s < S of fa / post are read.  A D that is 0 or not finite under g(s') > 0, or a sum of g
+// that is not a finite number >= 0, sets ROV_ERR_DENOM in flags[restart of A] and flags[RA + restart of B] and gives NaN; a sum
+// of exactly 0 (disjoint supports) gives -inf.
+// grid (queries, pairs), block RGN_NT; out[row of the pair * nq + query].  Static LDS: g, h, both fa rows (4 x 8 KB), the
+// compacted list and the permutation rows of segments n and n + 1 (3 x 2 KB): 38 KB, four workgroups per CU.
+// =============================================================================
+#define ROV_ERR_DENOM 1u
+struct RovArgs {
+    const double *faB, *postB, *pdB;   // restart B's planes, strides as A's: [RB][N][SP], [RB][N][SP], [RB][NBE][M][D]
+    const int32_t *pairs;              // [np][4]: restart of A, restart of B, output row, 0
+    const int32_t *queries;            // [nq][4]: a, b, permutation index, 0
+    const int16_t *perms;              // [nperm][C][S]: state of A -> the state of B it is compared with
+    const double *Wr;                  // [TC][S][S] sqrt(Wb) (MODE 0 with Wb rows), else null
+    int nq, RA;
+};
+// x^lam y^mu, and g / (DA^lam DB^mu): the roots of the factors; in MODE 1 one division after the other (DA DB may underflow)
+template <int MODE> __device__ __forceinline__ double rov_mul(double x, double y) { return MODE == 0 ? sqrt(x) * sqrt(y) : x * y; }
+template <int MODE> __device__ __forceinline__ double rov_div(double g, double DA, double DB) { return MODE == 0 ? g / (sqrt(DA) * sqrt(DB)) : (g / DA) / DB; }
+// the roots of the plain weight tables: n entries
+__global__ void k_overlap_roots(const double *W, double *Wr, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) Wr[i] = sqrt(W[i]);
+}
+template <int MODE>
+__global__ __launch_bounds__(RGN_NT) void k_restart_overlap(Dev d, int use_wb, RovArgs q, double *out, uint32_t *flags) {
+    __shared__ double g[RGN_MAXS], h[RGN_MAXS], fA[RGN_MAXS], fB[RGN_MAXS];
+    __shared__ double red[RGN_NT / 64];
+    __shared__ int16_t pm[2][RGN_MAXS], idx[RGN_MAXS];
+    __shared__ int nact, s_bad;
+    const int qi = blockIdx.x, pi = blockIdx.y, tid = threadIdx.x;
+    const int grp = tid / RGN_GL, gl = tid % RGN_GL;
+    const int S = d.S;
+    const int rA = q.pairs[4 * pi], rB = q.pairs[4 * pi + 1], orow = q.pairs[4 * pi + 2];
+    const int a = q.queries[4 * qi], b = q.queries[4 * qi + 1];
+    const int16_t *perm = q.perms + (size_t)q.queries[4 * qi + 2] * d.C * S;
+    if (tid == 0) s_bad = 0;
+    int cur = 0;              // pm[cur]: the permutation row of segment n + 1
+    double logp = 0.;
+    bool failed = false;
+    // ---- start: g_b(s) = post_A(s)^lam post_B(pi s)^mu ---------------------------------------------------
+    {
+        const double *pA = d.post + rs_off(d, rA, b), *pB = q.postB + rs_off(d, rB, b);
+        const int16_t *pr = perm + (size_t)d.seg_class[b] * S;
+        double part = 0.;
+        for (int s = tid; s < S; s += RGN_NT) {
+            const int t = pr[s];
+            pm[cur][s] = (int16_t)t;
+            const double v = rov_mul<MODE>(pA[s], pB[t]);
+            g[s] = v; part += v;
+        }
+        const double Z = rgn_block_sum(part, red);
+        if (rgn_take_sum(Z, false, logp, failed))
+            for (int s = tid; s < S; s += RGN_NT) g[s] = g[s] / Z;
+    }
+    for (int n = b - 1; n >= a && !failed && logp > -INFINITY; n--) {
+        const auto [wb, Wt, pdA] = rgn_adj(d, rA, n, use_wb);
+        const double *pdB = pdA ? q.pdB + ((size_t)rB * d.NBE + d.brk_slot[n]) * d.M * d.D : nullptr;
+        const double *faA = d.fa + rs_off(d, rA, n), *faB = q.faB + rs_off(d, rB, n);
+        const int16_t *pr = perm + (size_t)d.seg_class[n] * S;
+        const int16_t *p1 = pm[cur];
+        int16_t *p0 = pm[cur ^ 1];
+        for (int s = tid; s < S; s += RGN_NT) {
+            fA[s] = faA[s]; fB[s] = faB[s];
+            p0[s] = pr[s];
+        }
+        __syncthreads();
+        if (wb) {
+            const double *Wm = MODE == 0 ? q.Wr + (Wt - d.Wb) : Wt;      // the table the g pass multiplies: the roots, or the weights
+            // the states s' with g(s') > 0, in state order
+            const int na = rgn_compact(S, idx, nact, [&](int s) { return g[s] > 0.; });
+            // D_A(s'), D_B(pi s') and h(s'): 16 lanes per s'
+            for (int j0 = 0; j0 < na; j0 += RGN_NT / RGN_GL) {
+                const int j = j0 + grp;
+                const bool ok = j < na;
+                const int sp = ok ? idx[j] : 0;
+                double pa = 0., pb = 0.;
+                if (ok) {
+                    const double *wa = Wt + (size_t)sp * S, *wr = Wt + (size_t)p1[sp] * S;
+                    for (int s = gl; s < S; s += RGN_GL) {
+                        pa = fma(fA[s], wa[s], pa);
+                        pb = fma(fB[s], wr[s], pb);
+                    }
+                }
+                const double DA = group_sum(pa, RGN_GL), DB = group_sum(pb, RGN_GL);
+                if (ok && gl == 0) {
+                    if (!(DA > 0. && DA < INFINITY && DB > 0. && DB < INFINITY)) s_bad = 1;
+                    h[j] = rov_div<MODE>(g[sp], DA, DB);
+                }
+            }
+            __syncthreads();
+            // g(s): the thread owns s; W_A(s, s') is a run of consecutive s, W_B(pi s, pi s') is gathered
+            for (int s = tid; s < S; s += RGN_NT) {
+                const int t = p0[s];
+                const double f = rov_mul<MODE>(fA[s], fB[t]);
+                const double *wa = Wm + s, *wr = Wm + t;
+                double acc = 0.;
+#pragma unroll 4
+                for (int j = 0; j < na; j++) {
+                    const int sp = idx[j];
+                    acc = fma(wa[(size_t)sp * S] * wr[(size_t)p1[sp] * S], h[j], acc);
+                }
+                g[s] = acc * f;
+            }
+        } else {
+            // D_A(s'), D_B(pi s') and h(s'): the thread owns s'
+            for (int sp = tid; sp < S; sp += RGN_NT) {
+                const double gv = g[sp];
+                double hv = 0.;
+                if (gv > 0.) {
+                    const double DA = rgn_D_exp(d, n, sp, fA, pdA), DB = rgn_D_exp(d, n, p1[sp], fB, pdB);
+                    if (!(DA > 0. && DA < INFINITY && DB > 0. && DB < INFINITY)) s_bad = 1;
+                    hv = rov_div<MODE>(gv, DA, DB);
+                }
+                h[sp] = hv;
+            }
+            __syncthreads();
+            // g(s): 16 lanes per s
+            for (int s0 = 0; s0 < S; s0 += RGN_NT / RGN_GL) {
+                const int s = s0 + grp;
+                const int t = s < S ? p0[s] : 0;
+                const double f = s < S ? rov_mul<MODE>(fA[s], fB[t]) : 0.;
+                const bool ok = f != 0.;
+                double p = 0.;
+                if (ok) {
+                    for (int sp = gl; sp < S; sp += RGN_GL) {
+                        const double hv = h[sp];
+                        if (hv != 0.) {
+                            const double TA = trans_value(d, n, s, sp, pdA), TB = trans_value(d, n, t, p1[sp], pdB);
+                            p = fma(MODE == 0 ? exp(0.5 * TA + 0.5 * TB) : exp(TA + TB), hv, p);
+                        }
+                    }
+                }
+                const double sum = group_sum(p, RGN_GL);
+                if (s < S && gl == 0) g[s] = ok ? sum * f : 0.;
+            }
+        }
+        __syncthreads();
+        double part = 0.;
+        for (int s = tid; s < S; s += RGN_NT) part += g[s];
+        const double Z = rgn_block_sum(part, red);
+        if (rgn_take_sum(Z, s_bad != 0, logp, failed))
+            for (int s = tid; s < S; s += RGN_NT) g[s] = g[s] / Z;
+        cur ^= 1;
+    }
+    if (tid == 0) {
+        if (failed) {
+            atomicOr(&flags[rA], ROV_ERR_DENOM);
+            atomicOr(&flags[q.RA + rB], ROV_ERR_DENOM);
+        }
+        out[(size_t)orow * q.nq + qi] = failed ? __builtin_nan("") : logp;
+    }
+}

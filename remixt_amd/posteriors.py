@@ -1493,3 +1493,149 @@ def region_extremes_on(config):
     if on and defaults.get_param(config, 'cn_regions') is None:
         raise ValueError('cn_region_extremes needs cn_regions')
     return on
+
+
+# ---- overlap between two restarts' structured posteriors (rmx_restart_overlap) ----
+OVERLAP_MODES = (('log_overlap', 0), ('log_coincidence', 1))
+
+
+def clone_permutations(num_clones):
+    """The (M - 1)! orders of the tumour clones as clone maps, identity first: tuples p of length M with p[0] == 0 (the normal
+    clone stays) -- clone m of restart A is compared with clone p[m] of restart B."""
+    import itertools
+    return [(0,) + p for p in itertools.permutations(range(1, int(num_clones)))]
+
+
+def state_permutation_tables(cn_classes, perms):
+    """int16 (P, C, S): for every clone map of `perms` and every state class, the state index of B that a state index of A is
+    compared with -- the table entry whose clone p[m] carries the copy numbers of A's clone m.  A state table holds one
+    representative of {state, both alleles swapped in every clone} (cn_model.create_cn_states), so the image is the entry equal
+    to the permuted copy numbers or to their allele swap; a table without such an entry is a ValueError."""
+    cn = np.asarray(cn_classes, dtype=np.int64)
+    C_, S, M = cn.shape[:3]
+    out = np.zeros((len(perms), C_, S), dtype=np.int16)
+    for c in range(C_):
+        index = dict((cn[c, s].tobytes(), s) for s in range(S))
+        for i, p in enumerate(perms):
+            p = np.asarray(p, dtype=np.int64)
+            if sorted(p.tolist()) != list(range(M)) or p[0] != 0:
+                raise ValueError('a clone map is a permutation of the clones that keeps the normal clone')
+            target = np.zeros_like(cn[c])
+            target[:, p] = cn[c]
+            for s in range(S):
+                t = index.get(target[s].tobytes())
+                if t is None:
+                    t = index.get(np.ascontiguousarray(target[s, :, ::-1]).tobytes())
+                if t is None:
+                    raise ValueError('state table %d has no entry for state %d under the clone map %s' % (c, s, tuple(p.tolist())))
+                out[i, c, s] = t
+    return out
+
+
+def batch_restart_overlap(batches, offsets, pairs, regions, seg_fwd_remap, seg_is_original, is_telomere, perm_tables, mode):
+    """log Z (npairs, len(regions), nmaps) of rmx_restart_overlap's `mode` for pairs of restarts over experiment-order
+    regions, under every state permutation of perm_tables (nmaps, C, S).  The restarts are those of `batches` in order,
+    batch g holding restarts offsets[g] .. offsets[g + 1] - 1; a pair may straddle two batches.  Chains are independent
+    under the structured posterior, so a region's log Z is the sum over its pieces (region_queries, combine).  One device
+    call per pair of batches that the pairs touch."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    if len(pairs) and (pairs.min() < 0 or pairs.max() >= offsets[-1]):
+        raise ValueError('a pair names a restart outside the set')
+    cs, ce = chains_from_telomeres(is_telomere)
+    runs, piece_region, _ = region_queries(regions, seg_fwd_remap, seg_is_original, cs, ce)
+    P, R, nmaps = len(runs), len(np.asarray(regions).reshape(-1, 2)), len(perm_tables)
+    out = np.zeros((len(pairs), R, nmaps))
+    if P == 0 or len(pairs) == 0:
+        return out
+    q = np.zeros((nmaps, P, 4), dtype=np.int32)
+    q[:, :, :2] = runs[None]
+    q[:, :, 2] = np.arange(nmaps)[:, None]
+    group = np.searchsorted(offsets, pairs, side='right') - 1      # the batch of either side
+    for ga, gb in sorted(set(map(tuple, group.tolist()))):
+        sel = np.flatnonzero((group[:, 0] == ga) & (group[:, 1] == gb))
+        local = pairs[sel] - offsets[[ga, gb]][None]
+        logz = batches[ga].restart_overlap_raw(batches[gb], local, q.reshape(-1, 4), perm_tables, mode).reshape(len(sel), nmaps, P)
+        out[sel] = np.moveaxis(combine(logz, piece_region, R), 1, 2)
+    return out
+
+
+def cluster_restarts(distance, threshold):
+    """Single-linkage clusters of restarts: i and j share a cluster when a chain of restarts joins them whose consecutive
+    distances are all <= threshold.  distance: symmetric (R, R) (NaN: no link).  Returns int labels (R,), numbered in the order
+    of each cluster's first member."""
+    d = np.asarray(distance, dtype=float)
+    R = d.shape[0]
+    if d.shape != (R, R):
+        raise ValueError('distance must be a square matrix')
+    with np.errstate(invalid='ignore'):
+        link = (d <= threshold) | (d.T <= threshold)
+    labels = np.full(R, -1, dtype=np.int64)
+    k = 0
+    for i in range(R):
+        if labels[i] >= 0:
+            continue
+        labels[i] = k
+        todo = [i]
+        while todo:
+            j = todo.pop()
+            for m in np.flatnonzero(link[j] & (labels < 0)):
+                labels[m] = k
+                todo.append(int(m))
+        k += 1
+    return labels
+
+
+def pair_matrix(pairs, values, num_restarts, diagonal=0.):
+    """Symmetric (R, R) matrix of a per-pair value (NaN where no pair was computed; `diagonal` on the diagonal)."""
+    out = np.full((num_restarts, num_restarts), np.nan)
+    np.fill_diagonal(out, diagonal)
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    out[pr[:, 0], pr[:, 1]] = values
+    out[pr[:, 1], pr[:, 0]] = values
+    return out
+
+
+def overlap_summary(pairs, clone_maps, log_overlap, log_coincidence, self_log_coincidence, num_real_segments):
+    """What .restart_overlap returns, from the raw sums: `pairs` (npairs, 2), `clone_maps`, `log_overlap` and `log_coincidence`
+    (npairs, nreg + 1, nmaps; the whole genome is the last region), `clone_map` (npairs,): the map with the largest
+    whole-genome log overlap, `hellinger` (npairs, nreg): the Hellinger distance sqrt(1 - BC) of every region at that map,
+    `distance_rate` (npairs, nmaps): -log BC of the genome per real segment -- BC of a whole genome multiplies over tens of
+    thousands of segments and is 0 for any two distinct fits, the rate is the number to cluster on --, and
+    `self_log_coincidence` (R, nreg + 1): the log collision probability of every restart's own region posterior."""
+    lo = np.asarray(log_overlap, dtype=float)
+    npairs = lo.shape[0]
+    best = np.zeros(npairs, dtype=np.int64)
+    if npairs:
+        with np.errstate(invalid='ignore'):
+            best = np.argmax(np.where(np.isnan(lo[:, -1, :]), -np.inf, lo[:, -1, :]), axis=1)
+    at = lo[np.arange(npairs), :-1, best] if npairs else np.zeros((0, lo.shape[1] - 1))
+    with np.errstate(invalid='ignore'):
+        hell = np.sqrt(np.maximum(-np.expm1(np.minimum(at, 0.)), 0.))
+    return {'pairs': np.asarray(pairs, dtype=np.int64).reshape(-1, 2), 'clone_maps': [tuple(int(v) for v in p) for p in clone_maps],
+            'log_overlap': lo, 'log_coincidence': np.asarray(log_coincidence, dtype=float), 'clone_map': best, 'hellinger': hell,
+            'distance_rate': -lo[:, -1, :] / float(num_real_segments), 'self_log_coincidence': np.asarray(self_log_coincidence, dtype=float)}
+
+
+def restart_overlap(batches, counts, model, regions=None, pairs=None, clone_maps='all'):
+    """The exact overlap between the restarts of `batches` (RemixtBatch objects of one problem on one device; batch g holds
+    counts[g] restarts; `model`: any of their BreakpointModels, for the segment maps): overlap_summary of the Bhattacharyya
+    overlap and the coincidence probability of every pair (default: all i < j across the batches) over `regions`
+    ((first, last) experiment segments; the whole genome is always appended) under every clone map (default 'all':
+    clone_permutations)."""
+    if any(b is None or not hasattr(b, 'restart_overlap_raw') for b in batches):
+        raise NotImplementedError('restart_overlap needs the device batches of the HIP library')
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    R = int(offsets[-1])
+    cn_classes = np.asarray(batches[0].cn_classes)
+    maps = clone_permutations(cn_classes.shape[2]) if isinstance(clone_maps, str) and clone_maps == 'all' else [tuple(p) for p in clone_maps]
+    tables = state_permutation_tables(cn_classes, maps)
+    if pairs is None:
+        pairs = [(i, j) for i in range(R) for j in range(i + 1, R)]
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    reg = genome_region([] if regions is None else regions, len(model.seg_fwd_remap))
+    args = (reg, model.seg_fwd_remap, model.seg_is_original, model.is_telomere)
+    raw = dict((name, batch_restart_overlap(batches, offsets, pairs, *args, tables, mode)) for name, mode in OVERLAP_MODES)
+    own = np.stack([np.arange(R), np.arange(R)], axis=1)
+    self_lc = batch_restart_overlap(batches, offsets, own, *args, tables[:1], 1)[:, :, 0]
+    return overlap_summary(pairs, maps, raw['log_overlap'], raw['log_coincidence'], self_lc, int(np.count_nonzero(model.seg_is_original)))

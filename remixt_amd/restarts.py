@@ -701,6 +701,14 @@ class RestartSet(object):
         m = self.models[0]
         return posteriors.batch_clone_extremes(self.batch, 0, len(self.models), regions, m.seg_fwd_remap, m.seg_is_original, m.is_telomere, bins=bins)
 
+    def restart_overlap(self, regions=None, pairs=None, clone_maps='all'):
+        """The exact overlap between the restarts' structured posteriors (posteriors.restart_overlap): for every
+        pair (default all i < j) and every order of the tumour clones, the log Bhattacharyya overlap and the log probability
+        that independent draws coincide over `regions` and the whole genome (the last region), the best clone map, the
+        Hellinger distance of every region at it, and the per-segment distance rate to cluster on (posteriors.cluster_restarts)."""
+        from . import posteriors
+        return posteriors.restart_overlap([self.batch], [len(self.models)], self.models[0], regions, pairs, clone_maps)
+
     def region_cn_moments(self, regions):
         """BreakpointModel.region_cn_moments of every restart from one device call per feature group: a dict of `length`
         (len(regions),) and arrays (restarts, len(regions), ...)."""
@@ -984,6 +992,13 @@ class RestartGroups(object):
         """RestartSet.region_clone_extremes over the groups, restarts in order: arrays (restarts, len(regions), M - 1, bins)."""
         return _join(self._map(lambda rs: rs.region_clone_extremes(regions, bins)))
 
+    def restart_overlap(self, regions=None, pairs=None, clone_maps='all'):
+        """RestartSet.restart_overlap over all restarts of all groups, restarts in order: a pair may straddle two groups (the call
+        then reads both groups' batches).  The groups must be idle."""
+        from . import posteriors
+        self.synchronize()
+        return posteriors.restart_overlap(self.batches, [len(rs.models) for rs in self.sets], self.models[0], regions, pairs, clone_maps)
+
     def region_cn_moments(self, regions):
         """RestartSet.region_cn_moments over the groups, restarts in order: `length` (len(regions),) and arrays (restarts, len(regions), ...)."""
         return _join(self._map(lambda rs: rs.region_cn_moments(regions)), shared=('length',))
@@ -1160,6 +1175,11 @@ class DatasetGroups(object):
     def region_clone_extremes(self, regions, bins=16):
         """RestartGroups.region_clone_extremes of every dataset: a list, one dict per dataset."""
         return self._map(lambda part: part.region_clone_extremes(regions, bins))
+
+    def restart_overlap(self, regions=None, pairs=None, clone_maps='all'):
+        """RestartGroups.restart_overlap of every dataset: a list, one dict per dataset (pairs stay within a dataset and
+        count its restarts from 0)."""
+        return self._map(lambda part: part.restart_overlap(regions, pairs, clone_maps))
 
     def region_call(self, regions, event=None):
         """RestartGroups.region_call of every dataset: a list, one dict per dataset."""

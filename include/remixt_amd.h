@@ -503,6 +503,36 @@ int rmx_region_moments(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const i
 int rmx_region_extent(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks,
                       int32_t nlabel, const int16_t *labels, const uint8_t *constrain, int32_t wl, int32_t wr, double *logp_out);
 
+/* Region conditionals: the marginal of every segment of a window given that an event of rmx_region_prob holds over an evidence
+ * run inside it -- "suppose it is so: what follows?".  The structured posterior is the Markov chain of the
+ * reference's forward-backward pass (remixt/bpmodel.pyx:1213-1246: alphas, betas and the pairwise posterior of neighbouring
+ * segments; the reference itself only reads the unconditional marginals off it), so c_n separates the two sides of n and
+ *   q(c_n = s | E) = P(E on [a, n] | c_n = s) * q(c_n = s, E on [n, b]) / P(E)
+ * at every n of the chain, from one walk per direction.  Query i = (a, b, mask index or -1, label index or -1) is the evidence
+ * run with the event E of rmx_region_prob; windows[i] = (lo, hi), lo <= a, b <= hi, all of one chain, names the segments that
+ * come back.  Slot k of a query stands for model segment lo + k and holds Q + 3 doubles:
+ *   out[r][i][k][q]     = sum_s q(c_n = s | E) * weights[seg_class[n]][s][q],   q < Q   (weights [C][S][Q], as rmx_posterior_summary)
+ *   out[r][i][k][Q]     = max_s q(c_n = s | E)
+ *   out[r][i][k][Q + 1] = the first index of that maximum, as a double
+ *   out[r][i][k][Q + 2] = q(c_n = states[r][n] | E), 0 where states is NULL (states [nr][N], indices into the segment's class table)
+ * and logp_out[r][i] = log P(E).  Slots past hi are NaN.  An impossible event gives logp_out = -inf and NaN in every slot of the
+ * query; it is no error.  Without mask and label the slots are rmx_posterior_summary's.  The model is not modified.
+ *   masks, labels, constrain   as rmx_region_prob
+ *   nslot     slots per query: the longest window or more, <= 16384; an evidence run holds at most 4096 segments
+ *   Q         1 .. 64
+ * A (restart, query) slot is bit-identical in any restart range, any batch of queries, any chunking and any window that covers
+ * it.  A call is split into chunks of (restart, query) pairs whose outputs fit 64 MiB of staging and whose evidence rows fit a
+ * 256 MiB device workspace ((longest run) * S doubles per pair); both buffers stay with the batch and only grow.
+ * RMX_EARG, with nothing launched and both outputs untouched: a bad range, nq < 1, a missing pointer, Q outside [1, 64], nslot
+ * outside [1, 16384], a run or window outside [0, N) or out of order, a window that does not cover its run, crosses a chain end
+ * or is longer than nslot, a run longer than 4096, a mask or label index out of range, a state index outside [0, S).
+ * RMX_EVALUE with the restarts listed: a restart has had no update_p_cn.  RMX_EASSERT with the restarts listed: a step met a
+ * zero or non-finite normaliser, or a sum that is not a finite number >= 0 (logp_out and every slot of that query are NaN).
+ * RMX_EUNSUPPORTED: more than 1024 states. */
+int rmx_region_conditional(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, const int32_t *windows, int32_t nslot,
+                           int32_t nmask, const uint8_t *masks, int32_t nlabel, const int16_t *labels, const uint8_t *constrain, int32_t Q,
+                           const double *weights, const int16_t *states, double *logp_out, double *out);
+
 /* Region event spans: the joint law of where an event of rmx_region_prob begins and ends around an anchor segment, and so of
  * its length.  Query i = (anchor n0, mask index or -1, label index or -1, 0); with the event E of rmx_region_prob,
  *   logp_out[r][i][a][c] = log P(E on [n0 - a, n0 + c]),   a = 0 .. wl,   c = 0 .. wr.
@@ -589,6 +619,10 @@ int rmx_profile_get(rmx_batch *b, int32_t kernel_id, double *total_ms, int64_t *
 int rmx_profile_reset(rmx_batch *b);
 const char *rmx_kernel_name(int32_t kernel_id);
 int rmx_num_kernels(void);
+/* every id rmx_profile_get takes: the ids of rmx_num_kernels() first, under the names of rmx_kernel_name(), then the kernels added
+ * after those two lists were closed (k_region_conditional).  "" outside [0, rmx_num_profile_ids()). */
+const char *rmx_profile_name(int32_t profile_id);
+int rmx_num_profile_ids(void);
 
 #ifdef __cplusplus
 }

@@ -111,6 +111,10 @@ SYMBOLS = {
     "rmx_profile_reset": (C.c_int, [C.c_void_p]),
     "rmx_kernel_name": (C.c_char_p, [C.c_int32]),
     "rmx_num_kernels": (C.c_int, []),
+    "rmx_profile_name": (C.c_char_p, [C.c_int32]),
+    "rmx_num_profile_ids": (C.c_int, []),
+    "rmx_region_conditional": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
+                                         C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_int16), C.POINTER(C.c_uint8), C.c_int32, _dp, C.POINTER(C.c_int16), _dp, _dp]),
 }
 
 _lib = None

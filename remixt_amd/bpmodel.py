@@ -759,6 +759,52 @@ class RemixtBatch(object):
         self._ck(self._lib.rmx_region_extent(self._handle, r0, nr, *args, wl, wr, obuf.ctypes.data_as(_dp)))
         return out
 
+    def region_conditional_raw(self, r0, nr, queries, windows, masks, labels, constrain, weights, states=None):
+        """Conditional marginals of the segments of a window given that an event of region_logprob_raw holds over an evidence run
+        inside it, under the structured posterior of the last update_p_cn of restarts r0 .. r0+nr-1 (rmx_region_conditional):
+        (logp (nr, nq), out (nr, nq, nslot, Q + 3)).  queries int (nq, 4): the evidence run's first and last segment, mask
+        index or -1, label index or -1; windows int (nq, 2): first and last segment that come back, around the run and in its
+        chain; masks, labels and constrain as region_logprob_raw; weights (C, S, Q) or (S, Q), Q in 1 .. 64, as
+        posterior_summary_raw; states int (nr, N) or (N,) with nr = 1, or None.  logp is log P(event).  Slot k of a query
+        stands for model segment windows[i, 0] + k (nslot: the longest window) and holds the conditional marginal's projection
+        on the Q weight columns, its maximum, the first index of the maximum and its entry at states[r, n] (0 without states);
+        slots past the window are NaN, as is every slot of an impossible event (logp -inf).  A window holds at most 16 384
+        segments, an evidence run at most 4 096."""
+        r0, nr = int(r0), int(nr)
+        N, S, C_ = self.num_segments, self.num_cn_states, self.cn_classes.shape[0]
+        rows = max(nr, 0)
+        q, args, _keep = self._region_args(queries, masks, labels, constrain)
+        wn = np.asarray(windows)
+        if wn.shape != (q.shape[0], 2):
+            raise ValueError('windows must have shape (nq, 2)')
+        if wn.size and (wn.min() < -2 ** 31 or wn.max() >= 2 ** 31):
+            raise ValueError('window entry out of range')
+        wn = np.ascontiguousarray(wn, dtype=np.int32)
+        nslot = int(np.clip((wn[:, 1].astype(np.int64) - wn[:, 0] + 1).max(), 1, 16384)) if wn.shape[0] else 1
+        w = np.asarray(weights, dtype=np.float64)
+        if w.ndim == 2:
+            w = np.broadcast_to(w[None], (C_,) + w.shape)
+        if w.ndim != 3 or w.shape[:2] != (C_, S):
+            raise ValueError('weights must have shape (num_classes, num_cn_states, Q) or (num_cn_states, Q)')
+        w = np.ascontiguousarray(w)
+        Q = w.shape[2]
+        i16p, i32p = C.POINTER(C.c_int16), C.POINTER(C.c_int32)
+        sp = i16p()
+        if states is not None:
+            st = np.asarray(states)
+            if st.shape != (rows, N) and not (rows == 1 and st.shape == (N,)):
+                raise ValueError('states must have shape (nr, num_segments)')
+            if st.size and (st.min() < -32768 or st.max() > 32767):
+                raise ValueError('state index out of range')
+            st = np.ascontiguousarray(st, dtype=np.int16)
+            sp = st.ctypes.data_as(i16p)
+        logp = np.zeros((rows, q.shape[0]), dtype=np.float64)
+        out = np.zeros((rows, q.shape[0], nslot, (Q + 3) if 1 <= Q <= 64 else 1), dtype=np.float64)
+        bufs = [x if x.size else np.zeros(4, dtype=x.dtype) for x in (wn, w, logp, out)]
+        self._ck(self._lib.rmx_region_conditional(self._handle, r0, nr, args[0], args[1], bufs[0].ctypes.data_as(i32p), nslot, *args[2:], Q,
+                                                  bufs[1].ctypes.data_as(_dp), sp, bufs[2].ctypes.data_as(_dp), bufs[3].ctypes.data_as(_dp)))
+        return logp, out
+
     def region_span_raw(self, r0, nr, queries, masks=None, labels=None, constrain=None, wl=0, wr=0):
         """log-probabilities (nr, nq, wl + 1, wr + 1) of an event of region_logprob_raw over every interval around an anchor,
         under the structured posterior of the last update_p_cn of restarts r0 .. r0+nr-1 (rmx_region_span): the joint law of
@@ -838,11 +884,11 @@ class RemixtBatch(object):
     def profile(self):
         """{kernel name: (total_ms, launches)} since the last reset."""
         out = {}
-        for i in range(self._lib.rmx_num_kernels()):
+        for i in range(self._lib.rmx_num_profile_ids()):
             ms = C.c_double(0.); n = C.c_int64(0)
             self._ck(self._lib.rmx_profile_get(self._handle, i, C.byref(ms), C.byref(n)))
             if n.value:
-                out[self._lib.rmx_kernel_name(i).decode()] = (float(ms.value), int(n.value))
+                out[self._lib.rmx_profile_name(i).decode()] = (float(ms.value), int(n.value))
         return out
 
 
@@ -1062,6 +1108,11 @@ class RemixtModel(object):
     def region_extent(self, queries, masks=None, labels=None, constrain=None, wl=0, wr=0):
         """RemixtBatch.region_extent_raw of this model: log-probabilities (nq, wl + wr + 1)."""
         return self._batch.region_extent_raw(self._r, 1, queries, masks, labels, constrain, wl, wr)[0]
+
+    def region_conditional(self, queries, windows, masks, labels, constrain, weights, states=None):
+        """RemixtBatch.region_conditional_raw of this model: (logp (nq,), out (nq, nslot, Q + 3))."""
+        logp, out = self._batch.region_conditional_raw(self._r, 1, queries, windows, masks, labels, constrain, weights, states)
+        return logp[0], out[0]
 
     def region_span(self, queries, masks=None, labels=None, constrain=None, wl=0, wr=0):
         """RemixtBatch.region_span_raw of this model: log-probabilities (nq, wl + 1, wr + 1)."""

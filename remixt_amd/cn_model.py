@@ -817,6 +817,24 @@ class BreakpointModel(object):
         return posteriors.batch_event_extents(self.model._batch, self.model._r, 1, anchors, event, window, self.seg_fwd_remap,
                                               self.seg_is_original, self.is_telomere)[0]
 
+    def conditional_summary(self, regions, event, window='chain', cn=None, marginals=False):
+        """"Suppose it is so: what follows?"  Exact per-segment posterior summaries given that a copy-number event holds over a
+        region, under the structured posterior of the last variational update: regions is a list of (first, last) experiment
+        segment indices, each an evidence of its own; event a mask name of posteriors.MASK_NAMES ('hdel': every segment of the
+        region is homozygously deleted), a label name of posteriors.LABEL_NAMES, a (mask, label) pair, or a boolean
+        (classes, states) table of the states the evidence allows; window 'chain' (the whole chain of the region) or the number
+        of model segments on either side.  One dict per region: `log_evidence`, the log-probability of the event, and the
+        arrays of posterior_summary without the entropy, in experiment segment order, NaN outside the window.  cn: a decoded
+        path ([N][M][2], model segment order), which supplies cn_posterior_prob given the event.
+        posteriors.evidence_shift compares a dict with posterior_summary()."""
+        from . import posteriors
+        if not hasattr(self.model, 'region_conditional'):
+            raise NotImplementedError('kernel module %s has no conditional summaries' % getattr(self._kernel_module(), '__name__', '?'))
+        b = self.model._batch
+        states = None if cn is None else posteriors.cn_to_states(cn, b.cn_classes, b.seg_class)[None]
+        return posteriors.batch_conditional_summary(b, self.model._r, 1, regions, event, window, self.seg_fwd_remap, self.seg_is_original,
+                                                    self.is_telomere, marginals=marginals, states=states)[0]
+
     def event_span(self, anchors, event, window=64):
         """The joint law of where a copy-number event begins and ends around anchor segments, and so of its length, exactly,
         under the structured posterior of the last variational update; anchors, event and window as event_extent (the

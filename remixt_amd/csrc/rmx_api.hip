@@ -56,6 +56,11 @@ static const char *kKernelNames[KID_COUNT] = {
 // last of the list above): rmx_num_kernels and rmx_kernel_name run over both, and a batch's profile keeps KID_ALL slots.
 enum PairKernelId { KID_RESTART_OVERLAP = KID_COUNT, KID_ALL };
 static const char *kPairKernelNames[KID_ALL - KID_COUNT] = {"k_restart_overlap"};
+// Both lists above are closed (tests/test_restart_overlap_cpu.py pins k_restart_overlap as the last name rmx_num_kernels reaches, and
+// an empty name at rmx_num_kernels()): later kernels take ids in a third range, which rmx_num_profile_ids and rmx_profile_name
+// run over together with the first two.  A batch's profile keeps KID_PROFILE_ALL slots.
+enum LaterKernelId { KID_REGION_CONDITIONAL = KID_ALL, KID_PROFILE_ALL };
+static const char *kLaterKernelNames[KID_PROFILE_ALL - KID_ALL] = {"k_region_conditional"};
 
 struct ProfRec { int id; hipEvent_t a, b; };
 
@@ -161,6 +166,7 @@ struct rmx_batch {
     std::vector<int64_t> last_path; int vit_cap = 0; size_t bp_cap = 0;
     int16_t *d_samp = nullptr; size_t samp_cap = 0; uint64_t *d_seeds = nullptr; uint32_t *d_sflags = nullptr;   // rmx_sample_cn: paths of a chunk of samples, seeds, flags [R]
     double *d_psum = nullptr; size_t psum_cap = 0; double *d_psw = nullptr; size_t psw_cap = 0;   // rmx_posterior_summary: output staging of a chunk (doubles), weights [C][S][Q]
+    double *d_rgcw = nullptr; size_t rgcw_cap = 0;   // rmx_region_conditional: the U rows of a chunk (doubles), at most 256 MiB
     double *d_rgn = nullptr; size_t rgn_cap = 0; uint8_t *d_rgt = nullptr; size_t rgt_cap = 0; uint32_t *d_rflags = nullptr; int16_t *d_rgbp = nullptr; size_t rgbp_cap = 0;   // (d_rgbp: the back-pointer strips of a chunk of rmx_region_decode)  rmx_region_prob: outputs + queries of a chunk (doubles), label / mask / constrain tables (bytes), flags [R]
     double *d_ovr = nullptr; size_t ovr_cap = 0; uint32_t *d_ovf = nullptr; size_t ovf_cap = 0; hipEvent_t ev_ov = nullptr;   // rmx_restart_overlap: sqrt(Wb) [TC][S][S] (built per call), flags [R + R of the other batch], the other batch's stream has reached the call
     uint16_t *d_comp = nullptr; int32_t *d_ends = nullptr; size_t comp_cap = 0, ends_cap = 0; int last_traceback = 0;      // parallel trace-back: composed maps [nr][NBLK][S], block end states [nr][NBLK]
@@ -197,8 +203,8 @@ struct rmx_batch {
     int prof = 0;     // 0 off, 1 all kernels, 2 variational-sweep kernels only
     std::vector<ProfRec> prof_pending;
     std::vector<hipEvent_t> ev_pool;
-    double prof_ms[KID_ALL] = {0};
-    long long prof_n[KID_ALL] = {0};
+    double prof_ms[KID_PROFILE_ALL] = {0};
+    long long prof_n[KID_PROFILE_ALL] = {0};
     hipEvent_t tm_a = nullptr, tm_b = nullptr;
     std::vector<hipEvent_t> done_ev;   // [R] completion marker of a restart's last queued read-back
     std::mutex mu;                     // guards the profiling lists and launch sequences of concurrent callers
@@ -848,13 +854,14 @@ static int tiles_per_wave(int S) {
 // blocks of 65535 restarts; within a block, one launch per run of restarts of one transition model:
 //   launch(Dev of the run, its first restart, its length, its offset in the call, use_wb, device queries, their number, the run's outputs, flags)
 // under profile id `kid`.  Rows [nrr][nqc * per] come back to logp_out [nr][nq][per]; a raised flag fails the call with flag_msg.
+// max_pairs: the most (restart, query) pairs of a chunk, for an entry point whose kernel keeps a workspace per pair.
 template <typename L> static int run_queries(rmx_batch *b, int r0, int nr, int nq, const int32_t *queries, int per, int kid, const char *flag_msg,
-                                             double *logp_out, L launch) {
+                                             double *logp_out, L launch, size_t max_pairs = SIZE_MAX) {
     int rc;
     if (!b->d_rflags && (rc = dalloc(b, &b->d_rflags, b->R))) return rc;
     const size_t budget = (size_t)64 << 20;
-    const int nrc = std::min(nr, 65535);
-    const size_t qc = std::max<size_t>(1, std::min<size_t>((size_t)nq, budget / ((size_t)nrc * per * 8 + 16)));
+    const int nrc = (int)std::min<size_t>((size_t)std::min(nr, 65535), std::max<size_t>(1, max_pairs));
+    const size_t qc = std::max<size_t>(1, std::min<size_t>({(size_t)nq, budget / ((size_t)nrc * per * 8 + 16), max_pairs / (size_t)nrc}));
     if ((rc = grow(b, &b->d_rgn, &b->rgn_cap, (size_t)nrc * qc * per + 2 * qc))) return rc;
     double *dout = b->d_rgn;
     int32_t *dq = (int32_t *)(b->d_rgn + (size_t)nrc * qc * per);
@@ -3553,6 +3560,89 @@ int rmx_region_extent(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const in
     });
 }
 
+// Region conditionals (k_region_conditional): for every (restart, query) the marginal of every segment of a window
+// given rmx_region_prob's event over an evidence run inside it, as projections on caller weights and row statistics, and the
+// event's log-probability.  Everything the kernel trusts is checked here before anything is queued (rmxh::check_conditional: the
+// runs, the windows, the table indices; the weight count; the state indices), and no output is written on an error.  The
+// run, table indices and window of every query are staged whole behind the tables as [nq][6] int32, and the queries handed to
+// run_queries name their row of it, so a chunk needs nothing else.  A (restart, query) output is 1 + nslot (Q + 3) doubles and
+// goes through run_queries' 64 MiB staging buffer; its U rows take run_max * S doubles of b->d_rgcw (run_max: the longest
+// evidence run of the call), a buffer that only grows.  A chunk holds at most rmxh::conditional_pairs (restart, query)
+// pairs: as many as keep the outputs within 64 MiB and the U rows within 256 MiB, and never less than one (the largest single
+// output is 8.4 MiB, the largest strip 32 MiB).  One workgroup computes a (restart, query) on its own in its own strip, and
+// both walks are prefix recursions from the run, so a slot depends on neither the restart range, the chunking, the other
+// queries nor the window.
+int rmx_region_conditional(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, const int32_t *windows, int32_t nslot,
+                           int32_t nmask, const uint8_t *masks, int32_t nlabel, const int16_t *labels, const uint8_t *constrain, int32_t Q,
+                           const double *weights, const int16_t *states, double *logp_out, double *out) { BIND(b);
+    int rc;
+    if ((rc = check_region_call(b, "region_conditional", r0, nr, nq, queries, out))) return rc;
+    if (!windows || !logp_out) return fail(RMX_EARG, "region_conditional: no windows or no output");
+    if ((rc = check_mask_label_tables("region_conditional", nmask, masks, nlabel, labels))) return rc;
+    if (!rmxh::conditional_q_ok(Q) || !weights) return fail(RMX_EARG, "region_conditional: Q must be 1 .. 64, with weights");
+    const int N = b->d.N, S = b->d.S;
+    if (S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "region_conditional: more than 1024 states");
+    int32_t run_max = 1;
+    {
+        // chain of a segment = the number of chain ends (tclass < 0) before it
+        std::vector<int32_t> chain(N);
+        int32_t c = 0;
+        for (int n = 0; n < N; n++) { chain[n] = c; if (b->tclass[n] < 0) c++; }
+        const char *why = nullptr;
+        const int64_t bad = rmxh::check_conditional(nq, queries, windows, nslot, N, chain.data(), nmask, nlabel, &why);
+        if (bad >= 0) return fail(RMX_EARG, std::string("region_conditional: ") + why + " (query " + std::to_string(bad) + ")");
+        for (int i = 0; i < nq; i++) run_max = std::max(run_max, queries[4 * (size_t)i + 1] - queries[4 * (size_t)i] + 1);
+    }
+    if (states) {       // before anything is queued: the kernel gathers cond[states[n]] unchecked
+        const size_t cnt = (size_t)nr * N;
+        for (size_t i = 0; i < cnt; i++) if (states[i] < 0 || states[i] >= S) return fail(RMX_EARG, "region_conditional: state index out of range");
+    }
+    if ((rc = require_snapshot(b, r0, nr, "region_conditional"))) return rc;
+    const int SL = Q + 3;
+    const size_t per = (size_t)nslot * SL + 1, strip = (size_t)run_max * S;
+    const size_t max_pairs = rmxh::conditional_pairs(per, strip);
+    // tables, then [nq][6] specs, then the states [nr][N]
+    std::vector<int32_t> spec((size_t)nq * 6), qidx((size_t)nq * 4, 0);
+    for (int i = 0; i < nq; i++) {
+        std::copy(queries + 4 * (size_t)i, queries + 4 * (size_t)i + 4, spec.begin() + 6 * (size_t)i);
+        spec[6 * (size_t)i + 4] = windows[2 * (size_t)i]; spec[6 * (size_t)i + 5] = windows[2 * (size_t)i + 1];
+        qidx[4 * (size_t)i] = i;
+    }
+    RgnArgs ra;
+    uint8_t *dextra = nullptr;
+    const size_t spec_bytes = ((size_t)nq * 24 + 15) / 16 * 16, st_bytes = states ? (size_t)nr * N * 2 : 0;
+    if ((rc = stage_region_tables(b, nmask, masks, nlabel, labels, constrain, &ra, spec_bytes + st_bytes, &dextra))) return rc;
+    const size_t wn = (size_t)b->d.C * S * Q;
+    if ((rc = grow(b, &b->d_psw, &b->psw_cap, wn))) return rc;
+    {
+        const size_t pairs = std::min<size_t>(max_pairs, (size_t)nr * nq);
+        if ((rc = grow(b, &b->d_rgcw, &b->rgcw_cap, pairs * strip))) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(dextra, spec.data(), (size_t)nq * 24, hipMemcpyHostToDevice, b->stream));
+    if (states) HIPCHK(hipMemcpyAsync(dextra + spec_bytes, states, st_bytes, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemcpyAsync(b->d_psw, weights, wn * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    RgcArgs ca;
+    ca.spec = (const int32_t *)dextra; ca.W = b->d_psw; ca.Q = Q; ca.nslot = nslot; ca.run_max = run_max;
+    ca.QP = 1; while (ca.QP < Q) ca.QP <<= 1;
+    const int16_t *dstates = states ? (const int16_t *)(dextra + spec_bytes) : nullptr;
+    // [nr][nq][1 + nslot * SL] comes back in one piece; logp_out and out are filled only once the call has run (or failed on the device)
+    std::vector<double> host((size_t)nr * nq * per);
+    rc = run_queries(b, r0, nr, nq, qidx.data(), (int)per, KID_REGION_CONDITIONAL, "region_conditional: a step has a zero or non-finite normaliser", host.data(),
+                     [&](const Dev &dv, int r, int n, int i, int use_wb, const int32_t *dq, int nqc, double *o, uint32_t *flags) {
+        ra.queries = dq; ra.nq = nqc;
+        const size_t at = (size_t)(o - b->d_rgn) / per;      // the run's first (restart, query) of the chunk
+        ca.states = dstates ? dstates + (size_t)i * N : nullptr;
+        ca.ws = b->d_rgcw + at * strip;
+        hipLaunchKernelGGL(k_region_conditional, dim3((unsigned)nqc, n), dim3(RGN_NT), 0, b->stream, dv, r, use_wb, ra, ca, o, flags);
+    }, max_pairs);
+    if (rc != RMX_OK && rc != RMX_EASSERT) return rc;
+    for (size_t k = 0; k < (size_t)nr * nq; k++) {
+        logp_out[k] = host[k * per];
+        std::copy(host.begin() + k * per + 1, host.begin() + (k + 1) * per, out + k * (per - 1));
+    }
+    return rc;
+}
+
 // Region event spans (k_region_span): for every (restart, query) the table of rmx_region_prob's event over every interval
 // [n0 - a, n0 + c] around an anchor, (wl + 1) (wr + 1) entries from one walk per group of 16 right ends.  The checks are
 // rmx_region_extent's with the window rule of a table; tables, staging and chunking are rmx_region_prob's.  One workgroup computes
@@ -3706,14 +3796,17 @@ int rmx_timer_stop(rmx_batch *b, double *ms) { BIND(b);
 }
 int rmx_profile_enable(rmx_batch *b, int32_t on) { BIND(b); prof_collect(b); b->prof = on < 0 ? 0 : (on > 2 ? 1 : on); return RMX_OK; }
 int rmx_profile_get(rmx_batch *b, int32_t id, double *ms, int64_t *n) { BIND(b);
-    if (id < 0 || id >= KID_ALL) return fail(RMX_EARG, "bad kernel id");
+    if (id < 0 || id >= KID_PROFILE_ALL) return fail(RMX_EARG, "bad kernel id");
     HIPCHK(hipStreamSynchronize(b->stream));
     prof_collect(b);
     *ms = b->prof_ms[id]; *n = b->prof_n[id];
     return RMX_OK;
 }
-int rmx_profile_reset(rmx_batch *b) { BIND(b); prof_collect(b); for (int i = 0; i < KID_ALL; i++) { b->prof_ms[i] = 0; b->prof_n[i] = 0; } return RMX_OK; }
+int rmx_profile_reset(rmx_batch *b) { BIND(b); prof_collect(b); for (int i = 0; i < KID_PROFILE_ALL; i++) { b->prof_ms[i] = 0; b->prof_n[i] = 0; } return RMX_OK; }
 const char *rmx_kernel_name(int32_t id) { return (id >= 0 && id < KID_COUNT) ? kKernelNames[id] : ((id >= KID_COUNT && id < KID_ALL) ? kPairKernelNames[id - KID_COUNT] : ""); }
 int rmx_num_kernels(void) { return KID_ALL; }
+// every profile id: those of rmx_num_kernels / rmx_kernel_name, then the third range
+const char *rmx_profile_name(int32_t id) { return (id >= KID_ALL && id < KID_PROFILE_ALL) ? kLaterKernelNames[id - KID_ALL] : rmx_kernel_name(id); }
+int rmx_num_profile_ids(void) { return KID_PROFILE_ALL; }
 
 }  // extern "C"

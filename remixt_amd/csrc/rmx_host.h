@@ -4,6 +4,7 @@
 //   lt_classes           the total-copy classes of the state tables (compact read-depth planes of the cell cache)
 //   span_window_ok, span_spread_nan  rmx_region_span: the window rule of a table, and NaN in every entry of a failed query
 //   check_patterns       rmx_region_pattern: the rules of the piece lists of its queries
+//   check_conditional, conditional_q_ok, conditional_pairs  rmx_region_conditional: the run and window rules, and the chunks of a call
 //   decode_max_len_ok, check_decode_lengths, decode_plan  rmx_region_decode: the length rules and the chunks of a call
 //   extremes_ncol_ok, check_levels  rmx_region_extremes: the column rule, and that no level entry is negative
 //   check_pairs, check_permutations  rmx_restart_overlap: the restart pairs lie inside the two batches, every permutation row is a bijection
@@ -82,6 +83,46 @@ inline int64_t check_patterns(int32_t nq, const int32_t *queries, int32_t npiece
     }
     if (reason) *reason = why;
     return bad;
+}
+
+// rmx_region_conditional.  Its queries [nq][4] = (a, b, mask index or -1, label index or -1) are evidence runs, its windows
+// [nq][2] = (lo, hi) the segments whose conditional marginals come back, nslot slots per query.  The rules: 1 <= nslot <=
+// COND_MAX_SLOTS; 0 <= lo <= a <= b <= hi < N, lo and hi in one chain (chain[n]: the chain of segment n, [N]; a and b lie between
+// them); hi - lo + 1 <= nslot; b - a + 1 <= COND_MAX_RUN; table indices in [-1, nmask) / [-1, nlabel).  Returns the index of the
+// first query that breaks a rule, with *reason (a string literal), or -1.
+constexpr int32_t COND_MAX_SLOTS = 16384;
+constexpr int32_t COND_MAX_RUN = 4096;
+constexpr int32_t COND_MAX_Q = 64;
+constexpr size_t COND_OUT_BUDGET = (size_t)64 << 20;       // outputs and queries of a chunk, bytes
+constexpr size_t COND_WS_BUDGET = (size_t)256 << 20;       // U rows of a chunk, bytes
+inline bool conditional_q_ok(int32_t Q) { return Q >= 1 && Q <= COND_MAX_Q; }
+inline int64_t check_conditional(int32_t nq, const int32_t *queries, const int32_t *windows, int32_t nslot, int32_t N, const int32_t *chain,
+                                 int32_t nmask, int32_t nlabel, const char **reason) {
+    const char *why = nullptr;
+    int64_t bad = -1;
+    if (nq < 0 || N < 0 || (nq > 0 && (!queries || !windows)) || (N > 0 && !chain)) { why = "bad arguments"; bad = 0; }
+    else if (nslot < 1 || nslot > COND_MAX_SLOTS) { why = "nslot must be in [1, 16384]"; bad = 0; }
+    for (int32_t i = 0; i < nq && !why; i++) {
+        const int32_t *qq = queries + 4 * (size_t)i;
+        const int64_t a = qq[0], b = qq[1], lo = windows[2 * (size_t)i], hi = windows[2 * (size_t)i + 1];
+        if (a < 0 || b >= N || a > b) why = "a query needs 0 <= first <= last < num_segments";
+        else if (lo < 0 || hi >= N || lo > a || hi < b) why = "a window needs 0 <= lo <= first and last <= hi < num_segments";
+        else if (chain[lo] != chain[hi]) why = "a window crosses a chain end";
+        else if (hi - lo + 1 > (int64_t)nslot) why = "a window is longer than nslot";
+        else if (b - a + 1 > (int64_t)COND_MAX_RUN) why = "an evidence run is longer than 4096 segments";
+        else if (qq[2] < -1 || qq[2] >= nmask) why = "mask index out of range";
+        else if (qq[3] < -1 || qq[3] >= nlabel) why = "label index out of range";
+        if (why) bad = i;
+    }
+    if (reason) *reason = why;
+    return bad;
+}
+// the most (restart, query) pairs of a chunk: a pair has `per` doubles of output (and 16 bytes of staged query) and `strip`
+// doubles of U rows; the outputs stay within COND_OUT_BUDGET and the strips within COND_WS_BUDGET, and a chunk never holds less
+// than one pair
+inline size_t conditional_pairs(size_t per, size_t strip) {
+    const size_t by_out = COND_OUT_BUDGET / (per * 8 + 16), by_ws = COND_WS_BUDGET / (std::max<size_t>(strip, 1) * 8);
+    return std::max<size_t>(1, std::min(by_out, by_ws));
 }
 
 // rmx_region_decode.  Its max_len rule: 1 <= max_len <= DECODE_MAX_LEN

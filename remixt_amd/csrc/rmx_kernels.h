@@ -7421,6 +7421,371 @@ __global__ __launch_bounds__(RGN_NT) void k_region_decode(Dev d, int r0, int use
 }
 
 // =============================================================================
+// Region conditionals: the marginal of every segment of a window [lo, hi] given k_region_prob's event E over an evidence run
+// [a, b] inside it (lo <= a <= b <= hi, one chain), and log P(E).  Under the backward kernel c_n separates the two sides, so
+//   q(c_n = s | E) = U_n(s) g_n(s) / P(E),
+//   g_n(s) = q(c_n = s, E on [n, b]): k_region_prob's backward recursion from b, continued unconstrained below a;
+//   U_n(s) = P(E on [a, n] | c_n = s): k_region_extent's forward recursion from a, continued unconstrained above b,
+// with U = 1 left of a and g_n = post_n right of b.  Two walks per (restart, query):
+//   right, a -> hi: U as k_region_extent computes it (one pass over the S x S weights per step, scaled by its maximum over the
+//     states with mass in post or fa); mask and label bind up to b.  The rows of [a, b] go to the query's strip of a device
+//     workspace, S doubles per segment; a segment n > b emits its slot from post_n(s) U_n(s).
+//   left, b -> lo: g as k_region_prob computes it (D pass, then g pass); mask and label bind down to a.  A segment of [a, b]
+//     emits its slot from U_n(s) g_n(s), U read back from the strip by the thread that wrote it; a segment n < a from g_n(s).
+//     log P(E) is the sum of the logarithms of the step sums down to a.
+// An emitted row is divided by its own sum, so no scale of either walk is kept.  A slot is Q + 3 doubles: the projection
+// sum_s cond(s) W[seg_class[n]][s][q], the row maximum, the first index of the maximum, and the entry at states[n] (0 without
+// states).  The projection has lane = (s mod (64 / QP)) * QP + q, QP = Q rounded up to a power of two: a wave reads 64 / QP
+// consecutive rows of W at once, each row's Q weights contiguous; the partial sums meet by a butterfly over the lanes of one q,
+// then over the four waves through [4][64] doubles of LDS that lane j of wave w writes at word w * 64 + j (no two lanes of a
+// wave on one bank).  The conditional row is read from LDS as a broadcast per s.
+// Lane mappings, compaction and the order of every sum are those of the two kernels; every order is fixed by S and Q alone, and
+// both walks are prefix recursions from the run: a slot does not depend on the launch, the other queries or the window.
+// Only columns s < S of fa / post are read; selects, never a multiply by 0.  A bad normaliser sets RGN_ERR_DENOM in flags[r] and
+// gives NaN everywhere; an impossible event gives log P(E) = -inf and NaN in every slot; slots past hi are NaN.
+// grid (queries, restarts), block RGN_NT; out[(ri * nq + query) * (nslot * (Q + 3) + 1)]: log P(E), then the slots of lo, lo + 1, ...
+// LDS: four rows of RGN_MAXS doubles (g, h, fa, the conditional row), labels and the compacted index, 38 KiB + 2 KiB of
+// reduction space: four workgroups per CU by LDS.
+// =============================================================================
+#define RGC_MAXQ 64           // weight columns of a call
+#define RGC_MAXSLOT 16384     // slots of a query's window
+#define RGC_MAXRUN 4096       // segments of a query's evidence run
+struct RgcArgs {
+    const int32_t *spec;      // [queries of the call][6]: a, b, mask index or -1, label index or -1, lo, hi; field 0 of a staged query indexes it
+    const double *W;          // [C][S][Q]
+    const int16_t *states;    // [restarts of the launch][N], or null
+    double *ws;               // U rows of the launch: [restarts][queries][run_max][S]
+    int Q, QP, nslot, run_max;
+};
+// maximum over the workgroup; every thread gets it
+__device__ inline double rgc_block_max(double m, double *red) {
+    m = group_max(m, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    double t = red[0];
+#pragma unroll
+    for (int i = 1; i < RGN_NW; i++) t = fmax(t, red[i]);
+    return t;
+}
+// one slot from the row cr[0 .. S) (LDS, every entry written by the thread that owns s = tid + k RGN_NT; not normalised): the
+// row is divided by its sum in place, then statistics and projection go to oslot.  0: written; 1: the sum is 0; 2: the sum is
+// not a finite number >= 0.  red: [3 RGN_NW], redq: [RGN_NW][64]; ends with a barrier, so cr may be written again at once
+__device__ __forceinline__ int rgc_emit(const Dev &d, const RgcArgs &c, int n, int st, double *cr, double *red, double (*redq)[64], double *oslot) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, S = d.S, Q = c.Q, QP = c.QP;
+    double part = 0.;
+    for (int s = tid; s < S; s += RGN_NT) part += cr[s];
+    const double Z = rgn_block_sum(part, red);
+    if (!(Z >= 0. && Z < INFINITY)) return 2;
+    if (Z == 0.) return 1;
+    double mx = -1.;
+    int am = 0x7fffffff;
+    for (int s = tid; s < S; s += RGN_NT) {
+        const double v = cr[s] / Z;
+        cr[s] = v;
+        if (v > mx) { mx = v; am = s; }
+    }
+    for (int off = 1; off < 64; off <<= 1) {
+        const double omx = __shfl_xor(mx, off, 64);
+        const int oam = __shfl_xor(am, off, 64);
+        if (omx > mx || (omx == mx && oam < am)) { mx = omx; am = oam; }
+    }
+    if (lane == 0) { red[RGN_NW + wv] = mx; red[2 * RGN_NW + wv] = (double)am; }
+    __syncthreads();
+    if (tid == 0) {
+        double m = red[RGN_NW], ai = red[2 * RGN_NW];
+#pragma unroll
+        for (int i = 1; i < RGN_NW; i++) {
+            const double om = red[RGN_NW + i], oa = red[2 * RGN_NW + i];
+            if (om > m || (om == m && oa < ai)) { m = om; ai = oa; }
+        }
+        oslot[Q] = m;
+        oslot[Q + 1] = ai;
+        oslot[Q + 2] = st >= 0 ? cr[st] : 0.;
+    }
+    // projection: QP lanes take the columns, 64 / QP groups of them and the four waves stride the states
+    const int nsub = 64 / QP, sub = lane / QP, qq = lane % QP;
+    const double *Wc = c.W + (size_t)d.seg_class[n] * S * Q;
+    double acc = 0.;
+    if (qq < Q) {
+        for (int s = wv * nsub + sub; s < S; s += RGN_NW * nsub) {
+            const double v = cr[s];
+            if (v != 0.) acc = fma(v, Wc[(size_t)s * Q + qq], acc);
+        }
+    }
+    for (int off = QP; off < 64; off <<= 1) acc += __shfl_xor(acc, off, 64);
+    if (lane < QP) redq[wv][lane] = acc;
+    __syncthreads();
+    if (tid < Q) {
+        double t = 0.;
+#pragma unroll
+        for (int i = 0; i < RGN_NW; i++) t += redq[i][tid];
+        oslot[tid] = t;
+    }
+    __syncthreads();
+    return 0;
+}
+__global__ __launch_bounds__(RGN_NT) void k_region_conditional(Dev d, int r0, int use_wb, RgnArgs q, RgcArgs c, double *out, uint32_t *flags) {
+    __shared__ double g[RGN_MAXS], h[RGN_MAXS], fas[RGN_MAXS], cr[RGN_MAXS];
+    __shared__ double red[3 * RGN_NW], redq[RGN_NW][64];
+    __shared__ int16_t lab[2][RGN_MAXS], idx[RGN_MAXS];
+    __shared__ int nact, s_bad;
+    const int qi = blockIdx.x, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x;
+    const int grp = tid / RGN_GL, gl = tid % RGN_GL;
+    const int S = d.S, Q = c.Q, SL = Q + 3;
+    const int32_t *spec = c.spec + 6 * (size_t)q.queries[4 * qi];
+    const int a = spec[0], b = spec[1], mi = spec[2], li = spec[3], lo = spec[4], hi = spec[5];
+    const size_t per = (size_t)c.nslot * SL + 1;
+    double *orow = out + ((size_t)ri * q.nq + qi) * per;
+    double *U = c.ws + ((size_t)ri * q.nq + qi) * c.run_max * S;      // rows a .. b of this (restart, query)
+    const int16_t *st = c.states ? c.states + (size_t)ri * d.N : nullptr;
+    if (tid == 0) s_bad = 0;
+    bool failed = false, dead = false;        // dead: the event cannot happen
+    // ---- right walk: steps n -> n + 1 for n = a .. hi - 1; g holds fa_n U_n during a step, h takes U_n+1 --------------------
+    {
+        int cur = 0;              // lab[cur]: the labels of segment n
+        {
+            const auto [mk, lb] = rgn_tabs(d, q, a, mi, li);
+            for (int s = tid; s < S; s += RGN_NT) {
+                const double u = (!mk || mk[s]) ? 1. : 0.;
+                g[s] = u;
+                U[s] = u;
+                if (lb) lab[cur][s] = lb[s];
+            }
+        }
+        for (int n = a; n < hi && !failed && !dead; n++) {
+            const bool in = n + 1 <= b;       // mask and label bind at n + 1 and across n -> n + 1
+            const auto [wb, Wt, pd] = rgn_adj(d, r, n, use_wb);
+            const double *fa = d.fa + rs_off(d, r, n);
+            const double *post1 = d.post + rs_off(d, r, n + 1);
+            const auto [mk1, lb1] = rgn_tabs(d, q, n + 1, in ? mi : -1, in ? li : -1);
+            const int16_t *lab0 = lab[cur];
+            int16_t *lab1 = lab[cur ^ 1];
+            __syncthreads();
+            for (int s = tid; s < S; s += RGN_NT) {
+                const double f = fa[s];
+                fas[s] = f;
+                g[s] = f != 0. ? f * g[s] : 0.;
+                if (lb1) lab1[s] = lb1[s];
+            }
+            __syncthreads();
+            if (wb) {
+                // num(s') and D(s') from one read of row s': 16 lanes per s'
+                for (int j0 = 0; j0 < S; j0 += RGN_NT / RGN_GL) {
+                    const int sp = j0 + grp;
+                    const bool ok = sp < S && (!mk1 || mk1[sp]);
+                    double pD = 0., pN = 0.;
+                    if (ok) {
+                        const double *wrow = Wt + (size_t)sp * S;
+                        const int ls = lb1 ? lab1[sp] : 0;
+                        for (int s = gl; s < S; s += RGN_GL) {
+                            const double w = wrow[s];
+                            pD = fma(fas[s], w, pD);
+                            if (!lb1 || lab0[s] == ls) pN = fma(g[s], w, pN);
+                        }
+                    }
+                    const double D = group_sum(pD, RGN_GL), num = group_sum(pN, RGN_GL);
+                    if (sp < S && gl == 0) {
+                        double u = 0.;
+                        if (ok && num != 0.) {
+                            u = num / D;
+                            if (!(D > 0. && D < INFINITY) || !(u >= 0. && u < INFINITY)) s_bad = 1;
+                        }
+                        h[sp] = u;
+                    }
+                }
+            } else {
+                // num(s') and D(s'): the thread owns s'
+                for (int sp = tid; sp < S; sp += RGN_NT) {
+                    double u = 0.;
+                    if (!mk1 || mk1[sp]) {
+                        const int ls = lb1 ? lab1[sp] : 0;
+                        double D = 0., num = 0.;
+                        for (int s = 0; s < S; s++) {
+                            const double f = fas[s];
+                            if (f != 0.) {
+                                const double w = exp(trans_value(d, n, s, sp, pd));
+                                D = fma(f, w, D);
+                                if (!lb1 || lab0[s] == ls) num = fma(g[s], w, num);
+                            }
+                        }
+                        if (num != 0.) {
+                            u = num / D;
+                            if (!(D > 0. && D < INFINITY) || !(u >= 0. && u < INFINITY)) s_bad = 1;
+                        }
+                    }
+                    h[sp] = u;
+                }
+            }
+            __syncthreads();
+            // the scale: the largest U among the states with mass in the marginal or in the forward row of n + 1 (the others go to 0)
+            const double *fa1 = d.fa + rs_off(d, r, n + 1);
+            double mx = 0.;
+            for (int s = tid; s < S; s += RGN_NT) {
+                const bool live = post1[s] != 0. || fa1[s] != 0.;
+                const double u = live ? h[s] : 0.;
+                h[s] = u;
+                mx = fmax(mx, u);
+            }
+            mx = rgc_block_max(mx, red);
+            if (s_bad || !(mx >= 0. && mx < INFINITY)) failed = true;
+            else if (mx == 0.) dead = true;
+            else if (in) {
+                double *urow = U + (size_t)(n + 1 - a) * S;
+                for (int s = tid; s < S; s += RGN_NT) {
+                    const double u = h[s] / mx;
+                    g[s] = u;
+                    urow[s] = u;
+                }
+            } else {
+                for (int s = tid; s < S; s += RGN_NT) {
+                    const double u = h[s] / mx, p = post1[s];
+                    g[s] = u;
+                    cr[s] = (p != 0. && u != 0.) ? p * u : 0.;
+                }
+                const int e = rgc_emit(d, c, n + 1, st ? st[n + 1] : -1, cr, red, redq, orow + 1 + (size_t)(n + 1 - lo) * SL);
+                if (e == 2) failed = true;
+                else if (e == 1) dead = true;
+            }
+            cur ^= 1;
+        }
+    }
+    // ---- left walk: k_region_prob's steps from b down to lo; segment n emits before the step to n - 1 ---------------------------
+    double logp = 0.;
+    if (!failed && !dead) {
+        int cur = 0;              // lab[cur]: the labels of segment n
+        __syncthreads();
+        {
+            const double *post = d.post + rs_off(d, r, b);
+            const auto [mk, lb] = rgn_tabs(d, q, b, mi, li);
+            double part = 0.;
+            for (int s = tid; s < S; s += RGN_NT) {
+                const double v = (!mk || mk[s]) ? post[s] : 0.;
+                g[s] = v; part += v;
+                if (lb) lab[cur][s] = lb[s];
+            }
+            const double Z = rgn_block_sum(part, red);
+            if (rgn_take_sum(Z, false, logp, failed))
+                for (int s = tid; s < S; s += RGN_NT) g[s] = g[s] / Z;
+        }
+        for (int n1 = b; !failed && !dead && logp > -INFINITY; n1--) {
+            // the slot of n1: U g inside the run, g below it
+            {
+                const double *urow = U + (size_t)(n1 >= a ? n1 - a : 0) * S;
+                for (int s = tid; s < S; s += RGN_NT) {
+                    const double gv = g[s];
+                    double v = gv;
+                    if (n1 >= a) {
+                        const double u = urow[s];
+                        v = (gv != 0. && u != 0.) ? gv * u : 0.;
+                    }
+                    cr[s] = v;
+                }
+                const int e = rgc_emit(d, c, n1, st ? st[n1] : -1, cr, red, redq, orow + 1 + (size_t)(n1 - lo) * SL);
+                if (e == 2) failed = true;
+                else if (e == 1) dead = true;
+            }
+            if (failed || dead || n1 == lo) break;
+            const int n = n1 - 1;
+            const bool in = n >= a;           // mask and label bind at n and across n -> n + 1
+            const auto [wb, Wt, pd] = rgn_adj(d, r, n, use_wb);
+            const double *fa = d.fa + rs_off(d, r, n);
+            const auto [mk, lb] = rgn_tabs(d, q, n, in ? mi : -1, in ? li : -1);
+            const int16_t *lab1 = lab[cur];
+            int16_t *lab0 = lab[cur ^ 1];
+            for (int s = tid; s < S; s += RGN_NT) {
+                fas[s] = fa[s];
+                if (lb) lab0[s] = lb[s];
+            }
+            __syncthreads();
+            if (wb) {
+                // the states s' with g(s') > 0, in state order
+                const int na = rgn_compact(S, idx, nact, [&](int s) { return g[s] > 0.; });
+                // D(s') and h(s') = g(s') / D(s'): 16 lanes per s'
+                for (int j0 = 0; j0 < na; j0 += RGN_NT / RGN_GL) {
+                    const int j = j0 + grp;
+                    const bool ok = j < na;
+                    const int sp = ok ? idx[j] : 0;
+                    double p = 0.;
+                    if (ok) {
+                        const double *wrow = Wt + (size_t)sp * S;
+                        for (int s = gl; s < S; s += RGN_GL) p = fma(fas[s], wrow[s], p);
+                    }
+                    const double D = group_sum(p, RGN_GL);
+                    if (ok && gl == 0) {
+                        if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                        h[j] = g[sp] / D;
+                    }
+                }
+                __syncthreads();
+                // g(s): the thread owns s
+                for (int s = tid; s < S; s += RGN_NT) {
+                    double acc = 0.;
+                    if (!mk || mk[s]) {
+                        const int ls = lb ? lab0[s] : 0;
+                        const double *wc = Wt + s;
+#pragma unroll 4
+                        for (int j = 0; j < na; j++) {
+                            const int sp = idx[j];
+                            if (!lb || lab1[sp] == ls) acc = fma(wc[(size_t)sp * S], h[j], acc);
+                        }
+                        acc *= fas[s];
+                    }
+                    g[s] = acc;
+                }
+            } else {
+                // D(s') and h(s'): the thread owns s'
+                for (int sp = tid; sp < S; sp += RGN_NT) {
+                    const double gv = g[sp];
+                    double hv = 0.;
+                    if (gv > 0.) {
+                        const double D = rgn_D_exp(d, n, sp, fas, pd);
+                        if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                        hv = gv / D;
+                    }
+                    h[sp] = hv;
+                }
+                __syncthreads();
+                // g(s): 16 lanes per s
+                for (int s0 = 0; s0 < S; s0 += RGN_NT / RGN_GL) {
+                    const int s = s0 + grp;
+                    const bool ok = s < S && (!mk || mk[s]) && fas[s] != 0.;
+                    double p = 0.;
+                    if (ok) {
+                        const int ls = lb ? lab0[s] : 0;
+                        for (int sp = gl; sp < S; sp += RGN_GL) {
+                            const double hv = h[sp];
+                            if (hv != 0. && (!lb || lab1[sp] == ls)) p = fma(exp(trans_value(d, n, s, sp, pd)), hv, p);
+                        }
+                    }
+                    const double sum = group_sum(p, RGN_GL);
+                    if (s < S && gl == 0) g[s] = ok ? sum * fas[s] : 0.;
+                }
+            }
+            __syncthreads();
+            double part = 0.;
+            for (int s = tid; s < S; s += RGN_NT) part += g[s];
+            const double Z = rgn_block_sum(part, red);
+            // (below a nothing binds: the step sum is 1 up to rounding and is no part of log P(E))
+            double below = 0.;
+            if (rgn_take_sum(Z, s_bad != 0, in ? logp : below, failed))
+                for (int s = tid; s < S; s += RGN_NT) g[s] = g[s] / Z;
+            if (!(below > -INFINITY)) dead = true;
+            cur ^= 1;
+        }
+    }
+    // ---- the slots past hi, or every slot of a query that failed or cannot happen: NaN ------------------------------------------
+    __syncthreads();
+    const bool none = failed || dead || !(logp > -INFINITY);
+    const size_t first = none ? 0 : (size_t)(hi - lo + 1) * SL;
+    for (size_t k = first + tid; k + 1 < per; k += RGN_NT) orow[1 + k] = __builtin_nan("");
+    if (tid == 0) {
+        if (failed) atomicOr(&flags[r], RGN_ERR_DENOM);
+        orow[0] = failed ? __builtin_nan("") : (none ? -INFINITY : logp);
+    }
+}
+
+// =============================================================================
 // Restart overlap: log Z of two restarts' structured posteriors over the model segments [a, b] of one chain,
 //   Z = sum_x q_A(x_a .. x_b)^lam q_B(pi x_a .. pi x_b)^mu,   (lam, mu) = (1/2, 1/2) (MODE 0: the Bhattacharyya overlap) or (1, 1)
 // (MODE 1: the probability that independent draws of the two coincide), pi a bijection of the states per state class.  Both

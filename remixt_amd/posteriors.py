@@ -1639,3 +1639,120 @@ def restart_overlap(batches, counts, model, regions=None, pairs=None, clone_maps
     own = np.stack([np.arange(R), np.arange(R)], axis=1)
     self_lc = batch_restart_overlap(batches, offsets, own, *args, tables[:1], 1)[:, :, 0]
     return overlap_summary(pairs, maps, raw['log_overlap'], raw['log_coincidence'], self_lc, int(np.count_nonzero(model.seg_is_original)))
+
+
+# ---- per-segment posteriors given that an event holds (rmx_region_conditional) ----------------------------
+# the arrays of unpack a conditional summary holds (the row entropy is not computed given an event)
+CONDITIONAL_ARRAYS = ('total_cn_mean', 'total_cn_sd', 'expected_alleles_subclonal', 'p_subclonal', 'p_loh', 'p_hdel', 'cn_posterior_max', 'cn_mpm')
+_CONDITIONAL_MAX_SLOTS = 16384
+_CONDITIONAL_MAX_Q = 64
+
+
+def conditional_event(event, cn_classes):
+    """The evidence of a conditional summary as tables and indices: (masks (C, nmask, S), labels (C, nlabel, S), mask index or
+    -1, label index or -1).  event: as parse_event takes it, over the tables of event_tables, or a boolean (C, S) table of the
+    states the evidence allows (one mask of its own, no label)."""
+    if not isinstance(event, (str, tuple, list)) and np.ndim(event) == 2:
+        table = np.asarray(event)
+        cn = np.asarray(cn_classes)
+        if table.shape != cn.shape[:2]:
+            raise ValueError('a mask table must have shape (num_classes, num_cn_states)')
+        return np.ascontiguousarray((table != 0)[:, None, :], dtype=np.uint8), None, 0, -1
+    mi, li = parse_event(event)
+    masks, labels = event_tables(cn_classes)
+    return masks, labels, mi, li
+
+
+def conditional_queries(regions, window, seg_fwd_remap, seg_is_original, chain_start, chain_end):
+    """Regions ((first, last) experiment segment indices) and a window as the runs and windows of rmx_region_conditional:
+    (runs int32 (P, 2), windows int32 (P, 2), piece_region (P,), constrain uint8 (N1,)).  The runs are region_queries': a
+    region that spans chains is one piece per chain.  window: 'chain' -- every piece's whole chain -- or the number of model
+    segments on either side of the piece, cut at its chain's ends."""
+    runs, piece_region, constrain = region_queries(regions, seg_fwd_remap, seg_is_original, chain_start, chain_end)
+    cs, ce = np.asarray(chain_start, dtype=np.int64), np.asarray(chain_end, dtype=np.int64)
+    chain = np.searchsorted(ce, runs[:, 0], side='left')
+    if isinstance(window, str):
+        if window != 'chain':
+            raise ValueError("a window is 'chain' or a number of segments, not %r" % (window,))
+        lo, hi = cs[chain], ce[chain]
+    else:
+        if np.ndim(window) != 0 or int(window) != window or int(window) < 0:
+            raise ValueError("a window is 'chain' or a number of segments >= 0, not %r" % (window,))
+        lo, hi = np.maximum(runs[:, 0] - int(window), cs[chain]), np.minimum(runs[:, 1] + int(window), ce[chain])
+    windows = np.stack([lo, hi], axis=1).astype(np.int32).reshape(-1, 2)
+    if len(windows) and (windows[:, 1] - windows[:, 0] + 1).max() > _CONDITIONAL_MAX_SLOTS:
+        raise ValueError('a window holds at most %d model segments' % _CONDITIONAL_MAX_SLOTS)
+    return runs, windows, piece_region, constrain
+
+
+def conditional_unpack(logp, out, windows, piece_region, num_regions, layout, cn_classes, seg_class, seg_fwd_remap, with_prob):
+    """One restart's rows of rmx_region_conditional (logp (P,), out (P, nslot, Q + 3)) as one dict per region: `log_evidence`,
+    the sum over the region's pieces -- chains are independent under the structured posterior, so every chain's window is
+    conditioned on its own piece --, and the arrays of unpack without the entropy, in experiment segment order (inserted
+    segments dropped), NaN outside the windows (cn_mpm: -1) and everywhere where the evidence cannot happen."""
+    N1, Q = len(seg_class), layout['Q']
+    fwd = np.asarray(seg_fwd_remap, dtype=np.int64)
+    log_ev = combine(np.asarray(logp, dtype=float), piece_region, num_regions)
+    res = []
+    for R in range(int(num_regions)):
+        proj = np.full((N1, Q), np.nan)
+        stats = np.full((N1, 3), np.nan)
+        amax = np.zeros(N1, dtype=np.int64)
+        for p in np.flatnonzero(np.asarray(piece_region) == R):
+            lo, hi = int(windows[p, 0]), int(windows[p, 1])
+            rows = np.asarray(out[p, :hi - lo + 1])
+            proj[lo:hi + 1] = rows[:, :Q]
+            stats[lo:hi + 1, 0], stats[lo:hi + 1, 2] = rows[:, Q], rows[:, Q + 2]
+            amax[lo:hi + 1] = np.where(np.isnan(rows[:, Q + 1]), 0, rows[:, Q + 1]).astype(np.int64)
+        s = unpack(proj, stats, amax, layout, cn_classes, seg_class)
+        del s['cn_posterior_entropy']
+        if not with_prob:
+            del s['cn_posterior_prob']
+        s['cn_mpm'] = np.where(np.isnan(stats[:, 0])[:, None, None], -1, s['cn_mpm'])
+        s = dict((k, v[fwd]) for k, v in s.items())
+        s['log_evidence'] = float(log_ev[R])
+        res.append(s)
+    return res
+
+
+def batch_conditional_summary(batch, r0, nr, regions, event, window, seg_fwd_remap, seg_is_original, is_telomere, marginals=False, states=None):
+    """Exact per-segment summaries given that an event holds over a region, for restarts r0 .. r0+nr-1 of a RemixtBatch from
+    one device call: a list over restarts of lists over regions of conditional_unpack dicts.  regions: (first, last)
+    experiment segment indices; event: conditional_event; window: conditional_queries; marginals: the one-hot columns of
+    feature_matrix too (cn_marginals), where they fit 64 weight columns; states: int16 (nr, N1) decoded states in model order
+    for cn_posterior_prob given the event, or None (the key is then left out)."""
+    weights, layout = feature_matrix(batch.cn_classes, marginals)
+    if layout['Q'] > _CONDITIONAL_MAX_Q:
+        raise ValueError('a conditional summary takes at most %d weight columns, %d asked for (marginals=%r)' % (_CONDITIONAL_MAX_Q, layout['Q'], marginals))
+    masks, labels, mi, li = conditional_event(event, batch.cn_classes)
+    cs, ce = chains_from_telomeres(is_telomere)
+    runs, windows, piece_region, constrain = conditional_queries(regions, window, seg_fwd_remap, seg_is_original, cs, ce)
+    R = len(np.asarray(regions).reshape(-1, 2))
+    if len(runs) == 0:
+        return [[] for _ in range(nr)]
+    q = np.zeros((len(runs), 4), dtype=np.int32)
+    q[:, :2], q[:, 2], q[:, 3] = runs, mi, li
+    logp, out = batch.region_conditional_raw(r0, nr, q, windows, masks, labels, constrain, weights, states)
+    return [conditional_unpack(logp[i], out[i], windows, piece_region, R, layout, batch.cn_classes, batch.seg_class, seg_fwd_remap, states is not None)
+            for i in range(nr)]
+
+
+def evidence_shift(conditional, unconditional, l=None):
+    """What the evidence changes: for one region's conditional summary (conditional_unpack) and the unconditional summary of
+    the same restart (unpack, experiment order), the differences conditional - unconditional of the floating-point arrays
+    both hold, NaN outside the window; `cn_mpm_changed`, whether the marginal arg-max moved (False outside the window);
+    `log_evidence`; and with segment lengths l (experiment order) `ploidy_before` and `ploidy_after`, summary_stats'
+    ploidy_posterior_mean over the segments of the window alone."""
+    out = {'log_evidence': conditional['log_evidence']}
+    for k, v in conditional.items():
+        if k in unconditional and np.asarray(v).dtype.kind == 'f' and np.ndim(v) >= 1:
+            out[k] = np.asarray(v) - np.asarray(unconditional[k])
+    inside = ~np.isnan(np.asarray(conditional['cn_posterior_max']))
+    if 'cn_mpm' in unconditional:
+        out['cn_mpm_changed'] = inside & np.any(np.asarray(conditional['cn_mpm']) != np.asarray(unconditional['cn_mpm']), axis=(1, 2))
+    if l is not None:
+        lw = np.asarray(l, dtype=float)[inside]
+        for name, s in (('ploidy_before', unconditional), ('ploidy_after', conditional)):
+            part = {'total_cn_mean': np.asarray(s['total_cn_mean'])[inside], 'expected_alleles_subclonal': np.asarray(s['expected_alleles_subclonal'])[inside]}
+            out[name] = summary_stats(part, lw)['ploidy_posterior_mean'] if inside.any() and lw.sum() > 0 else float('nan')
+    return out

@@ -729,6 +729,21 @@ class RestartSet(object):
         return posteriors.batch_event_extents(self.batch, 0, len(self.models), anchors, event, window, m.seg_fwd_remap, m.seg_is_original,
                                               m.is_telomere)
 
+    def conditional_summary(self, regions, event, window='chain', cn=None, marginals=False):
+        """BreakpointModel.conditional_summary of every restart from one device call: a list over restarts of lists over
+        regions.  cn: the restarts' decoded paths in experiment order (the `cn` of results()), or None."""
+        from . import posteriors
+        if self.batch is None or not hasattr(self.batch, 'region_conditional_raw'):
+            if cn is not None:
+                raise NotImplementedError('conditional summaries against a decoded path need the batched kernel module')
+            return [m.conditional_summary(regions, event, window, marginals=marginals) for m in self.models]
+        b, m = self.batch, self.models[0]
+        states = None
+        if cn is not None:
+            states = np.stack([posteriors.states_in_model_order(cn[r], b, mm.seg_fwd_remap) for r, mm in enumerate(self.models)])
+        return posteriors.batch_conditional_summary(b, 0, len(self.models), regions, event, window, m.seg_fwd_remap, m.seg_is_original, m.is_telomere,
+                                                    marginals=marginals, states=states)
+
     def event_span(self, anchors, event, window=64):
         """BreakpointModel.event_span of every restart from one device call: a list over restarts of lists of
         posteriors.span_summary dicts, one per anchor."""
@@ -1007,6 +1022,10 @@ class RestartGroups(object):
         """RestartSet.event_extent over the groups, restarts in order: a list over restarts of lists over anchors."""
         return _join(self._map(lambda rs: rs.event_extent(anchors, event, window)))
 
+    def conditional_summary(self, regions, event, window='chain', cn=None, marginals=False):
+        """RestartSet.conditional_summary over the groups, restarts in order (cn: of all restarts): a list over restarts of lists over regions."""
+        return _join(self._map(lambda rs: rs.conditional_summary(regions, event, window, self._own(rs, cn), marginals)))
+
     def event_span(self, anchors, event, window=64):
         """RestartSet.event_span over the groups, restarts in order: a list over restarts of lists over anchors."""
         return _join(self._map(lambda rs: rs.event_span(anchors, event, window)))
@@ -1151,6 +1170,10 @@ class DatasetGroups(object):
     def event_extent(self, anchors, event, window=64):
         """RestartGroups.event_extent of every dataset: a list, one list over restarts per dataset."""
         return self._map(lambda part: part.event_extent(anchors, event, window))
+
+    def conditional_summary(self, regions, event, window='chain', cn=None, marginals=False):
+        """RestartGroups.conditional_summary of every dataset: a list, one list over restarts per dataset (cn: per dataset)."""
+        return self._map(lambda part: part.conditional_summary(regions, event, window, self._own(part, cn), marginals))
 
     def event_span(self, anchors, event, window=64):
         """RestartGroups.event_span of every dataset: a list, one list over restarts per dataset."""

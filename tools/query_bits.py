@@ -1,7 +1,7 @@
 """The raw outputs of the posterior queries on seeded scenarios, for comparing two builds of the library to the last bit:
 sample_states, posterior_summary_raw, region_logprob_raw, region_counts_raw (1, 5 and 16 bins), call_logprob_raw,
-region_moments_raw (nf 1 and 4), region_extent_raw, region_pattern_raw, region_decode_raw (log-probabilities and states) and
-region_extremes_raw (1, 5 and 16 columns), each with
+region_moments_raw (nf 1 and 4), region_extent_raw, region_pattern_raw, region_decode_raw (log-probabilities and states),
+region_extremes_raw (1, 5 and 16 columns) and region_conditional_raw (log-probabilities and slots; chain windows), each with
 and without a constrain vector that leaves segments unbound (a library without an entry point leaves its arrays out).
 Scenarios: the three grids of tests/test_hip_sample_cn.py (60, 40 and 24 segments at 165, 355 and 457 states) and 16 segments at
 max_copy_number 16 (more than 512 states: the <16> instantiations), three chains, four restarts after two sweeps, restarts 1 and 2
@@ -107,6 +107,11 @@ def scenario(N, M, max_cn, out):
                     qe = np.array([[a, z, mi, names.index(lv)] for a, z in runs
                                    for mi, lv in ((-1, 'peak_total_1'), (1, 'peak_total_any'), (5, 'floor_total_1'), (-1, 'floor_minor_any'))], dtype=np.int32)
                     out[key('region_extremes%d_%s' % (K, tag))] = b.region_extremes_raw(0, R, qe, masks, levels, con, K)
+            if hasattr(b, 'region_conditional_raw'):
+                cw, _ = posteriors.feature_matrix(b.cn_classes)
+                win = np.array([(cs[np.searchsorted(ce, a)], ce[np.searchsorted(ce, a)]) for a in qr[:, 0]], dtype=np.int32)
+                out[key('region_conditional_logp_' + tag)], out[key('region_conditional_' + tag)] = b.region_conditional_raw(
+                    0, R, qr, win, masks, labels, con, cw, argmax)
         out[key('region_moments1')] = b.region_moments_raw(0, R, qm1, feats, weights, 1)
         out[key('region_moments4')] = b.region_moments_raw(0, R, qm4, feats, weights, 4)
         print('%d states, %d model segments, %d chains, %d plain and %d breakend adjacencies, %d runs, %d anchors, %d of %d segments unbound' % (

@@ -598,6 +598,33 @@ int rmx_region_decode(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const in
                       int32_t nmask, const uint8_t *masks, int32_t nlabel, const int16_t *labels, const uint8_t *constrain,
                       int32_t max_len, int16_t *states_out, double *logp_out);
 
+/* Region alternatives: the K most probable copy-number configurations of a region, and their probabilities.
+ * Queries, tables and constrain are those of rmx_region_decode; for the event E of query i over the model segments [a, b],
+ *   logp_out[r][i][k] = log P*_k,  P*_0 >= P*_1 >= .. the K largest values of q(c_a, .., c_b) over pairwise distinct
+ * configurations that satisfy E, q the marginal of the run as in rmx_region_decode, and states_out[r][i][k][j] = c_{a+j} of
+ * the configuration of rank k.  Every state keeps its K best continuations, so the K configurations are distinct paths by
+ * construction.  If fewer than K configurations have positive probability, the remaining ranks are -inf with states -1.
+ * Tie rule: at every step the candidates W_n(s, s') h(s', j) are compared before the multiplication by fa_n(s) and the scaling;
+ * one enters a state's list only if it is strictly greater than the entry it displaces, and candidates are met in order of s'
+ * ascending, then rank j ascending, so equal values keep the lower (s', j) first; the final selection orders by value
+ * descending, then state, then rank ascending.  Rank 0 -- value and states -- equals rmx_region_decode's result bit for bit.
+ * A lower rank more than about 1e-308 below the most probable partial path of a step underflows and drops out, as a state
+ * does in rmx_region_decode.  The model is not modified.
+ *   K          1 .. 8
+ *   max_len    1 .. 16384, at least every query's b - a + 1
+ *   states_out int16 [nr][nq][K][max_len]; entries past the run, every entry of an empty rank and of a failed query are -1
+ *   logp_out   [nr][nq][K]; -inf for an empty rank (all K for an impossible event)
+ * A (restart, query) result, all K values and paths, is bit-identical in any restart range, any batch of queries, any
+ * chunking and for any max_len, and ranks 0 .. K' - 1 of a call with K equal a call with K' < K.  Device memory a call holds
+ * beyond the model, kept with the batch and shared with rmx_region_decode: at most 64 MiB of staged outputs and queries and
+ * at most 1 GiB of int16 back-pointers, max_len * K * S per (restart, query) of a chunk (the largest strip is 256 MiB); a
+ * call that needs more runs in chunks of queries and blocks of restarts (rmxh::kbest_plan, rmx_host.h).
+ * Errors as rmx_region_decode, and RMX_EARG with nothing launched and both outputs untouched for K outside [1, 8].
+ * RMX_EASSERT with the restarts listed: every rank of the failed query is NaN, its states -1. */
+int rmx_region_kbest(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries,
+                     int32_t nmask, const uint8_t *masks, int32_t nlabel, const int16_t *labels, const uint8_t *constrain,
+                     int32_t K, int32_t max_len, int16_t *states_out, double *logp_out);
+
 /* -- module-level functions on caller-supplied dense inputs ----------------- */
 /* sum_product (:1213-1246): f [N][S], T [N-1][S][S] -> alphas, betas [N][S] */
 int rmx_sum_product(const double *f, const double *T, double *alphas, double *betas,

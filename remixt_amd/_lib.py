@@ -115,6 +115,8 @@ SYMBOLS = {
     "rmx_num_profile_ids": (C.c_int, []),
     "rmx_region_conditional": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                          C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_int16), C.POINTER(C.c_uint8), C.c_int32, _dp, C.POINTER(C.c_int16), _dp, _dp]),
+    "rmx_region_kbest": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_uint8),
+                                   C.c_int32, C.POINTER(C.c_int16), C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_int16), _dp]),
 }
 
 _lib = None

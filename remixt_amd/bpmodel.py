@@ -866,6 +866,28 @@ class RemixtBatch(object):
         self._ck(self._lib.rmx_region_decode(self._handle, r0, nr, *args, max_len, sbuf.ctypes.data_as(C.POINTER(C.c_int16)), obuf.ctypes.data_as(_dp)))
         return out, states
 
+    def region_kbest_raw(self, r0, nr, queries, k, masks=None, labels=None, constrain=None, max_len=None):
+        """The k most probable pairwise distinct configurations of every query's run, and their log-probabilities, under the
+        structured posterior of the last update_p_cn of restarts r0 .. r0+nr-1 (rmx_region_kbest): (logp (nr, nq, k), states
+        int16 (nr, nq, k, max_len)).  queries, masks, labels, constrain and max_len as region_decode_raw; 1 <= k <= 8.
+        logp[r, i] does not increase along its ranks, rank 0 is region_decode_raw's result bit for bit, and ranks past the
+        number of configurations with positive probability are -inf with states -1.  Ties: equal values keep the lower
+        (next state, rank) first at every step, the final order is value descending, then state, then rank ascending."""
+        r0, nr, k = int(r0), int(nr), int(k)
+        q, args, _keep = self._region_args(queries, masks, labels, constrain)
+        if not -2 ** 31 <= k < 2 ** 31:
+            raise ValueError('k out of range')
+        if max_len is None:
+            max_len = int(np.clip((q[:, 1].astype(np.int64) - q[:, 0] + 1).max(), 1, 16384)) if q.shape[0] else 1
+        max_len = int(max_len)
+        kk = k if 1 <= k <= 8 else 1
+        out = np.zeros((max(nr, 0), q.shape[0], kk), dtype=np.float64)
+        states = np.full((max(nr, 0), q.shape[0], kk, max(max_len, 0)), -1, dtype=np.int16)
+        obuf = out if out.size else np.zeros(1)
+        sbuf = states if states.size else np.zeros(1, dtype=np.int16)
+        self._ck(self._lib.rmx_region_kbest(self._handle, r0, nr, *args, k, max_len, sbuf.ctypes.data_as(C.POINTER(C.c_int16)), obuf.ctypes.data_as(_dp)))
+        return out, states
+
     # -- measurement ------------------------------------------------------------
     def timer_start(self):
         self._ck(self._lib.rmx_timer_start(self._handle))
@@ -1121,6 +1143,11 @@ class RemixtModel(object):
     def region_pattern(self, queries, pieces, masks=None, labels=None, constrain=None):
         """RemixtBatch.region_pattern_raw of this model: log-probabilities (nq,)."""
         return self._batch.region_pattern_raw(self._r, 1, queries, pieces, masks, labels, constrain)[0]
+
+    def region_kbest(self, queries, k, masks=None, labels=None, constrain=None, max_len=None):
+        """RemixtBatch.region_kbest_raw of this model: (logp (nq, k), states int16 (nq, k, max_len))."""
+        logp, states = self._batch.region_kbest_raw(self._r, 1, queries, k, masks, labels, constrain, max_len)
+        return logp[0], states[0]
 
     def region_decode(self, queries, masks=None, labels=None, constrain=None, max_len=None):
         """RemixtBatch.region_decode_raw of this model: (logp (nq,), states int16 (nq, max_len))."""

@@ -899,6 +899,21 @@ class BreakpointModel(object):
         out = posteriors.batch_region_calls(b, r, 1, regions, self.seg_fwd_remap, self.seg_is_original, self.is_telomere, event=event, cn=states)
         return dict((k, v[0]) for k, v in out.items())
 
+    def region_alternatives(self, regions, k=4, event=None, cn=None):
+        """The k most probable copy-number configurations of every region under the structured posterior of the last
+        variational update (posteriors.batch_region_alternatives): what else could be there besides region_call's answer, and
+        how much of the mass the list explains.  regions, event and cn as region_call; 1 <= k <= 8.  A list over regions of
+        dicts: cn (a list over the found ranks of (segments, M, 2) arrays), log_prob (k,), log_p_event, log_prob_given_event
+        (k,), coverage, n_differ (k,), rank_of_call and duplicate_of (k,)."""
+        from . import posteriors
+        if not hasattr(self.model, 'region_kbest'):
+            raise NotImplementedError('kernel module %s has no region alternatives' % getattr(self._kernel_module(), '__name__', '?'))
+        b, r, states, single = self._call_states(cn)
+        if not single:
+            raise ValueError('region_alternatives takes one call of shape (num_segments, num_clones, 2)')
+        return posteriors.batch_region_alternatives(b, r, 1, regions, self.seg_fwd_remap, self.seg_is_original, self.is_telomere, k=k, event=event,
+                                                    cn=states)[0]
+
     def ploidy_posterior_sd(self):
         """The exact posterior SD of the tumour ploidy whose mean is stats['ploidy_posterior_mean']: the whole genome as one
         region of region_cn_moments (posteriors.moment_stats)."""

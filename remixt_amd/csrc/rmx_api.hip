@@ -61,6 +61,9 @@ static const char *kPairKernelNames[KID_ALL - KID_COUNT] = {"k_restart_overlap"}
 // run over together with the first two.  A batch's profile keeps KID_PROFILE_ALL slots.
 enum LaterKernelId { KID_REGION_CONDITIONAL = KID_ALL, KID_PROFILE_ALL };
 static const char *kLaterKernelNames[KID_PROFILE_ALL - KID_ALL] = {"k_region_conditional"};
+// The third range is closed too (tests/test_conditional_posterior_cpu.py pins rmx_num_profile_ids() == rmx_num_kernels() + 1 with
+// k_region_conditional last, tests/test_hip_region_conditional.py pins RMX_EARG at rmx_num_profile_ids()): k_region_kbest has no
+// profile id.  Its launches run without a ProfScope; tools time it with rmx_timer_start / rmx_timer_stop.
 
 struct ProfRec { int id; hipEvent_t a, b; };
 
@@ -167,7 +170,7 @@ struct rmx_batch {
     int16_t *d_samp = nullptr; size_t samp_cap = 0; uint64_t *d_seeds = nullptr; uint32_t *d_sflags = nullptr;   // rmx_sample_cn: paths of a chunk of samples, seeds, flags [R]
     double *d_psum = nullptr; size_t psum_cap = 0; double *d_psw = nullptr; size_t psw_cap = 0;   // rmx_posterior_summary: output staging of a chunk (doubles), weights [C][S][Q]
     double *d_rgcw = nullptr; size_t rgcw_cap = 0;   // rmx_region_conditional: the U rows of a chunk (doubles), at most 256 MiB
-    double *d_rgn = nullptr; size_t rgn_cap = 0; uint8_t *d_rgt = nullptr; size_t rgt_cap = 0; uint32_t *d_rflags = nullptr; int16_t *d_rgbp = nullptr; size_t rgbp_cap = 0;   // (d_rgbp: the back-pointer strips of a chunk of rmx_region_decode)  rmx_region_prob: outputs + queries of a chunk (doubles), label / mask / constrain tables (bytes), flags [R]
+    double *d_rgn = nullptr; size_t rgn_cap = 0; uint8_t *d_rgt = nullptr; size_t rgt_cap = 0; uint32_t *d_rflags = nullptr; int16_t *d_rgbp = nullptr; size_t rgbp_cap = 0; int kbest_lds_raised = 0;   // (d_rgbp: the back-pointer strips of a chunk of rmx_region_decode)  rmx_region_prob: outputs + queries of a chunk (doubles), label / mask / constrain tables (bytes), flags [R]
     double *d_ovr = nullptr; size_t ovr_cap = 0; uint32_t *d_ovf = nullptr; size_t ovf_cap = 0; hipEvent_t ev_ov = nullptr;   // rmx_restart_overlap: sqrt(Wb) [TC][S][S] (built per call), flags [R + R of the other batch], the other batch's stream has reached the call
     uint16_t *d_comp = nullptr; int32_t *d_ends = nullptr; size_t comp_cap = 0, ends_cap = 0; int last_traceback = 0;      // parallel trace-back: composed maps [nr][NBLK][S], block end states [nr][NBLK]
     uint8_t *d_vit_code = nullptr; double *d_vit_val = nullptr; bool vit_code_ok = false, vit_mul_ok = false;   // 8-bit codes of T(i, o) of class 0 + their values (k_viterbi_code)
@@ -926,6 +929,59 @@ static int run_decode(rmx_batch *b, int r0, int nr, int nq, const int32_t *queri
         }
     }
     return report_flags(b, b->d_rflags, r0, nr, "region_decode: a backward step has a zero or non-finite normaliser or maximum");
+}
+
+// rmx_region_kbest's driver, beside run_decode: K log-probabilities and K * max_len int16 states per (restart, query), and a strip of
+// max_len * K * S int16 back-pointers each.  The chunks are rmxh::kbest_plan's, under run_decode's two budgets and in its two
+// buffers.  KT, the kernel's list length, is K rounded up to 1, 2, 4 or 8; the dynamic LDS is SR (8 KT + 14) bytes, SR = S rounded
+// up to 4 (KT = 1: 8 SR more, its second row).  No profile id (see the lists at the top): the launches run without a ProfScope.
+template <int KT> static int launch_kbest(rmx_batch *b, const Dev &dv, int r, int nrun, int nqc, int use_wb, const RgnArgs &ra, int K, int max_len, int16_t *bp,
+                                          int16_t *states, double *out) {
+    const size_t SR = ((size_t)dv.S + 3) & ~(size_t)3, lds = SR * (8 * KT + 14 + (KT == 1 ? 8 : 0));
+    if (lds > 48 * 1024 && !(b->kbest_lds_raised & KT)) {      // (once per instance and batch: S is the batch's)
+        HIPCHK(hipFuncSetAttribute((const void *)k_region_kbest<KT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        b->kbest_lds_raised |= KT;
+    }
+    hipLaunchKernelGGL(k_region_kbest<KT>, dim3((unsigned)nqc, nrun), dim3(RGN_NT), lds, b->stream, dv, r, use_wb, ra, K, max_len, bp, states, out, b->d_rflags);
+    HIPCHK(hipGetLastError());
+    return RMX_OK;
+}
+static int run_kbest(rmx_batch *b, int r0, int nr, int nq, const int32_t *queries, int K, int max_len, RgnArgs ra, int16_t *states_out, double *logp_out) {
+    int rc;
+    if (!b->d_rflags && (rc = dalloc(b, &b->d_rflags, b->R))) return rc;
+    rmxh::KbestPlan pl;
+    if (rmxh::kbest_plan(nr, nq, b->d.S, K, max_len, &pl)) return fail(RMX_EARG, "region_kbest: no chunk plan");
+    const int nrc = pl.nrc;
+    const size_t qc = (size_t)pl.qc, row = (size_t)K * max_len;
+    if ((rc = grow(b, &b->d_rgn, &b->rgn_cap, pl.out_doubles))) return rc;
+    if ((rc = grow(b, &b->d_rgbp, &b->rgbp_cap, pl.bp_elems))) return rc;
+    double *dout = b->d_rgn;
+    int16_t *dstates = (int16_t *)(b->d_rgn + pl.states_at);
+    int32_t *dq = (int32_t *)(b->d_rgn + pl.queries_at);
+    HIPCHK(hipMemsetAsync(b->d_rflags + r0, 0, sizeof(uint32_t) * nr, b->stream));
+    for (size_t q0 = 0; q0 < (size_t)nq; q0 += qc) {
+        const size_t nqc = std::min(qc, (size_t)nq - q0);
+        HIPCHK(hipMemcpyAsync(dq, queries + 4 * q0, nqc * 16, hipMemcpyHostToDevice, b->stream));
+        ra.queries = dq; ra.nq = (int)nqc;
+        for (int rb = 0; rb < nr; rb += nrc) {
+            const int nrr = std::min(nrc, nr - rb);
+            rc = for_model_runs(b, r0, rb, rb + nrr, [&](int i, int j, int, const Dev &dv, int use_wb) -> int {
+                const size_t at = (size_t)(i - rb) * nqc;      // the run's first (restart, query) of the chunk
+                int16_t *bp = b->d_rgbp + at * pl.strip_elems, *st = dstates + at * row;
+                double *out = dout + at * K;
+                if (K == 1) return launch_kbest<1>(b, dv, r0 + i, j - i, (int)nqc, use_wb, ra, K, max_len, bp, st, out);
+                if (K == 2) return launch_kbest<2>(b, dv, r0 + i, j - i, (int)nqc, use_wb, ra, K, max_len, bp, st, out);
+                if (K <= 4) return launch_kbest<4>(b, dv, r0 + i, j - i, (int)nqc, use_wb, ra, K, max_len, bp, st, out);
+                return launch_kbest<8>(b, dv, r0 + i, j - i, (int)nqc, use_wb, ra, K, max_len, bp, st, out);
+            });
+            if (rc) return rc;
+            // device [nrr][nqc][K] and [nrr][nqc][K][max_len] -> host rows (rb .. rb+nrr)[q0 .. q0+nqc)
+            HIPCHK(hipMemcpy2DAsync(logp_out + ((size_t)rb * nq + q0) * K, (size_t)nq * K * 8, dout, nqc * K * 8, nqc * K * 8, nrr, hipMemcpyDeviceToHost, b->stream));
+            HIPCHK(hipMemcpy2DAsync(states_out + ((size_t)rb * nq + q0) * row, (size_t)nq * row * 2, dstates, nqc * row * 2, nqc * row * 2, nrr,
+                                    hipMemcpyDeviceToHost, b->stream));
+        }
+    }
+    return report_flags(b, b->d_rflags, r0, nr, "region_kbest: a backward step has a zero or non-finite normaliser or maximum");
 }
 
 // HIP's current device is per host thread and starts at 0: every entry point binds the calling thread to the
@@ -3744,6 +3800,43 @@ int rmx_region_decode(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const in
     if ((rc = stage_region_tables(b, nmask, masks, nlabel, labels, constrain, &ra))) return rc;
     return run_decode(b, r0, nr, nq, queries, max_len, ra, states_out, logp_out);
 }
+
+// Region alternatives (k_region_kbest): the K most probable pairwise distinct configurations of rmx_region_prob's event over every
+// query's run, their log-probabilities and their states.  Checks, tables and staging are rmx_region_decode's, with
+// rmxh::kbest_k_ok; the driver is run_kbest.  One workgroup computes a (restart, query) on its own in its own strip, so a result
+// depends on neither the restart range, the chunking, the other queries nor max_len, and its ranks below K' not on K >= K'.
+int rmx_region_kbest(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nmask, const uint8_t *masks, int32_t nlabel,
+                     const int16_t *labels, const uint8_t *constrain, int32_t K, int32_t max_len, int16_t *states_out, double *logp_out) { BIND(b);
+    int rc;
+    if ((rc = check_region_call(b, "region_kbest", r0, nr, nq, queries, logp_out))) return rc;
+    if (!states_out) return fail(RMX_EARG, "region_kbest: no queries or no output");
+    if ((rc = check_mask_label_tables("region_kbest", nmask, masks, nlabel, labels))) return rc;
+    if (!rmxh::kbest_k_ok(K)) return fail(RMX_EARG, "region_kbest: K must be in [1, 8]");
+    if (!rmxh::decode_max_len_ok(max_len)) return fail(RMX_EARG, "region_kbest: max_len must be in [1, 16384]");
+    if (b->d.S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "region_kbest: more than 1024 states");
+    if ((rc = check_queries(b, "region_kbest", nq, queries, {-1, nmask, "region_kbest: mask index out of range"}, {-1, nlabel, "region_kbest: label index out of range"}))) return rc;
+    {
+        const char *why = nullptr;
+        const int64_t bad = rmxh::check_decode_lengths(nq, queries, max_len, &why);
+        if (bad >= 0) return fail(RMX_EARG, std::string("region_kbest: ") + why + " (query " + std::to_string(bad) + ")");
+    }
+    if ((rc = require_snapshot(b, r0, nr, "region_kbest"))) return rc;
+    RgnArgs ra;
+    if ((rc = stage_region_tables(b, nmask, masks, nlabel, labels, constrain, &ra))) return rc;
+    return run_kbest(b, r0, nr, nq, queries, K, max_len, ra, states_out, logp_out);
+}
+
+#ifdef RMX_KBEST_COUNT
+// (instrumented builds only, tools/region_alternatives_time.py: the two counters of k_region_kbest, read and optionally reset)
+int rmx_kbest_counts(rmx_batch *b, uint64_t *out, int32_t reset) { BIND(b);
+    HIPCHK(hipStreamSynchronize(b->stream));
+    unsigned long long v[2] = {0, 0};
+    HIPCHK(hipMemcpyFromSymbol(v, HIP_SYMBOL(rgk_count), sizeof v));
+    out[0] = v[0]; out[1] = v[1];
+    if (reset) { v[0] = v[1] = 0; HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(rgk_count), v, sizeof v)); }
+    return RMX_OK;
+}
+#endif
 
 // ---- module-level functions -------------------------------------------------------------------
 int rmx_sum_product(const double *f, const double *T, double *alphas, double *betas, int32_t N, int32_t S, int32_t device) {

@@ -6,6 +6,7 @@
 //   check_patterns       rmx_region_pattern: the rules of the piece lists of its queries
 //   check_conditional, conditional_q_ok, conditional_pairs  rmx_region_conditional: the run and window rules, and the chunks of a call
 //   decode_max_len_ok, check_decode_lengths, decode_plan  rmx_region_decode: the length rules and the chunks of a call
+//   kbest_k_ok, kbest_plan                                rmx_region_kbest: the rank rule and the chunks of a call
 //   extremes_ncol_ok, check_levels  rmx_region_extremes: the column rule, and that no level entry is negative
 //   check_pairs, check_permutations  rmx_restart_overlap: the restart pairs lie inside the two batches, every permutation row is a bijection
 //   weighted_search      rmx_weighted_search: numpy's cumsum / searchsorted(side='right') for the weighted M-step samples
@@ -171,6 +172,37 @@ inline int decode_plan(int32_t nr, int32_t nq, int32_t S, int32_t max_len, Decod
     p->bp_elems = nrc * qc * strip;
     p->states_at = nrc * qc;
     p->queries_at = p->states_at + (nrc * qc * (size_t)max_len * 2 + 7) / 8;
+    p->out_doubles = p->queries_at + 2 * qc;
+    return 0;
+}
+
+// rmx_region_kbest.  Its rank rule: 1 <= K <= KBEST_MAX_K (a packed back-pointer keeps the rank in three bits)
+constexpr int32_t KBEST_MAX_K = 8;
+inline bool kbest_k_ok(int32_t K) { return K >= 1 && K <= KBEST_MAX_K; }
+// The chunks of a call, as decode_plan's with a rank axis: per (restart, query) a strip of max_len * K * S int16 pointers, K
+// log-probabilities (doubles) and K * max_len states (int16), and per query 16 bytes of staged query, under the same two budgets
+// (the buffers are the ones rmx_region_decode grows).  The length rules are check_decode_lengths.  nrc and qc are the largest with
+//   nrc * qc * strip_bytes <= DECODE_BP_BUDGET   and   qc * (nrc * K * (8 + 2 max_len) + 16) + 8 <= DECODE_OUT_BUDGET,
+// nrc <= 65535 taken first, and never below one restart and one query: the largest strip, 16384 * 8 * 1024 * 2 bytes = 256 MiB,
+// and the largest single output, 8 * (8 + 32768) + 16 bytes, fit their budgets.  The staging buffer, in doubles: logp [nrc][qc][K]
+// at 0, states int16 [nrc][qc][K][max_len] at states_at, queries int32 [qc][4] at queries_at, out_doubles in all
+struct KbestPlan {
+    int32_t nrc, qc;
+    size_t strip_elems;       // int16 per (restart, query) strip
+    size_t bp_elems;          // int16 of back-pointer scratch: nrc * qc * strip_elems
+    size_t states_at, queries_at, out_doubles;
+};
+inline int kbest_plan(int32_t nr, int32_t nq, int32_t S, int32_t K, int32_t max_len, KbestPlan *p) {
+    if (!p || nr < 1 || nq < 1 || S < 1 || S > DECODE_MAX_STATES || !kbest_k_ok(K) || !decode_max_len_ok(max_len)) return 5;
+    const size_t strip = (size_t)max_len * (size_t)K * (size_t)S, strip_bytes = strip * 2, per_out = (size_t)K * (8 + 2 * (size_t)max_len);
+    const size_t strips = std::max<size_t>(1, DECODE_BP_BUDGET / strip_bytes);
+    const size_t nrc = std::min<size_t>(std::min<size_t>((size_t)nr, 65535), std::min<size_t>(strips, std::max<size_t>(1, (DECODE_OUT_BUDGET - 24) / per_out)));
+    const size_t qc = std::max<size_t>(1, std::min<size_t>((size_t)nq, std::min<size_t>(strips / nrc, (DECODE_OUT_BUDGET - 8) / (nrc * per_out + 16))));
+    p->nrc = (int32_t)nrc; p->qc = (int32_t)qc;
+    p->strip_elems = strip;
+    p->bp_elems = nrc * qc * strip;
+    p->states_at = nrc * qc * (size_t)K;
+    p->queries_at = p->states_at + (nrc * qc * (size_t)K * (size_t)max_len * 2 + 7) / 8;
     p->out_doubles = p->queries_at + 2 * qc;
     return 0;
 }

@@ -7956,3 +7956,341 @@ __global__ __launch_bounds__(RGN_NT) void k_restart_overlap(Dev d, int use_wb, R
         out[(size_t)orow * q.nq + qi] = failed ? __builtin_nan("") : logp;
     }
 }
+
+// =============================================================================
+// Region alternatives: the K most probable pairwise distinct configurations of a region under the structured posterior of the
+// last update_p_cn, and their probabilities (K <= 8).  It is k_region_decode's recursion with a rank axis: every state keeps
+// its K best partial paths instead of one,
+//   g_b(s, 0) = [mask] post_b(s),   g_b(s, j) = 0 for j >= 1,   h(s', j) = g_n+1(s', j) / D_n(s')   (D the same SUM as in k_region_prob),
+//   g_n(s, .) = [mask] fa_n(s) (the K largest of { W_n(s, s') h(s', j) : label(s) == label(s'), j < K }), in descending order,
+//   bp_n(s, k) = the (s', j) that gave entry k, packed (s' << 3) | j, -1 for an empty entry,
+// and at n = a the K largest of all g_a(s, j).  Different (s', j) are different continuations, so the entries of a state, and
+// the K results, are distinct paths by construction.  g is divided by M = max_s g(s, 0) after every step (rank 0's scale, as in
+// k_region_decode) and the logarithms of M are added up; rank k's log-probability is that sum plus the logarithm of its unscaled
+// final value.  A lower rank more than about 1e-308 below the best state's rank 0 underflows and drops out, as a state does in
+// k_region_decode; a state whose fa entry underflowed to 0 in the sweep's scaled rows cannot be chosen.
+// Tie rule: every comparison is made on the products W h, before the multiplication by fa and the division by M; a candidate
+// enters a list only if it is strictly greater than the entry it displaces; candidates are met in order of s' ascending, then j
+// ascending, so equal values keep the lower (s', j) first.  The final selection orders by value descending, then s, then j
+// ascending.  h(s', .) does not increase in j and a multiplication by W >= 0 rounds monotonically, so the walk over j stops at
+// the first candidate that does not enter.  Rank 0 meets the same products in the same order as k_region_decode's Wb pass and
+// keeps the first maximum, which is also what that kernel's butterfly returns on exp(trans_value): rank 0, value and path, is
+// that kernel's result bit for bit; and ranks 0 .. K' - 1 do not depend on K >= K'.
+// One workgroup of 256 threads per (restart, query).  KT, the list length, is K rounded up to 1, 2, 4 or 8; ranks >= K are
+// computed and discarded.  Dynamic LDS, SR = S rounded up to 4: g [KT][SR] doubles, rank-major (threads that own consecutive s
+// read consecutive words); h overwrites g in place; fa [SR] doubles; two label rows and the compacted index [SR] int16:
+// SR (8 KT + 14) bytes.  KT = 1 alone keeps a second g row (SR * 30 bytes in all) that the list pass writes while the first is
+// read, the two swapping after the step: without values waiting in registers the instance fits the registers of five waves per
+// SIMD, k_region_decode's occupancy, which the short-run workloads need.  The D pass is k_region_decode's; after it the lanes of an s' divide that state's ranks (Wb), or the
+// thread that owns s' divides them (exp(trans_value)).  In the list pass the thread owns s = tid + 256 i on both adjacency kinds
+// and keeps its (value, pointer) lists in registers, every index a constant after unrolling; on Wb it walks the compacted s', on
+// exp(trans_value) the s' with h(s', 0) != 0 with one exponential per (s, s') for all ranks; masked rows and (there) rows with
+// fa = 0 are skipped.  New values wait in registers until a barrier says that every thread has read h; the pointers go straight
+// to the workgroup's strip of global scratch, int16 [max_len][K][S], written by consecutive threads.  They are published as in
+// k_region_decode (the wave waits for its stores, then a barrier) and threads k < K each trace one path a -> b.
+// Failure rule of k_region_decode (a NaN in rank 0 of g counts as an infinite maximum): RGD_ERR_DENOM in flags[r], every rank NaN,
+// states -1; a step maximum of exactly 0 gives -inf for every rank.  Ranks past the number of configurations with positive
+// probability are -inf with states -1.
+// grid (queries, restarts), block RGN_NT; out[(ri * nq + query) * K + k], states[((ri * nq + query) * K + k) * max_len + i].
+// =============================================================================
+#define RGK_MAXK 8
+#define RGK_NS (RGN_MAXS / RGN_NT)      // states a thread owns
+// (v, p) enters the descending list behind every entry >= v; the caller has checked v > val[KT - 1]
+template <int KT> __device__ __forceinline__ void rgk_insert(double (&val)[KT], int (&ptr)[KT], double v, int p) {
+#pragma unroll
+    for (int k = KT - 1; k >= 1; k--) {
+        const bool down = v > val[k - 1], here = v > val[k];      // (down implies here: the list descends)
+        val[k] = down ? val[k - 1] : (here ? v : val[k]);
+        ptr[k] = down ? ptr[k - 1] : (here ? p : ptr[k]);
+    }
+    const bool top = v > val[0];
+    val[0] = top ? v : val[0];
+    ptr[0] = top ? p : ptr[0];
+}
+#ifdef RMX_KBEST_COUNT
+// an instrumented build for tools/region_alternatives_time.py, never the library's: the (s, s') pairs the list passes met and the
+// (s', j) candidates they evaluated, summed over every launch since the last reset
+__device__ unsigned long long rgk_count[2];
+#define RGK_COUNT_PAIR() (c_pairs++)
+#define RGK_COUNT_EVAL() (c_evals++)
+#else
+#define RGK_COUNT_PAIR()
+#define RGK_COUNT_EVAL()
+#endif
+template <int KT>
+__global__ __launch_bounds__(RGN_NT) void k_region_kbest(Dev d, int r0, int use_wb, RgnArgs q, int K, int max_len, int16_t *bp_all, int16_t *states, double *out,
+                                                         uint32_t *flags) {
+    extern __shared__ double rgk_lds[];
+    __shared__ double red[RGN_NT / 64];
+    __shared__ int ired[RGN_NT / 64];
+    __shared__ int nact, s_bad;
+    __shared__ int pick_s[RGK_MAXK], pick_j[RGK_MAXK];
+    __shared__ double pick_v[RGK_MAXK];
+    const int qi = blockIdx.x, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x;
+    const int grp = tid / RGN_GL, gl = tid % RGN_GL;
+    const int S = d.S, SR = (S + 3) & ~3;
+    constexpr int UNR = KT == 1 ? 1 : RGK_NS;     // the list passes' unrolling over the states a thread owns
+    constexpr bool TWO = KT == 1;                 // KT = 1 keeps a second row: new values go straight to it (see the header)
+    double *g = rgk_lds;                          // [KT][SR]; h in place
+    double *g2 = g + (size_t)KT * SR;             // [SR] (TWO only): the row the step writes; the two swap after it
+    double *fas = g2 + (TWO ? SR : 0);            // [SR]
+    int16_t *labs = (int16_t *)(fas + SR);        // [2][SR]
+    int16_t *idx = labs + 2 * SR;                 // [SR]: the compacted list on Wb; the states' cursors of the final selection
+    const int a = q.queries[4 * qi], b = q.queries[4 * qi + 1], mi = q.queries[4 * qi + 2], li = q.queries[4 * qi + 3];
+    const size_t pair = (size_t)ri * q.nq + qi;
+    int16_t *bp = bp_all + pair * (size_t)max_len * K * S;      // row (n - a) * K + k: the pointers of rank k of segment n
+    int16_t *paths = states + pair * (size_t)K * max_len;
+    if (tid == 0) s_bad = 0;
+    int cur = 0;              // labs + cur * SR: the labels of segment n + 1
+    double logp = 0.;         // the logarithms of the maxima of the steps before the last one
+    bool failed = false;
+#ifdef RMX_KBEST_COUNT
+    unsigned long long c_pairs = 0, c_evals = 0;
+#endif
+    // ---- start: g_b(., 0) = [mask] post_b, the other ranks empty --------------------------------------------
+    {
+        const double *post = d.post + rs_off(d, r, b);
+        const auto [mk, lb] = rgn_tabs(d, q, b, mi, li);
+        for (int s = tid; s < S; s += RGN_NT) {
+            g[s] = (!mk || mk[s]) ? post[s] : 0.;
+#pragma unroll
+            for (int k = 1; k < KT; k++) g[k * SR + s] = 0.;
+            if (lb) labs[cur * SR + s] = lb[s];
+        }
+    }
+    for (int n = b - 1; n >= a; n--) {
+        // the maximum of the step before: rank 0's scale
+        double part = 0.;
+        bool nan = false;
+        for (int s = tid; s < S; s += RGN_NT) {
+            const double v = g[s];
+            part = fmax(part, v); nan |= v != v;
+        }
+        if (nan) part = INFINITY;      // (fmax drops a NaN: an infinite maximum fails the query)
+        const double M = rgd_block_max(part, red);
+        if (!rgd_take_max(M, s_bad != 0, logp, failed)) break;
+        for (int s = tid; s < S; s += RGN_NT) {
+#pragma unroll
+            for (int k = 0; k < KT; k++) g[k * SR + s] = g[k * SR + s] / M;
+        }
+        const auto [wb, Wt, pd] = rgn_adj(d, r, n, use_wb);
+        const double *fa = d.fa + rs_off(d, r, n);
+        const auto [mk, lb] = rgn_tabs(d, q, n, mi, li);
+        const int16_t *lab1 = labs + cur * SR;
+        int16_t *lab0 = labs + (cur ^ 1) * SR;
+        int16_t *bpn = bp + (size_t)(n - a) * K * S;
+        for (int s = tid; s < S; s += RGN_NT) {
+            fas[s] = fa[s];
+            if (lb) lab0[s] = lb[s];
+        }
+        __syncthreads();
+        double nv[RGK_NS][KT];
+        if (wb) {
+            // the states s' with g(s', 0) > 0, in state order
+            const int na = rgn_compact(S, idx, nact, [&](int s) { return g[s] > 0.; });
+            // D(s') and h(s', .) = g(s', .) / D(s'): 16 lanes per s'
+            for (int j0 = 0; j0 < na; j0 += RGN_NT / RGN_GL) {
+                const int j = j0 + grp;
+                const bool ok = j < na;
+                const int sp = ok ? idx[j] : 0;
+                double p = 0.;
+                if (ok) {
+                    const double *wr = Wt + (size_t)sp * S;
+                    for (int s = gl; s < S; s += RGN_GL) p = fma(fas[s], wr[s], p);
+                }
+                const double D = group_sum(p, RGN_GL);
+                if (ok && gl == 0 && !(D > 0. && D < INFINITY)) s_bad = 1;
+                if (ok && gl < KT) g[gl * SR + sp] = g[gl * SR + sp] / D;      // the lanes of an s' divide its ranks
+            }
+            __syncthreads();
+            // the lists of s: the thread owns s and walks the s' in state order, j ascending; strictly greater enters
+#pragma unroll UNR
+            for (int it = 0; it < RGK_NS; it++) {
+                const int s = tid + it * RGN_NT;
+                double val[KT];
+                int ptr[KT];
+#pragma unroll
+                for (int k = 0; k < KT; k++) { val[k] = 0.; ptr[k] = -1; }
+                const bool on = s < S && (!mk || mk[s]);
+                if (on) {
+                    const int ls = lb ? lab0[s] : 0;
+                    const double *wc = Wt + s;
+                    for (int j = 0; j < na; j++) {
+                        const int sp = idx[j];
+                        if (!lb || lab1[sp] == ls) {      // (off-label weights are not loaded)
+                            const double w = wc[(size_t)sp * S];
+                            RGK_COUNT_PAIR();
+#pragma unroll
+                            for (int k = 0; k < KT; k++) {
+                                const double v = w * g[k * SR + sp];
+                                RGK_COUNT_EVAL();
+                                if (!(v > val[KT - 1])) break;
+                                rgk_insert<KT>(val, ptr, v, (sp << 3) | k);
+                            }
+                        }
+                    }
+                }
+                const double f = on ? fas[s] : 0.;
+#pragma unroll
+                for (int k = 0; k < KT; k++) {
+                    if constexpr (TWO) { if (s < S) g2[s] = on ? val[k] * f : 0.; }
+                    else nv[it][k] = on ? val[k] * f : 0.;
+                    if (s < S && k < K) bpn[(size_t)k * S + s] = (int16_t)ptr[k];
+                }
+            }
+        } else {
+            // D(s') and h(s', .): the thread owns s'
+            for (int sp = tid; sp < S; sp += RGN_NT) {
+                const double gv = g[sp];
+                double D = 1.;
+                if (gv > 0.) {
+                    D = rgn_D_exp(d, n, sp, fas, pd);
+                    if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                }
+#pragma unroll
+                for (int k = 0; k < KT; k++) g[k * SR + sp] = gv > 0. ? g[k * SR + sp] / D : 0.;
+            }
+            __syncthreads();
+            // the lists of s: the thread owns s and walks the s' with h(s', 0) != 0; one exponential per (s, s')
+#pragma unroll UNR
+            for (int it = 0; it < RGK_NS; it++) {
+                const int s = tid + it * RGN_NT;
+                double val[KT];
+                int ptr[KT];
+#pragma unroll
+                for (int k = 0; k < KT; k++) { val[k] = 0.; ptr[k] = -1; }
+                const bool on = s < S && (!mk || mk[s]) && fas[s] != 0.;
+                if (on) {
+                    const int ls = lb ? lab0[s] : 0;
+                    for (int sp = 0; sp < S; sp++) {
+                        const double hv = g[sp];
+                        if (hv != 0. && (!lb || lab1[sp] == ls)) {
+                            const double w = exp(trans_value(d, n, s, sp, pd));
+                            RGK_COUNT_PAIR();
+#pragma unroll
+                            for (int k = 0; k < KT; k++) {
+                                const double v = w * g[k * SR + sp];
+                                RGK_COUNT_EVAL();
+                                if (!(v > val[KT - 1])) break;
+                                rgk_insert<KT>(val, ptr, v, (sp << 3) | k);
+                            }
+                        }
+                    }
+                }
+                const double f = on ? fas[s] : 0.;
+#pragma unroll
+                for (int k = 0; k < KT; k++) {
+                    if constexpr (TWO) { if (s < S) g2[s] = on ? val[k] * f : 0.; }
+                    else nv[it][k] = on ? val[k] * f : 0.;
+                    if (s < S && k < K) bpn[(size_t)k * S + s] = (int16_t)ptr[k];
+                }
+            }
+        }
+        if constexpr (TWO) {
+            double *t = g; g = g2; g2 = t;
+        } else {
+            __syncthreads();      // every thread has read h: g may be written
+#pragma unroll
+            for (int it = 0; it < RGK_NS; it++) {
+                const int s = tid + it * RGN_NT;
+                if (s < S) {
+#pragma unroll
+                    for (int k = 0; k < KT; k++) g[k * SR + s] = nv[it][k];
+                }
+            }
+        }
+        cur ^= 1;
+        __syncthreads();
+    }
+    // ---- the last maximum, and the K largest of all g_a(s, j): value descending, then s, then j ascending ------------
+    bool have = false;
+    if (!failed && logp > -INFINITY) {
+        __syncthreads();
+        double part = 0.;
+        bool nan = false;
+        for (int s = tid; s < S; s += RGN_NT) {
+            const double v = g[s];
+            part = fmax(part, v); nan |= v != v;
+            idx[s] = 0;       // the state's cursor: its ranks below are taken
+        }
+        if (nan) part = INFINITY;
+        const double M = rgd_block_max(part, red);
+        double scratch_logp = logp;
+        have = rgd_take_max(M, s_bad != 0, scratch_logp, failed);      // (logp stays the sum of the earlier steps)
+        if (!failed && M == 0.) logp = -INFINITY;
+    }
+    if (have) {
+        for (int k = 0; k < K; k++) {
+            double bv = 0.;
+            int bs = 0x7fffffff;
+            for (int s = tid; s < S; s += RGN_NT) {
+                const int c = idx[s];
+                const double v = c < KT ? g[c * SR + s] : 0.;
+                if (v > bv) { bv = v; bs = s; }
+            }
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const double ov = __shfl_xor(bv, o, 64);
+                const int os = __shfl_xor(bs, o, 64);
+                const bool take = ov > bv || (ov == bv && os < bs);
+                bv = take ? ov : bv;
+                bs = take ? os : bs;
+            }
+            __syncthreads();
+            if ((tid & 63) == 0) { red[tid >> 6] = bv; ired[tid >> 6] = bs; }
+            __syncthreads();
+            if (tid == 0) {
+                double tv = red[0];
+                int ts = ired[0];
+#pragma unroll
+                for (int i = 1; i < RGN_NT / 64; i++) {
+                    const bool take = red[i] > tv || (red[i] == tv && ired[i] < ts);
+                    tv = take ? red[i] : tv;
+                    ts = take ? ired[i] : ts;
+                }
+                const bool found = tv > 0. && ts < S;
+                pick_v[k] = found ? tv : 0.;
+                pick_s[k] = found ? ts : -1;
+                pick_j[k] = found ? idx[ts] : 0;
+                if (found) idx[ts] = (int16_t)(idx[ts] + 1);
+            }
+            __syncthreads();
+        }
+    }
+    // ---- trace a -> b through the workgroup's own strip: thread k traces rank k -----------------------------------------
+    // (have and pick_s are the same in every thread: the selection ended with a barrier)
+    const int L = b - a + 1;
+    for (int k = 0; k < K; k++) {
+        const int from = (have && pick_s[k] >= 0) ? L : 0;      // an empty rank, an impossible or a failed query: every entry
+        for (int i = from + tid; i < max_len; i += RGN_NT) paths[(size_t)k * max_len + i] = -1;      // entries past the run
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's back-pointer stores have landed
+    __syncthreads();
+    if (tid < K) {
+        int16_t *path = paths + (size_t)tid * max_len;
+        int c = have ? pick_s[tid] : -1, j = have ? pick_j[tid] : 0;
+        int i = 0;
+        if (c >= 0) {
+            path[0] = (int16_t)c;
+            for (i = 1; i < L; i++) {
+                const int p = bp[((size_t)(i - 1) * K + j) * S + c];
+                if (p < 0 || (p & 7) >= K) break;      // (an entry with positive value has a pointer, to a rank not above its own)
+                c = p >> 3; j = p & 7;
+                path[i] = (int16_t)c;
+            }
+        }
+        const bool whole = c >= 0 && i == L;
+        if (c >= 0 && !whole)
+            for (int k = 0; k < L; k++) path[k] = -1;      // (a trace that the guard ended: see above)
+        double res;
+        if (failed) res = __builtin_nan("");
+        else if (!whole) res = -INFINITY;
+        else res = logp + log(pick_v[tid]);
+        out[pair * K + tid] = res;
+    }
+    if (tid == 0 && failed) atomicOr(&flags[r], RGD_ERR_DENOM);
+#ifdef RMX_KBEST_COUNT
+    __hip_atomic_fetch_add(&rgk_count[0], c_pairs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(&rgk_count[1], c_evals, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+}

@@ -1308,6 +1308,113 @@ def region_calls_on(config):
     return on
 
 
+# ---- the K most probable configurations of a region (rmx_region_kbest) -----------------------------------
+def combine_kbest(logp, piece_region, num_regions, k):
+    """The k best configurations of every region from its pieces' k-best lists.  logp (..., P, K): per piece the
+    log-probabilities of its ranks, descending, -inf for an empty rank.  A region cut at chain ends is a product of independent
+    pieces, so its k best configurations are the k largest sums of one entry per piece: merged piece by piece over the at
+    most k x K candidates of a step, sums taken in piece order, ties to the lower tuple of ranks (in lexicographic order).
+    (values (..., num_regions, k), -inf where fewer than k combinations are possible; choice int (..., num_regions, k, P): the
+    rank taken of every piece of the region, -1 for the other pieces and for an empty rank).  A NaN in a piece makes every
+    value of its region NaN."""
+    logp = np.asarray(logp, dtype=float)
+    piece_region = np.asarray(piece_region, dtype=np.int64)
+    lead, (P, K), R, k = logp.shape[:-2], logp.shape[-2:], int(num_regions), int(k)
+    if k < 1:
+        raise ValueError('k must be at least 1')
+    flat = logp.reshape((-1, P, K))
+    values = np.full((flat.shape[0], R, k), -np.inf)
+    choice = np.full((flat.shape[0], R, k, P), -1, dtype=np.int64)
+    for i in range(flat.shape[0]):
+        for reg in range(R):
+            pieces = np.flatnonzero(piece_region == reg)
+            if np.isnan(flat[i, pieces]).any():
+                values[i, reg] = np.nan
+                continue
+            cur = [(0., ())]      # (sum, ranks of the pieces so far), best first
+            for p in pieces:
+                cand = [(v + w, t + (j,)) for v, t in cur for j, w in enumerate(flat[i, p]) if w > -np.inf]
+                cand.sort(key=lambda c: (-c[0], c[1]))
+                cur = cand[:k]
+            if len(pieces) == 0:
+                cur = []
+            for rank, (v, t) in enumerate(cur):
+                values[i, reg, rank] = v
+                choice[i, reg, rank, pieces] = t
+    return values.reshape(lead + (R, k)), choice.reshape(lead + (R, k, P))
+
+
+def batch_region_alternatives(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, k=4, event=None, cn=None):
+    """The k most probable copy-number configurations of every region under the structured posterior, for restarts
+    r0 .. r0+nr-1 of a RemixtBatch from one rmx_region_kbest call (and one rmx_region_prob call with an event).  regions, event
+    and the pieces as batch_region_calls; cn: None, or the restarts' calls as int (nr, N1) state indices in model segment order.
+    A list over restarts of lists over regions of dicts:
+      cn                    a list over the found ranks of int arrays (segments of the region, M, 2): the copy numbers of the
+                            region's original segments through the state tables, best first;
+      log_prob              (k,) the log-probabilities of the configurations of the region's model segments, -inf past the found ranks;
+      log_p_event           log P(event) over the same pieces, 0 without an event;
+      log_prob_given_event  (k,) log_prob - log_p_event;
+      coverage              the sum over the ranks of exp(log_prob_given_event): the share of the event's mass the list explains;
+      n_differ              int (k,) the number of the region's segments where a rank differs from the call (-1 past the found
+                            ranks and without a call);
+      rank_of_call          the first rank whose cn equals the call on the region, -1 if none;
+      duplicate_of          int (k,) the first earlier rank with the same cn, else -1.
+    Two state paths that differ only inside an inserted zero-length segment are distinct paths with the same copy numbers on
+    the region's segments: both are kept, the later one marked in duplicate_of, and their probabilities are not added up (the
+    k best of the summed-out law is another question, which this list does not answer)."""
+    mi, li = parse_call_event(event)
+    k = int(k)
+    reg = np.array([[int(r[-2]), int(r[-1])] for r in regions], dtype=np.int64).reshape(-1, 2)
+    masks, labels = event_tables(batch.cn_classes)
+    cs, ce = chains_from_telomeres(is_telomere)
+    runs, piece_region, constrain = region_queries(reg, seg_fwd_remap, seg_is_original, cs, ce)
+    P, R = len(runs), len(reg)
+    if P == 0:
+        return [[] for _ in range(nr)]
+    fwd = np.asarray(seg_fwd_remap, dtype=np.int64)
+    classes, seg_class = np.asarray(batch.cn_classes), np.asarray(batch.seg_class)
+    q = np.zeros((P, 4), dtype=np.int32)
+    q[:, :2], q[:, 2], q[:, 3] = runs, mi, li
+    logp, states = batch.region_kbest_raw(r0, nr, q, k, masks, labels, constrain)
+    values, choice = combine_kbest(logp, piece_region, R, k)
+    log_p_event = np.zeros((nr, R))
+    if event is not None:
+        with np.errstate(invalid='ignore'):
+            log_p_event = np.minimum(combine(batch.region_logprob_raw(r0, nr, q, masks, labels, constrain), piece_region, R), 0.)
+    call = None if cn is None else np.asarray(cn).reshape(nr, -1)
+    out = []
+    full = np.full(len(seg_class), -1, dtype=np.int64)
+    for r in range(nr):
+        row = []
+        for g in range(R):
+            seg = fwd[reg[g, 0]:reg[g, 1] + 1]
+            pieces = np.flatnonzero(piece_region == g)
+            found = int(np.isfinite(values[r, g]).sum())
+            paths = []
+            for rank in range(found):
+                for p in pieces:
+                    a, b = int(runs[p, 0]), int(runs[p, 1])
+                    full[a:b + 1] = states[r, p, choice[r, g, rank, p], :b - a + 1]
+                paths.append(full[seg].copy())
+            with np.errstate(invalid='ignore'):
+                given = values[r, g] - log_p_event[r, g]
+            n_differ = np.full(k, -1, dtype=np.int64)
+            duplicate_of = np.full(k, -1, dtype=np.int64)
+            rank_of_call = -1
+            for rank, st in enumerate(paths):
+                same = [j for j in range(rank) if np.array_equal(paths[j], st)]
+                duplicate_of[rank] = same[0] if same else -1
+                if call is not None:
+                    n_differ[rank] = int((st != call[r, seg]).sum())
+                    if rank_of_call < 0 and n_differ[rank] == 0:
+                        rank_of_call = rank
+            row.append({'cn': [classes[seg_class[seg], st] for st in paths], 'log_prob': values[r, g].copy(), 'log_p_event': float(log_p_event[r, g]),
+                        'log_prob_given_event': given, 'coverage': float(np.exp(given[:found]).sum()), 'n_differ': n_differ,
+                        'rank_of_call': rank_of_call, 'duplicate_of': duplicate_of})
+        out.append(row)
+    return out
+
+
 # ---- distribution of a region's peak and lowest copy number (rmx_region_extremes; DESIGN 4.18) ------------------------
 LEVEL_QUANTITIES = ('total', 'major', 'minor')
 LEVEL_ORIENTATIONS = ('peak', 'floor')

@@ -803,6 +803,16 @@ class RestartSet(object):
         return posteriors.batch_region_calls(self.batch, 0, len(self.models), regions, m.seg_fwd_remap, m.seg_is_original, m.is_telomere,
                                              event=event, cn=self._call_states(cn))
 
+    def region_alternatives(self, regions, k=4, event=None, cn=None):
+        """BreakpointModel.region_alternatives of every restart from one device call per kernel: a list over restarts of lists
+        over regions of dicts.  cn: the restarts' calls in experiment order (the `cn` of results()); None: the decoded paths."""
+        from . import posteriors
+        if self.batch is None or not hasattr(self.batch, 'region_kbest_raw'):
+            return [m.region_alternatives(regions, k, event, None if cn is None else cn[r]) for r, m in enumerate(self.models)]
+        m = self.models[0]
+        return posteriors.batch_region_alternatives(self.batch, 0, len(self.models), regions, m.seg_fwd_remap, m.seg_is_original, m.is_telomere,
+                                                    k=k, event=event, cn=self._call_states(cn))
+
     def _call_states(self, cn):
         """int16 (restarts, N1): the restarts' calls as state indices in model segment order.  cn: their paths in
         experiment order (the `cn` of results()); None: the decoded paths."""
@@ -1047,6 +1057,10 @@ class RestartGroups(object):
         """RestartSet.region_call over the groups, restarts in order (cn: of all restarts)."""
         return _join(self._map(lambda rs: rs.region_call(regions, event, self._own(rs, cn))), extend=('cn',))
 
+    def region_alternatives(self, regions, k=4, event=None, cn=None):
+        """RestartSet.region_alternatives over the groups, restarts in order (cn: of all restarts)."""
+        return _join(self._map(lambda rs: rs.region_alternatives(regions, k, event, self._own(rs, cn))))
+
     def call_confidence(self, regions, cn=None):
         """RestartSet.call_confidence over the groups, restarts in order (cn: of all restarts): a dict of arrays (restarts, len(regions))."""
         return _join(self._map(lambda rs: rs.call_confidence(regions, self._own(rs, cn))))
@@ -1207,6 +1221,11 @@ class DatasetGroups(object):
     def region_call(self, regions, event=None):
         """RestartGroups.region_call of every dataset: a list, one dict per dataset."""
         return self._map(lambda part: part.region_call(regions, event))
+
+    def region_alternatives(self, regions, k=4, event=None, cn=None):
+        """RestartGroups.region_alternatives of every dataset (cn: per dataset, a list of its restarts' paths): a list, one list
+        over restarts per dataset."""
+        return self._map(lambda part: part.region_alternatives(regions, k, event, self._own(part, cn)))
 
     def call_confidence(self, regions, cn=None):
         """RestartGroups.call_confidence of every dataset (cn: per dataset, a list of its restarts' paths): a list, one dict of arrays

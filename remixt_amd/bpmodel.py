@@ -95,6 +95,31 @@ def _i64(a):
     return np.ascontiguousarray(a, dtype=np.int64)
 
 
+def _class_weights(weights, num_classes, num_cn_states):
+    """weights (C, S, Q), or (S, Q) for all classes alike, as a contiguous float64 (C, S, Q)."""
+    w = np.asarray(weights, dtype=np.float64)
+    if w.ndim == 2:
+        w = np.broadcast_to(w[None], (num_classes,) + w.shape)
+    if w.ndim != 3 or w.shape[:2] != (num_classes, num_cn_states):
+        raise ValueError('weights must have shape (num_classes, num_cn_states, Q) or (num_cn_states, Q)')
+    return np.ascontiguousarray(w)
+
+
+def _restart_states(states, rows, num_segments):
+    """states int (rows, N), or (N,) with rows = 1, as a contiguous int16 array."""
+    st = np.asarray(states)
+    if st.shape != (rows, num_segments) and not (rows == 1 and st.shape == (num_segments,)):
+        raise ValueError('states must have shape (nr, num_segments)')
+    if st.size and (st.min() < -32768 or st.max() > 32767):
+        raise ValueError('state index out of range')
+    return np.ascontiguousarray(st, dtype=np.int16)
+
+
+def _longest_query(q):
+    """The default max_len of the decode calls: the longest run of queries q (nq, 4), within 1 .. 16384."""
+    return int(np.clip((q[:, 1].astype(np.int64) - q[:, 0] + 1).max(), 1, 16384)) if q.shape[0] else 1
+
+
 def compress_cn_states(cn_states, max_classes=64):
     """(N,S,M,2) int64 -> (classes (C,S,M,2), seg_class (N,) int32)."""
     lib = _lib.load()
@@ -550,12 +575,7 @@ class RemixtBatch(object):
         rows = max(nr, 0)
         Q, wp, proj = 0, _dp(), None
         if weights is not None:
-            w = np.asarray(weights, dtype=np.float64)
-            if w.ndim == 2:
-                w = np.broadcast_to(w[None], (C_,) + w.shape)
-            if w.ndim != 3 or w.shape[:2] != (C_, S):
-                raise ValueError('weights must have shape (num_classes, num_cn_states, Q) or (num_cn_states, Q)')
-            w = np.ascontiguousarray(w)
+            w = _class_weights(weights, C_, S)
             Q = w.shape[2]
             wbuf = w if w.size else np.zeros(1)      # (Q = 0 is the library's error to raise: a non-null pointer reaches it)
             wp = wbuf.ctypes.data_as(_dp)
@@ -564,12 +584,7 @@ class RemixtBatch(object):
         i16p = C.POINTER(C.c_int16)
         sp = i16p()
         if states is not None:
-            st = np.asarray(states)
-            if st.shape != (rows, N) and not (rows == 1 and st.shape == (N,)):
-                raise ValueError('states must have shape (nr, num_segments)')
-            if st.size and (st.min() < -32768 or st.max() > 32767):
-                raise ValueError('state index out of range')
-            st = np.ascontiguousarray(st, dtype=np.int16)
+            st = _restart_states(states, rows, N)
             sp = st.ctypes.data_as(i16p)
         stats = np.zeros((rows, N, 3), dtype=np.float64) if want_stats else None
         amax = np.zeros((rows, N), dtype=np.int16) if want_argmax else None
@@ -781,22 +796,12 @@ class RemixtBatch(object):
             raise ValueError('window entry out of range')
         wn = np.ascontiguousarray(wn, dtype=np.int32)
         nslot = int(np.clip((wn[:, 1].astype(np.int64) - wn[:, 0] + 1).max(), 1, 16384)) if wn.shape[0] else 1
-        w = np.asarray(weights, dtype=np.float64)
-        if w.ndim == 2:
-            w = np.broadcast_to(w[None], (C_,) + w.shape)
-        if w.ndim != 3 or w.shape[:2] != (C_, S):
-            raise ValueError('weights must have shape (num_classes, num_cn_states, Q) or (num_cn_states, Q)')
-        w = np.ascontiguousarray(w)
+        w = _class_weights(weights, C_, S)
         Q = w.shape[2]
         i16p, i32p = C.POINTER(C.c_int16), C.POINTER(C.c_int32)
         sp = i16p()
         if states is not None:
-            st = np.asarray(states)
-            if st.shape != (rows, N) and not (rows == 1 and st.shape == (N,)):
-                raise ValueError('states must have shape (nr, num_segments)')
-            if st.size and (st.min() < -32768 or st.max() > 32767):
-                raise ValueError('state index out of range')
-            st = np.ascontiguousarray(st, dtype=np.int16)
+            st = _restart_states(states, rows, N)
             sp = st.ctypes.data_as(i16p)
         logp = np.zeros((rows, q.shape[0]), dtype=np.float64)
         out = np.zeros((rows, q.shape[0], nslot, (Q + 3) if 1 <= Q <= 64 else 1), dtype=np.float64)
@@ -857,7 +862,7 @@ class RemixtBatch(object):
         r0, nr = int(r0), int(nr)
         q, args, _keep = self._region_args(queries, masks, labels, constrain)
         if max_len is None:
-            max_len = int(np.clip((q[:, 1].astype(np.int64) - q[:, 0] + 1).max(), 1, 16384)) if q.shape[0] else 1
+            max_len = _longest_query(q)
         max_len = int(max_len)
         out = np.zeros((max(nr, 0), q.shape[0]), dtype=np.float64)
         states = np.full((max(nr, 0), q.shape[0], max(max_len, 0)), -1, dtype=np.int16)
@@ -878,7 +883,7 @@ class RemixtBatch(object):
         if not -2 ** 31 <= k < 2 ** 31:
             raise ValueError('k out of range')
         if max_len is None:
-            max_len = int(np.clip((q[:, 1].astype(np.int64) - q[:, 0] + 1).max(), 1, 16384)) if q.shape[0] else 1
+            max_len = _longest_query(q)
         max_len = int(max_len)
         kk = k if 1 <= k <= 8 else 1
         out = np.zeros((max(nr, 0), q.shape[0], kk), dtype=np.float64)

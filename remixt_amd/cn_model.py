@@ -17,6 +17,8 @@ import itertools
 import numpy as np
 import scipy.optimize
 
+from . import posteriors, queries      # (neither imports this module: no cycle)
+
 
 def _get_brkend_seg_orient(breakend):
     """Breakend (segment, side) -> (left segment of the adjacency, orientation)  (cn_model.py:14-22)."""
@@ -207,6 +209,7 @@ def _sample_without_replacement(rng, n, size, p=None):
     return found[:size]
 
 
+@queries.answers('model')      # the posterior queries (posterior_summary, region_events, ...) come from the table of queries.py
 class BreakpointModel(object):
 
     def __init__(self, x, l, adjacencies, breakpoints, **kwargs):
@@ -720,252 +723,22 @@ class BreakpointModel(object):
             raise NotImplementedError('kernel module %s has no posterior sampler' % getattr(self._kernel_module(), '__name__', '?'))
         return self.model.sample_cn(num_samples, seed)[:, self.seg_fwd_remap]
 
-    def posterior_summary(self, cn=None, marginals=False):
-        """Exact per-segment summaries of the posterior marginals of the last variational update, in experiment segment
-        order (as optimal_cn): the arrays of posteriors.unpack -- total_cn_mean / total_cn_sd (N, M), p_subclonal, p_loh,
-        p_hdel, expected_alleles_subclonal, cn_posterior_max, cn_posterior_entropy, cn_mpm, and cn_marginals with
-        marginals=True.  cn: an already decoded path ([N][M][2], model segment order, e.g. what infer_cn fills); it
-        supplies cn_posterior_prob, the marginal probability of its state at every segment."""
-        from . import posteriors
-        if not hasattr(self.model, 'posterior_summary_raw'):
-            raise NotImplementedError('kernel module %s has no posterior summary' % getattr(self._kernel_module(), '__name__', '?'))
-        b = self.model._batch
-        states = None if cn is None else posteriors.cn_to_states(cn, b.cn_classes, b.seg_class)[None]
-        s = posteriors.batch_summaries(b, self.model._r, 1, states=states, marginals=marginals)[0]
-        return dict((k, v[self.seg_fwd_remap]) for k, v in s.items())
-
-    def _region_batch(self):
-        if not hasattr(self.model, 'region_logprob'):
-            raise NotImplementedError('kernel module %s has no region event probabilities' % getattr(self._kernel_module(), '__name__', '?'))
-        return self.model._batch, self.model._r
-
-    def region_events(self, regions):
-        """Exact probabilities, under the structured posterior of the last variational update, of copy-number events over
-        regions: regions is a list of (first, last) experiment segment indices; a dict of arrays (len(regions),):
-        p_all_loh, p_any_loh, p_all_hdel, p_any_hdel, p_any_subclonal (over the region's segments), p_no_change (the same
-        copy-number state along the whole region) and p_no_total_change (the same per-clone totals).  A region that spans
-        chain ends is the conjunction over its chains."""
-        from . import posteriors
-        b, r = self._region_batch()
-        out = posteriors.batch_region_events(b, r, 1, regions, self.seg_fwd_remap, self.seg_is_original, self.is_telomere)
-        return dict((k, v[0]) for k, v in out.items())
-
-    def region_change_counts(self, regions, bins=8):
-        """Exact posterior distribution of the number of copy-number changes inside regions ((first, last) experiment
-        segment indices): a dict of arrays (len(regions), bins), `num_changes` (changes of the copy-number state) and
-        `num_total_changes` (changes of the per-clone totals).  Entry k is the probability of exactly k changes, the
-        last entry that of bins - 1 or more.  Changes are counted between consecutive model segments: a path that takes a
-        third state in a zero-length segment inserted at a shared boundary changes twice there."""
-        from . import posteriors
-        if not hasattr(self.model, 'region_counts'):
-            raise NotImplementedError('kernel module %s has no region change counts' % getattr(self._kernel_module(), '__name__', '?'))
-        out = posteriors.batch_region_change_counts(self.model._batch, self.model._r, 1, regions, self.seg_fwd_remap, self.seg_is_original,
-                                                    self.is_telomere, bins=bins)
-        return dict((k, v[0]) for k, v in out.items())
-
-    def region_cn_extremes(self, regions, quantity='total', clone='any', bins=16, first_level=0):
-        """Exact posterior distribution, under the structured posterior of the last variational update, of the highest and of
-        the lowest copy number inside regions ((first, last) experiment segment indices): is the region amplified, how high
-        does it go, how deep is its deepest loss.  quantity: 'total', 'major' or 'minor'; clone: a tumour clone 1 .. M-1 or
-        'any'; the window of copy numbers is first_level .. first_level + bins - 1.  A dict of `bins`, `first_level`, arrays
-        (len(regions), bins) `peak_cdf`, `peak_pmf`, `floor_cdf` (P(lowest >= k)) and `floor_pmf`, and int arrays
-        (len(regions),) `peak_q05/q50/q95` and `floor_q05/q50/q95` (posteriors.batch_region_cn_extremes;
-        posteriors.amplification_prob gives P(peak >= threshold))."""
-        from . import posteriors
-        if not hasattr(self.model, 'region_extremes'):
-            raise NotImplementedError('kernel module %s has no region extremes' % getattr(self._kernel_module(), '__name__', '?'))
-        out = posteriors.batch_region_cn_extremes(self.model._batch, self.model._r, 1, regions, self.seg_fwd_remap, self.seg_is_original,
-                                                  self.is_telomere, quantity=quantity, clone=clone, bins=bins, first_level=first_level)
-        return dict((k, v[0] if isinstance(v, np.ndarray) else v) for k, v in out.items())
-
-    def region_clone_extremes(self, regions, bins=16):
-        """The distributions of the peak and of the lowest total copy number of every tumour clone over regions, from one
-        device call: a dict of `peak_total_pmf` and `floor_total_pmf`, (len(regions), M - 1, bins) each, window 0 .. bins - 1
-        (what config cn_region_extremes adds to a fit result)."""
-        from . import posteriors
-        if not hasattr(self.model, 'region_extremes'):
-            raise NotImplementedError('kernel module %s has no region extremes' % getattr(self._kernel_module(), '__name__', '?'))
-        out = posteriors.batch_clone_extremes(self.model._batch, self.model._r, 1, regions, self.seg_fwd_remap, self.seg_is_original,
-                                              self.is_telomere, bins=bins)
-        return dict((k, v[0]) for k, v in out.items())
-
-    def region_cn_moments(self, regions):
-        """Exact posterior mean and covariance, under the structured posterior of the last variational update, of copy
-        number over regions ((first, last) experiment segment indices): a dict of `length` (R,), `total_cn_mean` (R, M) and
-        `total_cn_cov` (R, M, M) -- the length-weighted mean total copy number of each clone over the region, with the
-        covariance matrix that the correlation between neighbouring segments gives it -- and `fraction_mean` (R, 4) and
-        `fraction_cov` (R, 4, 4) of the length fractions of posteriors.MOMENT_FRACTIONS.  Zero-length segments inserted at
-        shared boundaries have no weight; a region of length 0 gives NaN."""
-        from . import posteriors
-        if not hasattr(self.model, 'region_moments'):
-            raise NotImplementedError('kernel module %s has no region moments' % getattr(self._kernel_module(), '__name__', '?'))
-        out = posteriors.batch_region_cn_moments(self.model._batch, self.model._r, 1, regions, self.seg_fwd_remap, self.seg_is_original,
-                                                 self.is_telomere, self.l1)
-        return dict((k, v if k == 'length' else v[0]) for k, v in out.items())
-
-    def event_extent(self, anchors, event, window=64):
-        """Where a copy-number event begins and ends around anchor segments, exactly, under the structured posterior of the
-        last variational update: anchors are experiment segment indices, event a mask name of posteriors.MASK_NAMES ('loh':
-        the LOH run around the anchor), a label name of posteriors.LABEL_NAMES ('state' / 'total': the constant-state /
-        constant-total run around it) or a (mask, label) pair, window the number of model segments walked on each side (an
-        int or a (left, right) pair).  A list with one posteriors.extent_summary dict per anchor: p_event, the survival
-        curves of both ends, the boundary pmfs with their censored mass, and the 5 / 50 / 95 % quantiles of each boundary as
-        experiment segment indices."""
-        from . import posteriors
-        if not hasattr(self.model, 'region_extent'):
-            raise NotImplementedError('kernel module %s has no event extents' % getattr(self._kernel_module(), '__name__', '?'))
-        return posteriors.batch_event_extents(self.model._batch, self.model._r, 1, anchors, event, window, self.seg_fwd_remap,
-                                              self.seg_is_original, self.is_telomere)[0]
-
-    def conditional_summary(self, regions, event, window='chain', cn=None, marginals=False):
-        """"Suppose it is so: what follows?"  Exact per-segment posterior summaries given that a copy-number event holds over a
-        region, under the structured posterior of the last variational update: regions is a list of (first, last) experiment
-        segment indices, each an evidence of its own; event a mask name of posteriors.MASK_NAMES ('hdel': every segment of the
-        region is homozygously deleted), a label name of posteriors.LABEL_NAMES, a (mask, label) pair, or a boolean
-        (classes, states) table of the states the evidence allows; window 'chain' (the whole chain of the region) or the number
-        of model segments on either side.  One dict per region: `log_evidence`, the log-probability of the event, and the
-        arrays of posterior_summary without the entropy, in experiment segment order, NaN outside the window.  cn: a decoded
-        path ([N][M][2], model segment order), which supplies cn_posterior_prob given the event.
-        posteriors.evidence_shift compares a dict with posterior_summary()."""
-        from . import posteriors
-        if not hasattr(self.model, 'region_conditional'):
-            raise NotImplementedError('kernel module %s has no conditional summaries' % getattr(self._kernel_module(), '__name__', '?'))
-        b = self.model._batch
-        states = None if cn is None else posteriors.cn_to_states(cn, b.cn_classes, b.seg_class)[None]
-        return posteriors.batch_conditional_summary(b, self.model._r, 1, regions, event, window, self.seg_fwd_remap, self.seg_is_original,
-                                                    self.is_telomere, marginals=marginals, states=states)[0]
-
-    def event_span(self, anchors, event, window=64):
-        """The joint law of where a copy-number event begins and ends around anchor segments, and so of its length, exactly,
-        under the structured posterior of the last variational update; anchors, event and window as event_extent (the
-        window's table may hold at most 16 384 entries).  A list with one posteriors.span_summary dict per anchor: p_event,
-        the joint survival function and pmf of (left end, right end), the length of every cell in the units of the segment
-        lengths, the 5 / 50 / 95 % quantiles of the length and its distribution function."""
-        from . import posteriors
-        if not hasattr(self.model, 'region_span'):
-            raise NotImplementedError('kernel module %s has no event spans' % getattr(self._kernel_module(), '__name__', '?'))
-        return posteriors.batch_event_spans(self.model._batch, self.model._r, 1, anchors, event, window, self.seg_fwd_remap,
-                                            self.seg_is_original, self.is_telomere, self.l1)[0]
-
-    def _pattern_batch(self):
-        if not hasattr(self.model, 'region_pattern'):
-            raise NotImplementedError('kernel module %s has no region event patterns' % getattr(self._kernel_module(), '__name__', '?'))
-        return self.model._batch, self.model._r
-
-    def event_joint(self, patterns):
-        """The exact joint probability, under the structured posterior of the last variational update, of copy-number events
-        at several regions: patterns is a list of patterns, each a list of parts (first, last, event) -- experiment segment
-        indices and an event as event_extent takes it.  A dict of `log_p_joint`, `p_joint` and `lift` (len(patterns),) and
-        `p_parts`, a list of (parts,) arrays: each part alone; lift = p_joint / prod p_parts.  Parts in different chains are
-        independent; inside one chain nothing binds between the parts."""
-        from . import posteriors
-        b, r = self._pattern_batch()
-        out = posteriors.batch_event_joint(b, r, 1, patterns, self.seg_fwd_remap, self.seg_is_original, self.is_telomere)
-        return dict((k, [x[0] for x in v] if k == 'p_parts' else v[0]) for k, v in out.items())
-
-    def focal_events(self, regions, flank=1):
-        """Exact probabilities of focal events over regions ((first, last) experiment segment indices): a dict of arrays
-        (len(regions),), p_focal_loh -- every segment of the region in LOH and none of the `flank` segments on each side of
-        it, inside the chain --, p_focal_hdel and p_focal_subclonal likewise.  A side without segments drops out."""
-        from . import posteriors
-        b, r = self._pattern_batch()
-        out = posteriors.batch_focal_events(b, r, 1, regions, flank, self.seg_fwd_remap, self.seg_is_original, self.is_telomere)
-        return dict((k, v[0]) for k, v in out.items())
-
-    def breakend_changes(self, arrays=False):
-        """Whether the copy-number state changes at the two breakends of every breakpoint, jointly and exactly
-        (posteriors.batch_breakend_changes): keyed like breakpoint_prob(), a dict breakpoint -> dict of p_change (2,),
-        p_change_both, p_change_neither, p_change_only_first, p_change_only_second, log_p_same (2,) and log_p_same_both;
-        arrays=True: the dict of arrays over breakpoints instead, (K, 2) and (K,)."""
-        from . import posteriors
-        b, r = self._pattern_batch()
-        out = posteriors.batch_breakend_changes(b, r, 1, self.breakpoint_idx, self.num_breakpoints, self.is_telomere, self.seg_is_original)
-        out = dict((k, v[0]) for k, v in out.items())
-        return out if arrays else dict((bp, dict((k, v[i]) for k, v in out.items())) for i, bp in enumerate(self.breakpoints))
-
-    def region_call(self, regions, event=None, cn=None):
-        """The most probable copy-number configuration of every region under the structured posterior of the last
-        variational update, and its probability (posteriors.batch_region_calls): regions is a list of (first, last)
-        experiment segment indices; event None, or (mask name or None, label name or None) -- the most probable
-        configuration in which the event holds, e.g. ('hdel', None).  A dict of `cn`, a list over regions of (segments, M, 2)
-        arrays, and arrays (len(regions),): log_prob, log_p_event, log_prob_given_event, and against the call cn ((N, M, 2)
-        in experiment order; None: the decoded path) n_differ and log_prob_call."""
-        from . import posteriors
-        if not hasattr(self.model, 'region_decode'):
-            raise NotImplementedError('kernel module %s has no region decode' % getattr(self._kernel_module(), '__name__', '?'))
-        b, r, states, single = self._call_states(cn)
-        if not single:
-            raise ValueError('region_call takes one call of shape (num_segments, num_clones, 2)')
-        out = posteriors.batch_region_calls(b, r, 1, regions, self.seg_fwd_remap, self.seg_is_original, self.is_telomere, event=event, cn=states)
-        return dict((k, v[0]) for k, v in out.items())
-
-    def region_alternatives(self, regions, k=4, event=None, cn=None):
-        """The k most probable copy-number configurations of every region under the structured posterior of the last
-        variational update (posteriors.batch_region_alternatives): what else could be there besides region_call's answer, and
-        how much of the mass the list explains.  regions, event and cn as region_call; 1 <= k <= 8.  A list over regions of
-        dicts: cn (a list over the found ranks of (segments, M, 2) arrays), log_prob (k,), log_p_event, log_prob_given_event
-        (k,), coverage, n_differ (k,), rank_of_call and duplicate_of (k,)."""
-        from . import posteriors
-        if not hasattr(self.model, 'region_kbest'):
-            raise NotImplementedError('kernel module %s has no region alternatives' % getattr(self._kernel_module(), '__name__', '?'))
-        b, r, states, single = self._call_states(cn)
-        if not single:
-            raise ValueError('region_alternatives takes one call of shape (num_segments, num_clones, 2)')
-        return posteriors.batch_region_alternatives(b, r, 1, regions, self.seg_fwd_remap, self.seg_is_original, self.is_telomere, k=k, event=event,
-                                                    cn=states)[0]
-
     def ploidy_posterior_sd(self):
         """The exact posterior SD of the tumour ploidy whose mean is stats['ploidy_posterior_mean']: the whole genome as one
         region of region_cn_moments (posteriors.moment_stats)."""
-        from . import posteriors
         mom = self.region_cn_moments([(0, len(self.seg_fwd_remap) - 1)])
         return posteriors.moment_stats(*[mom[k][0] for k in posteriors.MOMENT_ARRAYS[1:]])['ploidy_posterior_sd']
 
     def _call_states(self, cn):
-        """(batch, restart, states (K, N1) in model order, whether cn was one path) of a call `cn` in experiment order
-        ((N, M, 2) or (K, N, M, 2)); None: the decoded path."""
-        from . import posteriors
-        if not hasattr(self.model, 'call_logprob'):
-            raise NotImplementedError('kernel module %s has no call probabilities' % getattr(self._kernel_module(), '__name__', '?'))
+        """States (K, N1) in model segment order of a call `cn` in experiment order ((N, M, 2): K = 1, or (K, N, M, 2));
+        None: the decoded path."""
         b = self.model._batch
         if cn is None:
             path = np.zeros((self.model.num_segments, self.model.num_clones, self.model.num_alleles), dtype=int)
             self.model.infer_cn(path)
-            return b, self.model._r, posteriors.cn_to_states(path, b.cn_classes, b.seg_class)[None], True
+            return posteriors.cn_to_states(path, b.cn_classes, b.seg_class)[None]
         cn = np.asarray(cn)
-        single = cn.ndim == 3
-        states = np.stack([posteriors.states_in_model_order(c, b, self.seg_fwd_remap) for c in (cn[None] if single else cn)])
-        return b, self.model._r, states, single
-
-    def call_confidence(self, regions, cn=None):
-        """Exact probabilities, under the structured posterior of the last variational update, that the copy-number path
-        agrees with a call over regions ((first, last) experiment segment indices): a dict of arrays (len(regions),),
-        p_call (the path equals the call at every segment of the region), p_call_unphased (up to a swap of the two alleles)
-        and p_call_total (the per-clone totals).  cn: the call, (N, M, 2) in experiment segment order as optimal_cn returns
-        it; None: the decoded path.  Zero-length segments inserted at shared boundaries are marginalised."""
-        from . import posteriors
-        b, r, states, single = self._call_states(cn)
-        if not single:
-            raise ValueError('call_confidence takes one call of shape (num_segments, num_clones, 2)')
-        out = posteriors.batch_call_confidence(b, r, 1, states, regions, self.seg_fwd_remap, self.seg_is_original, self.is_telomere)
-        return dict((k, v[0]) for k, v in out.items())
-
-    def cn_logprob(self, cn=None):
-        """log q(cn) under the structured posterior of the last variational update: the exact log-probability of a whole
-        copy-number path, a float -- or (K,) for cn of shape (K, N, M, 2).  cn in experiment segment order as optimal_cn
-        returns it; None: the decoded path.  Zero-length segments inserted at shared boundaries are marginalised.  -inf
-        also where a state's forward entry underflowed in the sweep."""
-        from . import posteriors
-        b, r, states, single = self._call_states(cn)
-        out = posteriors.batch_cn_logprob(b, r, 1, states[None], self.seg_is_original, self.is_telomere)[0]
-        return float(out[0]) if single else out
-
-    def cn_change_prob(self):
-        """(N - 1,): the posterior probability that the copy-number state changes between experiment segments n and n + 1
-        (1 - p_no_change of the region [n, n + 1]); NaN where no reference adjacency joins them."""
-        from . import posteriors
-        b, r = self._region_batch()
-        return posteriors.batch_change_prob(b, r, 1, self.seg_fwd_remap, self.seg_is_original, self.is_telomere)[0]
+        return np.stack([posteriors.states_in_model_order(c, b, self.seg_fwd_remap) for c in (cn[None] if cn.ndim == 3 else cn)])
 
     def breakpoint_prob(self):
         return dict(zip(self.breakpoints, np.asarray(self.model.p_breakpoint)))

@@ -13,7 +13,8 @@ import os
 import numpy as np
 
 from .cn_model import BreakpointModel
-from . import outputs, posteriors, synthetic
+from . import outputs, posteriors, queries, synthetic
+from .queries import _join      # (the groups' join, under its name here too)
 
 
 class SampleList(object):
@@ -35,6 +36,7 @@ class SampleList(object):
         return self.n
 
 
+@queries.answers('set')      # the posterior queries come from the table of queries.py
 class RestartSet(object):
     """R restarts of one experiment advancing in lockstep on one device."""
 
@@ -645,62 +647,6 @@ class RestartSet(object):
         states = self.batch.sample_states(0, len(self.models), num_samples, seeds)
         return [self.batch.states_to_cn(states[r])[:, m.seg_fwd_remap] for r, m in enumerate(self.models)]
 
-    def posterior_summary(self, cn=None, marginals=False):
-        """Exact posterior summaries of every restart (BreakpointModel.posterior_summary): a list of dicts of arrays in
-        experiment segment order, from one device call for the whole batch.  cn: the restarts' decoded paths in
-        experiment order (the `cn` of results()), which supply cn_posterior_prob; None leaves that key out."""
-        from . import posteriors
-        if self.batch is None or not hasattr(self.batch, 'posterior_summary_raw'):
-            if cn is not None:
-                raise NotImplementedError('posterior summaries against a decoded path need the batched kernel module')
-            return [m.posterior_summary(marginals=marginals) for m in self.models]
-        b, R = self.batch, len(self.models)
-        states = None
-        if cn is not None:
-            states = np.stack([posteriors.states_in_model_order(cn[r], b, m.seg_fwd_remap) for r, m in enumerate(self.models)])
-        out = posteriors.batch_summaries(b, 0, R, states=states, marginals=marginals)
-        return [dict((k, v[m.seg_fwd_remap]) for k, v in s.items()) for s, m in zip(out, self.models)]
-
-    def region_events(self, regions):
-        """BreakpointModel.region_events of every restart from one device call: a dict of arrays (restarts, len(regions))."""
-        from . import posteriors
-        if self.batch is None or not hasattr(self.batch, 'region_logprob_raw'):
-            per = [m.region_events(regions) for m in self.models]
-            return dict((k, np.stack([p[k] for p in per])) for k in posteriors.REGION_ARRAYS)
-        m = self.models[0]
-        return posteriors.batch_region_events(self.batch, 0, len(self.models), regions, m.seg_fwd_remap, m.seg_is_original, m.is_telomere)
-
-    def region_change_counts(self, regions, bins=8):
-        """BreakpointModel.region_change_counts of every restart from one device call: a dict of arrays
-        (restarts, len(regions), bins)."""
-        from . import posteriors
-        if self.batch is None or not hasattr(self.batch, 'region_counts_raw'):
-            per = [m.region_change_counts(regions, bins) for m in self.models]
-            return dict((k, np.stack([p[k] for p in per])) for k in posteriors.COUNT_ARRAYS)
-        m = self.models[0]
-        return posteriors.batch_region_change_counts(self.batch, 0, len(self.models), regions, m.seg_fwd_remap, m.seg_is_original, m.is_telomere,
-                                                     bins=bins)
-
-    def region_cn_extremes(self, regions, quantity='total', clone='any', bins=16, first_level=0):
-        """BreakpointModel.region_cn_extremes of every restart from one device call: `bins`, `first_level` and arrays
-        (restarts, len(regions), ...)."""
-        from . import posteriors
-        if self.batch is None or not hasattr(self.batch, 'region_extremes_raw'):
-            per = [m.region_cn_extremes(regions, quantity, clone, bins, first_level) for m in self.models]
-            return dict((k, np.stack([p[k] for p in per]) if isinstance(v, np.ndarray) else v) for k, v in per[0].items())
-        m = self.models[0]
-        return posteriors.batch_region_cn_extremes(self.batch, 0, len(self.models), regions, m.seg_fwd_remap, m.seg_is_original, m.is_telomere,
-                                                   quantity=quantity, clone=clone, bins=bins, first_level=first_level)
-
-    def region_clone_extremes(self, regions, bins=16):
-        """BreakpointModel.region_clone_extremes of every restart from one device call: arrays (restarts, len(regions), M - 1, bins)."""
-        from . import posteriors
-        if self.batch is None or not hasattr(self.batch, 'region_extremes_raw'):
-            per = [m.region_clone_extremes(regions, bins) for m in self.models]
-            return dict((k, np.stack([p[k] for p in per])) for k in posteriors.EXTREME_ARRAYS)
-        m = self.models[0]
-        return posteriors.batch_clone_extremes(self.batch, 0, len(self.models), regions, m.seg_fwd_remap, m.seg_is_original, m.is_telomere, bins=bins)
-
     def restart_overlap(self, regions=None, pairs=None, clone_maps='all'):
         """The exact overlap between the restarts' structured posteriors (posteriors.restart_overlap): for every
         pair (default all i < j) and every order of the tumour clones, the log Bhattacharyya overlap and the log probability
@@ -708,110 +654,6 @@ class RestartSet(object):
         Hellinger distance of every region at it, and the per-segment distance rate to cluster on (posteriors.cluster_restarts)."""
         from . import posteriors
         return posteriors.restart_overlap([self.batch], [len(self.models)], self.models[0], regions, pairs, clone_maps)
-
-    def region_cn_moments(self, regions):
-        """BreakpointModel.region_cn_moments of every restart from one device call per feature group: a dict of `length`
-        (len(regions),) and arrays (restarts, len(regions), ...)."""
-        from . import posteriors
-        if self.batch is None or not hasattr(self.batch, 'region_moments_raw'):
-            per = [m.region_cn_moments(regions) for m in self.models]
-            return dict((k, per[0][k] if k == 'length' else np.stack([p[k] for p in per])) for k in posteriors.MOMENT_ARRAYS)
-        m = self.models[0]
-        return posteriors.batch_region_cn_moments(self.batch, 0, len(self.models), regions, m.seg_fwd_remap, m.seg_is_original, m.is_telomere, m.l1)
-
-    def event_extent(self, anchors, event, window=64):
-        """BreakpointModel.event_extent of every restart from one device call: a list over restarts of lists of
-        posteriors.extent_summary dicts, one per anchor."""
-        from . import posteriors
-        if self.batch is None or not hasattr(self.batch, 'region_extent_raw'):
-            return [m.event_extent(anchors, event, window) for m in self.models]
-        m = self.models[0]
-        return posteriors.batch_event_extents(self.batch, 0, len(self.models), anchors, event, window, m.seg_fwd_remap, m.seg_is_original,
-                                              m.is_telomere)
-
-    def conditional_summary(self, regions, event, window='chain', cn=None, marginals=False):
-        """BreakpointModel.conditional_summary of every restart from one device call: a list over restarts of lists over
-        regions.  cn: the restarts' decoded paths in experiment order (the `cn` of results()), or None."""
-        from . import posteriors
-        if self.batch is None or not hasattr(self.batch, 'region_conditional_raw'):
-            if cn is not None:
-                raise NotImplementedError('conditional summaries against a decoded path need the batched kernel module')
-            return [m.conditional_summary(regions, event, window, marginals=marginals) for m in self.models]
-        b, m = self.batch, self.models[0]
-        states = None
-        if cn is not None:
-            states = np.stack([posteriors.states_in_model_order(cn[r], b, mm.seg_fwd_remap) for r, mm in enumerate(self.models)])
-        return posteriors.batch_conditional_summary(b, 0, len(self.models), regions, event, window, m.seg_fwd_remap, m.seg_is_original, m.is_telomere,
-                                                    marginals=marginals, states=states)
-
-    def event_span(self, anchors, event, window=64):
-        """BreakpointModel.event_span of every restart from one device call: a list over restarts of lists of
-        posteriors.span_summary dicts, one per anchor."""
-        from . import posteriors
-        if self.batch is None or not hasattr(self.batch, 'region_span_raw'):
-            return [m.event_span(anchors, event, window) for m in self.models]
-        m = self.models[0]
-        return posteriors.batch_event_spans(self.batch, 0, len(self.models), anchors, event, window, m.seg_fwd_remap, m.seg_is_original,
-                                            m.is_telomere, m.l1)
-
-    def _pattern_fallback(self):
-        return self.batch is None or not hasattr(self.batch, 'region_pattern_raw')
-
-    def event_joint(self, patterns):
-        """BreakpointModel.event_joint of every restart from one device call per kernel: a dict of arrays (restarts, len(patterns))
-        and `p_parts`, a list over patterns of (restarts, parts) arrays."""
-        from . import posteriors
-        if self._pattern_fallback():
-            per = [m.event_joint(patterns) for m in self.models]
-            out = dict((k, np.stack([p[k] for p in per])) for k in ('log_p_joint', 'p_joint', 'lift'))
-            out['p_parts'] = [np.stack([p['p_parts'][i] for p in per]) for i in range(len(per[0]['p_parts']))]
-            return out
-        m = self.models[0]
-        return posteriors.batch_event_joint(self.batch, 0, len(self.models), patterns, m.seg_fwd_remap, m.seg_is_original, m.is_telomere)
-
-    def focal_events(self, regions, flank=1):
-        """BreakpointModel.focal_events of every restart from one device call: a dict of arrays (restarts, len(regions))."""
-        from . import posteriors
-        if self._pattern_fallback():
-            per = [m.focal_events(regions, flank) for m in self.models]
-            return dict((k, np.stack([p[k] for p in per])) for k in posteriors.FOCAL_ARRAYS)
-        m = self.models[0]
-        return posteriors.batch_focal_events(self.batch, 0, len(self.models), regions, flank, m.seg_fwd_remap, m.seg_is_original, m.is_telomere)
-
-    def breakend_changes(self, arrays=False):
-        """BreakpointModel.breakend_changes of every restart from one device call per kernel: keyed by the breakpoints, a dict
-        breakpoint -> dict of arrays with a leading restart axis; arrays=True: the dict of arrays (restarts, K, 2) and
-        (restarts, K)."""
-        from . import posteriors
-        m = self.models[0]
-        if self._pattern_fallback():
-            per = [x.breakend_changes(arrays=True) for x in self.models]
-            out = dict((k, np.stack([p[k] for p in per])) for k in per[0])
-        else:
-            out = posteriors.batch_breakend_changes(self.batch, 0, len(self.models), m.breakpoint_idx, m.num_breakpoints, m.is_telomere, m.seg_is_original)
-        return out if arrays else dict((bp, dict((k, v[:, i]) for k, v in out.items())) for i, bp in enumerate(m.breakpoints))
-
-    def region_call(self, regions, event=None, cn=None):
-        """BreakpointModel.region_call of every restart from one device call per kernel: `cn` a list over restarts of lists over
-        regions, the arrays (restarts, len(regions)).  cn: the restarts' calls in experiment order (the `cn` of results());
-        None: the decoded paths."""
-        from . import posteriors
-        if self.batch is None or not hasattr(self.batch, 'region_decode_raw'):
-            per = [m.region_call(regions, event, None if cn is None else cn[r]) for r, m in enumerate(self.models)]
-            return dict((k, [p[k] for p in per] if k == 'cn' else np.stack([p[k] for p in per])) for k in per[0])
-        m = self.models[0]
-        return posteriors.batch_region_calls(self.batch, 0, len(self.models), regions, m.seg_fwd_remap, m.seg_is_original, m.is_telomere,
-                                             event=event, cn=self._call_states(cn))
-
-    def region_alternatives(self, regions, k=4, event=None, cn=None):
-        """BreakpointModel.region_alternatives of every restart from one device call per kernel: a list over restarts of lists
-        over regions of dicts.  cn: the restarts' calls in experiment order (the `cn` of results()); None: the decoded paths."""
-        from . import posteriors
-        if self.batch is None or not hasattr(self.batch, 'region_kbest_raw'):
-            return [m.region_alternatives(regions, k, event, None if cn is None else cn[r]) for r, m in enumerate(self.models)]
-        m = self.models[0]
-        return posteriors.batch_region_alternatives(self.batch, 0, len(self.models), regions, m.seg_fwd_remap, m.seg_is_original, m.is_telomere,
-                                                    k=k, event=event, cn=self._call_states(cn))
 
     def _call_states(self, cn):
         """int16 (restarts, N1): the restarts' calls as state indices in model segment order.  cn: their paths in
@@ -823,55 +665,8 @@ class RestartSet(object):
             return posteriors.cn_to_states(cn_all, b.cn_classes, b.seg_class)
         return np.stack([posteriors.states_in_model_order(cn[r], b, m.seg_fwd_remap) for r, m in enumerate(self.models)])
 
-    def call_confidence(self, regions, cn=None):
-        """BreakpointModel.call_confidence of every restart from one device call: a dict of arrays (restarts, len(regions)).
-        cn: the restarts' calls in experiment order (the `cn` of results()); None: the decoded paths."""
-        from . import posteriors
-        if self.batch is None or not hasattr(self.batch, 'call_logprob_raw'):
-            per = [m.call_confidence(regions, None if cn is None else cn[r]) for r, m in enumerate(self.models)]
-            return dict((k, np.stack([p[k] for p in per])) for k in posteriors.CALL_ARRAYS)
-        m = self.models[0]
-        return posteriors.batch_call_confidence(self.batch, 0, len(self.models), self._call_states(cn), regions, m.seg_fwd_remap,
-                                                m.seg_is_original, m.is_telomere)
 
-    def cn_logprob(self, cn=None):
-        """BreakpointModel.cn_logprob of every restart from one device call: (restarts,).  cn: the restarts' paths in
-        experiment order (the `cn` of results()); None: the decoded paths."""
-        from . import posteriors
-        if self.batch is None or not hasattr(self.batch, 'call_logprob_raw'):
-            return np.array([m.cn_logprob(None if cn is None else cn[r]) for r, m in enumerate(self.models)])
-        m = self.models[0]
-        return posteriors.batch_cn_logprob(self.batch, 0, len(self.models), self._call_states(cn)[:, None], m.seg_is_original, m.is_telomere)[:, 0]
-
-    def cn_change_prob(self):
-        """BreakpointModel.cn_change_prob of every restart from one device call: (restarts, N - 1)."""
-        from . import posteriors
-        if self.batch is None or not hasattr(self.batch, 'region_logprob_raw'):
-            return np.stack([m.cn_change_prob() for m in self.models])
-        m = self.models[0]
-        return posteriors.batch_change_prob(self.batch, 0, len(self.models), m.seg_fwd_remap, m.seg_is_original, m.is_telomere)
-
-
-def _join(parts, shared=(), extend=(), each=()):
-    """One query's results from several groups of restarts, as of all their restarts in order.  Lists over restarts are
-    strung together.  Of dicts, the arrays are concatenated along the restart axis, except the keys named in `shared` (the
-    same in every part: the first part's), in `extend` (lists over restarts: strung together) and in `each` (lists of arrays
-    with a restart axis: concatenated entry by entry)."""
-    if not isinstance(parts[0], dict):
-        return [x for part in parts for x in part]
-
-    def one(k):
-        values = [part[k] for part in parts]
-        if k in shared:
-            return values[0]
-        if k in extend:
-            return [x for v in values for x in v]
-        if k in each:
-            return [np.concatenate(v) for v in zip(*values)]
-        return np.concatenate(values)
-    return dict((k, one(k)) for k in parts[0])
-
-
+@queries.answers('groups')      # the posterior queries come from the table of queries.py
 class RestartGroups(object):
     """The restarts of one GPU split into `groups` RestartSets, each with its own device batch
     (own HIP stream) and its own host thread.
@@ -997,81 +792,12 @@ class RestartGroups(object):
         ids = list(range(self.num_restarts)) if init_ids is None else list(init_ids)
         return _join(self._map(lambda rs: rs.sample_cn(num_samples, seed, self._own(rs, ids))))
 
-    def posterior_summary(self, cn=None, marginals=False):
-        """RestartSet.posterior_summary over the groups, restarts in order (cn: of all restarts)."""
-        return _join(self._map(lambda rs: rs.posterior_summary(self._own(rs, cn), marginals)))
-
-    def region_events(self, regions):
-        """RestartSet.region_events over the groups, restarts in order: a dict of arrays (restarts, len(regions))."""
-        return _join(self._map(lambda rs: rs.region_events(regions)))
-
-    def region_change_counts(self, regions, bins=8):
-        """RestartSet.region_change_counts over the groups, restarts in order: a dict of arrays (restarts, len(regions), bins)."""
-        return _join(self._map(lambda rs: rs.region_change_counts(regions, bins)))
-
-    def region_cn_extremes(self, regions, quantity='total', clone='any', bins=16, first_level=0):
-        """RestartSet.region_cn_extremes over the groups, restarts in order: `bins`, `first_level` and arrays (restarts, len(regions), ...)."""
-        return _join(self._map(lambda rs: rs.region_cn_extremes(regions, quantity, clone, bins, first_level)), shared=('bins', 'first_level'))
-
-    def region_clone_extremes(self, regions, bins=16):
-        """RestartSet.region_clone_extremes over the groups, restarts in order: arrays (restarts, len(regions), M - 1, bins)."""
-        return _join(self._map(lambda rs: rs.region_clone_extremes(regions, bins)))
-
     def restart_overlap(self, regions=None, pairs=None, clone_maps='all'):
         """RestartSet.restart_overlap over all restarts of all groups, restarts in order: a pair may straddle two groups (the call
         then reads both groups' batches).  The groups must be idle."""
         from . import posteriors
         self.synchronize()
         return posteriors.restart_overlap(self.batches, [len(rs.models) for rs in self.sets], self.models[0], regions, pairs, clone_maps)
-
-    def region_cn_moments(self, regions):
-        """RestartSet.region_cn_moments over the groups, restarts in order: `length` (len(regions),) and arrays (restarts, len(regions), ...)."""
-        return _join(self._map(lambda rs: rs.region_cn_moments(regions)), shared=('length',))
-
-    def event_extent(self, anchors, event, window=64):
-        """RestartSet.event_extent over the groups, restarts in order: a list over restarts of lists over anchors."""
-        return _join(self._map(lambda rs: rs.event_extent(anchors, event, window)))
-
-    def conditional_summary(self, regions, event, window='chain', cn=None, marginals=False):
-        """RestartSet.conditional_summary over the groups, restarts in order (cn: of all restarts): a list over restarts of lists over regions."""
-        return _join(self._map(lambda rs: rs.conditional_summary(regions, event, window, self._own(rs, cn), marginals)))
-
-    def event_span(self, anchors, event, window=64):
-        """RestartSet.event_span over the groups, restarts in order: a list over restarts of lists over anchors."""
-        return _join(self._map(lambda rs: rs.event_span(anchors, event, window)))
-
-    def event_joint(self, patterns):
-        """RestartSet.event_joint over the groups, restarts in order."""
-        return _join(self._map(lambda rs: rs.event_joint(patterns)), each=('p_parts',))
-
-    def focal_events(self, regions, flank=1):
-        """RestartSet.focal_events over the groups, restarts in order: a dict of arrays (restarts, len(regions))."""
-        return _join(self._map(lambda rs: rs.focal_events(regions, flank)))
-
-    def breakend_changes(self, arrays=False):
-        """RestartSet.breakend_changes over the groups, restarts in order."""
-        out = _join(self._map(lambda rs: rs.breakend_changes(arrays=True)))
-        return out if arrays else dict((bp, dict((k, v[:, i]) for k, v in out.items())) for i, bp in enumerate(self.sets[0].models[0].breakpoints))
-
-    def region_call(self, regions, event=None, cn=None):
-        """RestartSet.region_call over the groups, restarts in order (cn: of all restarts)."""
-        return _join(self._map(lambda rs: rs.region_call(regions, event, self._own(rs, cn))), extend=('cn',))
-
-    def region_alternatives(self, regions, k=4, event=None, cn=None):
-        """RestartSet.region_alternatives over the groups, restarts in order (cn: of all restarts)."""
-        return _join(self._map(lambda rs: rs.region_alternatives(regions, k, event, self._own(rs, cn))))
-
-    def call_confidence(self, regions, cn=None):
-        """RestartSet.call_confidence over the groups, restarts in order (cn: of all restarts): a dict of arrays (restarts, len(regions))."""
-        return _join(self._map(lambda rs: rs.call_confidence(regions, self._own(rs, cn))))
-
-    def cn_logprob(self, cn=None):
-        """RestartSet.cn_logprob over the groups, restarts in order (cn: of all restarts): (restarts,)."""
-        return np.concatenate(self._map(lambda rs: rs.cn_logprob(self._own(rs, cn))))
-
-    def cn_change_prob(self):
-        """RestartSet.cn_change_prob over the groups, restarts in order: (restarts, N - 1)."""
-        return np.concatenate(self._map(lambda rs: rs.cn_change_prob()))
 
     def profile(self):
         """{kernel: (ms, launches)} summed over the groups' batches."""
@@ -1085,6 +811,7 @@ class RestartGroups(object):
         return out
 
 
+@queries.answers('datasets')      # the posterior queries come from the table of queries.py
 class DatasetGroups(object):
     """Several datasets resident on one GPU at once (BASELINE configs[4]: the tumour samples of one patient share
     the segmentation and the breakpoints and are fitted independently, reference remixt/workflow.py:472-485): one
@@ -1165,80 +892,10 @@ class DatasetGroups(object):
         """RestartGroups.sample_cn of every dataset, dataset after dataset (restart indices within each dataset)."""
         return _join(self._map(lambda part: part.sample_cn(num_samples, seed)))
 
-    def posterior_summary(self, cn=None, marginals=False):
-        """RestartGroups.posterior_summary of every dataset, dataset after dataset (cn: per dataset, a list of its restarts' paths)."""
-        return _join(self._map(lambda part: part.posterior_summary(self._own(part, cn), marginals)))
-
-    def region_events(self, regions):
-        """RestartGroups.region_events of every dataset: a list, one dict of arrays (restarts, len(regions)) per dataset."""
-        return self._map(lambda part: part.region_events(regions))
-
-    def region_change_counts(self, regions, bins=8):
-        """RestartGroups.region_change_counts of every dataset: a list, one dict of arrays (restarts, len(regions), bins) per dataset."""
-        return self._map(lambda part: part.region_change_counts(regions, bins))
-
-    def region_cn_moments(self, regions):
-        """RestartGroups.region_cn_moments of every dataset: a list, one dict per dataset."""
-        return self._map(lambda part: part.region_cn_moments(regions))
-
-    def event_extent(self, anchors, event, window=64):
-        """RestartGroups.event_extent of every dataset: a list, one list over restarts per dataset."""
-        return self._map(lambda part: part.event_extent(anchors, event, window))
-
-    def conditional_summary(self, regions, event, window='chain', cn=None, marginals=False):
-        """RestartGroups.conditional_summary of every dataset: a list, one list over restarts per dataset (cn: per dataset)."""
-        return self._map(lambda part: part.conditional_summary(regions, event, window, self._own(part, cn), marginals))
-
-    def event_span(self, anchors, event, window=64):
-        """RestartGroups.event_span of every dataset: a list, one list over restarts per dataset."""
-        return self._map(lambda part: part.event_span(anchors, event, window))
-
-    def event_joint(self, patterns):
-        """RestartGroups.event_joint of every dataset: a list, one dict per dataset."""
-        return self._map(lambda part: part.event_joint(patterns))
-
-    def focal_events(self, regions, flank=1):
-        """RestartGroups.focal_events of every dataset: a list, one dict of arrays (restarts, len(regions)) per dataset."""
-        return self._map(lambda part: part.focal_events(regions, flank))
-
-    def breakend_changes(self, arrays=False):
-        """RestartGroups.breakend_changes of every dataset: a list, one dict per dataset."""
-        return self._map(lambda part: part.breakend_changes(arrays))
-
-    def region_cn_extremes(self, regions, quantity='total', clone='any', bins=16, first_level=0):
-        """RestartGroups.region_cn_extremes of every dataset: a list, one dict per dataset."""
-        return self._map(lambda part: part.region_cn_extremes(regions, quantity, clone, bins, first_level))
-
-    def region_clone_extremes(self, regions, bins=16):
-        """RestartGroups.region_clone_extremes of every dataset: a list, one dict per dataset."""
-        return self._map(lambda part: part.region_clone_extremes(regions, bins))
-
     def restart_overlap(self, regions=None, pairs=None, clone_maps='all'):
         """RestartGroups.restart_overlap of every dataset: a list, one dict per dataset (pairs stay within a dataset and
         count its restarts from 0)."""
         return self._map(lambda part: part.restart_overlap(regions, pairs, clone_maps))
-
-    def region_call(self, regions, event=None):
-        """RestartGroups.region_call of every dataset: a list, one dict per dataset."""
-        return self._map(lambda part: part.region_call(regions, event))
-
-    def region_alternatives(self, regions, k=4, event=None, cn=None):
-        """RestartGroups.region_alternatives of every dataset (cn: per dataset, a list of its restarts' paths): a list, one list
-        over restarts per dataset."""
-        return self._map(lambda part: part.region_alternatives(regions, k, event, self._own(part, cn)))
-
-    def call_confidence(self, regions, cn=None):
-        """RestartGroups.call_confidence of every dataset (cn: per dataset, a list of its restarts' paths): a list, one dict of arrays
-        (restarts, len(regions)) per dataset."""
-        return self._map(lambda part: part.call_confidence(regions, self._own(part, cn)))
-
-    def cn_logprob(self, cn=None):
-        """RestartGroups.cn_logprob of every dataset (cn: per dataset, a list of its restarts' paths): a list of (restarts,) arrays."""
-        return self._map(lambda part: part.cn_logprob(self._own(part, cn)))
-
-    def cn_change_prob(self):
-        """RestartGroups.cn_change_prob of every dataset: a list of (restarts, N - 1) arrays."""
-        return self._map(lambda part: part.cn_change_prob())
 
     def results_by_dataset(self):
         return self._map(lambda part: part.results())

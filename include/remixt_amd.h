@@ -625,6 +625,32 @@ int rmx_region_kbest(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int
                      int32_t nmask, const uint8_t *masks, int32_t nlabel, const int16_t *labels, const uint8_t *constrain,
                      int32_t K, int32_t max_len, int16_t *states_out, double *logp_out);
 
+/* Locus joints: the exact joint posterior of copy number at two loci of a chain.  Query i is (a, t, row level
+ * index, column level index): model segments a <= t of one chain and two of the level tables, levels int16 [C][nlevel][S]
+ * with every entry >= 0 (a per-state integer under the state class of a segment: a clone's total, a 0/1 event).  With post,
+ * fa, W_n and D_n as in rmx_region_prob,
+ *   G_t(s, j) = [level_col,t(s) = j] post_t(s),   G_n(s, j) = fa_n(s) sum_s' W_n(s, s') G_n+1(s', j) / D_n(s'),
+ *   cell(n; i, j) = log sum_{s: level_row,n(s) = i} G_n(s, j) = log P(level_row(c_n) = i and level_col(c_t) = j);
+ * nothing binds between the loci.  nrow and ncol lie in 1 .. 16; a state whose level is >= ncol (>= nrow) is in no column
+ * (row); an empty cell is -inf and is not an error.
+ *   nslot = 0    the pair form: logp_out [nr][nq][nrow][ncol] holds the table at n = a
+ *   nslot >= 1   the profile form: logp_out [nr][nq][nslot][nrow][ncol]; slot k holds the table at segment t - k for
+ *                k = 0 .. t - a, later slots are NaN.  nslot <= 4096, every query has t - a + 1 <= nslot
+ * Slot 0, and a pair with a = t, is log sum post_t(s) over the states that carry both levels.  max(nslot, 1) nrow ncol may
+ * not exceed 2^20.  Every column keeps its own scale and running logarithm and is divided by its own sum after every step, the
+ * start included (in real arithmetic that sum is 1: the division removes rounding drift).  Inside a column the rows share
+ * the scale: a cell more than about 1e-308 below its column's total comes out -inf.  An fa entry that underflowed to 0 in the
+ * sweep is a state the walk cannot pass.  The model is not modified.
+ * A cell is bit-identical in any restart range, any batch and order of queries, any chunking, for any nrow that contains it
+ * and any nslot; slot k of a profile query equals the pair form's table of (t - k, t) bit for bit.
+ * Errors: RMX_EARG with nothing launched and the output untouched for a bad restart range, nq < 1, a NULL pointer, nrow or
+ * ncol outside [1, 16], nlevel < 1, a level index out of range, a negative level entry, nslot outside [0, 4096], a profile
+ * query longer than nslot, segments outside the model, a > t or in two chains; RMX_EVALUE with the restarts listed before
+ * update_p_cn; RMX_EASSERT with the restarts listed for a normaliser D that is 0 or not finite under mass or a sum that is not
+ * a finite number >= 0: every cell of that query is NaN; RMX_EUNSUPPORTED above 1024 states.  The kernel has no profile id. */
+int rmx_locus_joint(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nlevel, const int16_t *levels,
+                    int32_t nrow, int32_t ncol, int32_t nslot, double *logp_out);
+
 /* -- module-level functions on caller-supplied dense inputs ----------------- */
 /* sum_product (:1213-1246): f [N][S], T [N-1][S][S] -> alphas, betas [N][S] */
 int rmx_sum_product(const double *f, const double *T, double *alphas, double *betas,

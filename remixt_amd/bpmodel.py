@@ -679,6 +679,22 @@ class RemixtBatch(object):
         self._ck(self._lib.rmx_region_extremes(self._handle, r0, nr, *args, ncol, obuf.ctypes.data_as(_dp)))
         return out
 
+    def locus_joint_raw(self, r0, nr, queries, levels, nrow, ncol, nslot=0):
+        """The exact joint posterior of two per-state integer levels at two model segments of one chain, under the structured
+        posterior of the last update_p_cn of restarts r0 .. r0+nr-1 (rmx_locus_joint).  queries int (nq, 4): segments a <= t,
+        row level index, column level index; levels int (C, nlevel, S), every entry >= 0.  nslot = 0: (nr, nq, nrow, ncol),
+        entry [i, j] = log P(level_row(c_a) = i and level_col(c_t) = j).  nslot >= 1: (nr, nq, nslot, nrow, ncol), slot k the
+        same table of segment t - k against t for k = 0 .. t - a, NaN in the later slots.  A state whose level is >= nrow
+        (>= ncol) is in no row (column); -inf for an empty cell.  nrow, ncol in 1 .. 16, nslot in 0 .. 4096."""
+        r0, nr, nrow, ncol, nslot = int(r0), int(nr), int(nrow), int(ncol), int(nslot)
+        q, args, _keep = self._region_args(queries, None, levels, None)
+        ok = 1 <= nrow <= 16 and 1 <= ncol <= 16 and 0 <= nslot <= 4096
+        shape = ((nslot,) if nslot >= 1 else ()) + (nrow, ncol)
+        out = np.zeros((max(nr, 0), q.shape[0]) + (shape if ok else (1, 1)), dtype=np.float64)
+        obuf = out if out.size else np.zeros(1)
+        self._ck(self._lib.rmx_locus_joint(self._handle, r0, nr, args[0], args[1], args[4], args[5], nrow, ncol, nslot, obuf.ctypes.data_as(_dp)))
+        return out
+
     def restart_overlap_raw(self, other, pairs, queries, perms, mode):
         """log Z (npairs, nq) of the structured posteriors of pairs of restarts over runs of model segments
         (rmx_restart_overlap): Z = sum_x q_A(x)^lam q_B(pi x)^mu, mode 0 the Bhattacharyya overlap (lam = mu = 1/2), mode 1 the
@@ -1127,6 +1143,10 @@ class RemixtModel(object):
     def region_extremes(self, queries, masks, levels, constrain, ncol):
         """RemixtBatch.region_extremes_raw of this model: log-probabilities (nq, ncol)."""
         return self._batch.region_extremes_raw(self._r, 1, queries, masks, levels, constrain, ncol)[0]
+
+    def locus_joint(self, queries, levels, nrow, ncol, nslot=0):
+        """RemixtBatch.locus_joint_raw of this model: log-probabilities (nq, nrow, ncol), or (nq, nslot, nrow, ncol)."""
+        return self._batch.locus_joint_raw(self._r, 1, queries, levels, nrow, ncol, nslot)[0]
 
     def region_moments(self, queries, features, weights, nf):
         """RemixtBatch.region_moments_raw of this model: means and covariances (nq, nf + nf (nf + 1) / 2)."""

@@ -63,7 +63,9 @@ enum LaterKernelId { KID_REGION_CONDITIONAL = KID_ALL, KID_PROFILE_ALL };
 static const char *kLaterKernelNames[KID_PROFILE_ALL - KID_ALL] = {"k_region_conditional"};
 // The third range is closed too (tests/test_conditional_posterior_cpu.py pins rmx_num_profile_ids() == rmx_num_kernels() + 1 with
 // k_region_conditional last, tests/test_hip_region_conditional.py pins RMX_EARG at rmx_num_profile_ids()): k_region_kbest has no
-// profile id.  Its launches run without a ProfScope; tools time it with rmx_timer_start / rmx_timer_stop.
+// profile id.  Its launches run without a ProfScope; tools time it with rmx_timer_start / rmx_timer_stop.  Nor has k_locus_joint:
+// it goes through run_queries with KID_NONE, under which run_queries opens no ProfScope.
+enum { KID_NONE = -1 };
 
 struct ProfRec { int id; hipEvent_t a, b; };
 
@@ -875,8 +877,11 @@ template <typename L> static int run_queries(rmx_batch *b, int r0, int nr, int n
         for (int rb = 0; rb < nr; rb += nrc) {
             const int nrr = std::min(nrc, nr - rb);
             rc = for_model_runs(b, r0, rb, rb + nrr, [&](int i, int j, int, const Dev &dv, int use_wb) -> int {
-                ProfScope ps(b, kid);
-                launch(dv, r0 + i, j - i, i, use_wb, dq, (int)nqc, dout + (size_t)(i - rb) * nqc * per, b->d_rflags);
+                if (kid == KID_NONE) launch(dv, r0 + i, j - i, i, use_wb, dq, (int)nqc, dout + (size_t)(i - rb) * nqc * per, b->d_rflags);      // (a kernel without a profile id)
+                else {
+                    ProfScope ps(b, kid);
+                    launch(dv, r0 + i, j - i, i, use_wb, dq, (int)nqc, dout + (size_t)(i - rb) * nqc * per, b->d_rflags);
+                }
                 HIPCHK(hipGetLastError());
                 return RMX_OK;
             });
@@ -3824,6 +3829,47 @@ int rmx_region_kbest(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int
     RgnArgs ra;
     if ((rc = stage_region_tables(b, nmask, masks, nlabel, labels, constrain, &ra))) return rc;
     return run_kbest(b, r0, nr, nq, queries, K, max_len, ra, states_out, logp_out);
+}
+
+// Locus joints (k_locus_joint): for every (restart, query) the table log P(level_row(c_a) = i, level_col(c_t) = j) of two
+// model segments a <= t of one chain (nslot = 0), or that table at every segment t, t - 1, .. a against t (nslot >= 1: slot k is
+// t - k, the slots past t - a are NaN).  Fields 2 and 3 of a query name the row and the column level table; the tables travel
+// where the label tables of the siblings do.  Everything is checked before anything is queued (check_queries: the two segments;
+// rmxh::locus_shape_ok, rmxh::check_locus_lengths, rmxh::check_levels), and no output is written on an error.  A (restart, query)
+// output is max(nslot, 1) nrow ncol doubles, 8 MiB at the most, and goes through run_queries' 64 MiB staging buffer: a chunk holds
+// as many pairs as fit it.  One workgroup computes a (restart, query) on its own, so a cell depends on neither the restart
+// range, the chunking, the other queries, nrow nor nslot.  The kernel has no profile id (KID_NONE).
+int rmx_locus_joint(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nlevel, const int16_t *levels,
+                    int32_t nrow, int32_t ncol, int32_t nslot, double *logp_out) { BIND(b);
+    int rc;
+    if ((rc = check_region_call(b, "locus_joint", r0, nr, nq, queries, logp_out))) return rc;
+    if (nrow < 1 || nrow > rmxh::LOCUS_MAX_LEVELS || ncol < 1 || ncol > rmxh::LOCUS_MAX_LEVELS) return fail(RMX_EARG, "locus_joint: the numbers of rows and of columns must be in [1, 16]");
+    if (nslot < 0 || nslot > rmxh::LOCUS_MAX_SLOTS) return fail(RMX_EARG, "locus_joint: nslot must be in [0, 4096]");
+    if (!rmxh::locus_shape_ok(nrow, ncol, nslot)) return fail(RMX_EARG, "locus_joint: a query's tables hold more than 1048576 entries");
+    if (nlevel < 1 || !levels) return fail(RMX_EARG, "locus_joint: no level tables");
+    if (b->d.S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "locus_joint: more than 1024 states");
+    if ((rc = check_queries(b, "locus_joint", nq, queries, {0, nlevel, "locus_joint: a query needs a row level index in [0, nlevel)"},
+                            {0, nlevel, "locus_joint: a query needs a column level index in [0, nlevel)"}))) return rc;
+    if (rmxh::check_levels(b->d.C, nlevel, b->d.S, levels) != -1) return fail(RMX_EARG, "locus_joint: a level entry is negative");
+    {
+        const char *why = nullptr;
+        const int64_t bad = rmxh::check_locus_lengths(nq, queries, nslot, &why);
+        if (bad >= 0) return fail(RMX_EARG, std::string("locus_joint: ") + why + " (query " + std::to_string(bad) + ")");
+    }
+    if ((rc = require_snapshot(b, r0, nr, "locus_joint"))) return rc;
+    RgnArgs ra;
+    if ((rc = stage_region_tables(b, 0, nullptr, nlevel, levels, nullptr, &ra))) return rc;
+    const size_t lds = rlj_lds_bytes(b->d.S);
+    const int tpw = tiles_per_wave(b->d.S);
+    auto kf = tpw == 3 ? k_locus_joint<3> : (tpw == 8 ? k_locus_joint<8> : k_locus_joint<16>);
+    if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const size_t per = (size_t)std::max(nslot, 1) * nrow * ncol;
+    const size_t max_pairs = std::max<size_t>(1, ((size_t)64 << 20) / (per * 8 + 16));      // a chunk's outputs and queries stay within the staging buffer
+    return run_queries(b, r0, nr, nq, queries, (int)per, KID_NONE, "locus_joint: a backward step has a zero or non-finite normaliser", logp_out,
+                       [&](const Dev &dv, int r, int n, int, int use_wb, const int32_t *dq, int nqc, double *out, uint32_t *flags) {
+        ra.queries = dq; ra.nq = nqc;
+        hipLaunchKernelGGL(kf, dim3((unsigned)nqc, n), dim3(RGN_NT), lds, b->stream, dv, r, use_wb, ra, (int)nrow, (int)ncol, (int)nslot, out, flags);
+    }, max_pairs);
 }
 
 #ifdef RMX_KBEST_COUNT

@@ -8,6 +8,7 @@
 //   decode_max_len_ok, check_decode_lengths, decode_plan  rmx_region_decode: the length rules and the chunks of a call
 //   kbest_k_ok, kbest_plan                                rmx_region_kbest: the rank rule and the chunks of a call
 //   extremes_ncol_ok, check_levels  rmx_region_extremes: the column rule, and that no level entry is negative
+//   locus_shape_ok, check_locus_lengths  rmx_locus_joint: the table and slot rule, and that a profile query fits its slots
 //   check_pairs, check_permutations  rmx_restart_overlap: the restart pairs lie inside the two batches, every permutation row is a bijection
 //   weighted_search      rmx_weighted_search: numpy's cumsum / searchsorted(side='right') for the weighted M-step samples
 //                        (reference remixt/cn_model.py:475-480)
@@ -218,6 +219,34 @@ inline int64_t check_levels(int64_t C, int64_t nlevel, int64_t S, const int16_t 
     if (n > 0 && !levels) return -2;
     for (uint64_t i = 0; i < n; i++) if (levels[i] < 0) return (int64_t)i;
     return -1;
+}
+
+// rmx_locus_joint.  Its shape rule: 1 <= nrow, ncol <= LOCUS_MAX_LEVELS (the 16 x 16 threads of an emission, the columns of the
+// matrix instruction's B operand), 0 <= nslot <= LOCUS_MAX_SLOTS (0: the pair form), and a (restart, query) output of
+// max(nslot, 1) nrow ncol <= LOCUS_MAX_ENTRIES doubles (no overflow for any int32 triple)
+constexpr int32_t LOCUS_MAX_LEVELS = 16;
+constexpr int32_t LOCUS_MAX_SLOTS = 4096;
+constexpr int64_t LOCUS_MAX_ENTRIES = (int64_t)1 << 20;
+inline bool locus_shape_ok(int32_t nrow, int32_t ncol, int32_t nslot) {
+    if (nrow < 1 || nrow > LOCUS_MAX_LEVELS || ncol < 1 || ncol > LOCUS_MAX_LEVELS || nslot < 0 || nslot > LOCUS_MAX_SLOTS) return false;
+    return (int64_t)std::max<int32_t>(nslot, 1) * nrow * ncol <= LOCUS_MAX_ENTRIES;
+}
+// every query [nq][4] = (a, t, .., ..) has a <= t, and in the profile form (nslot >= 1) t - a + 1 <= nslot: slot t - a is
+// the last one the kernel writes (no overflow for any int32 pair).  Returns the index of the first query that breaks a rule,
+// with *reason (a string literal), or -1
+inline int64_t check_locus_lengths(int32_t nq, const int32_t *queries, int32_t nslot, const char **reason) {
+    const char *why = nullptr;
+    int64_t bad = -1;
+    if (nq < 0 || (nq > 0 && !queries)) { why = "bad arguments"; bad = 0; }
+    else if (nslot < 0 || nslot > LOCUS_MAX_SLOTS) { why = "nslot must be in [0, 4096]"; bad = 0; }
+    for (int32_t i = 0; i < nq && !why; i++) {
+        const int64_t a = queries[4 * (size_t)i], t = queries[4 * (size_t)i + 1];
+        if (a > t) why = "a query needs first <= last";
+        else if (nslot >= 1 && t - a + 1 > (int64_t)nslot) why = "a profile query is longer than nslot";
+        if (why) bad = i;
+    }
+    if (reason) *reason = why;
+    return bad;
 }
 
 // rmx_restart_overlap.  Its pairs [npairs][2]: a restart of batch A in [0, RA) and one of batch B in [0, RB).  Returns the index

@@ -7421,6 +7421,206 @@ __global__ __launch_bounds__(RGN_NT) void k_region_decode(Dev d, int r0, int use
 }
 
 // =============================================================================
+// Locus joints: for a query (a, t, row level, column level) over two model segments a <= t of one chain, the table
+//   cell(n; i, j) = log P(level_row(c_n) = i and level_col(c_t) = j),   i < nrow, j < ncol,
+// of two per-state integer levels >= 0 under the state classes of n and t, at n = a (the pair form, nslot = 0) or at every
+// n = t, t - 1, .. a (the profile form: slot k is n = t - k; the slots past t - a are NaN).  It is k_region_extremes' multi-column
+// backward recursion with disjoint columns and nothing that binds on the walk: with G_t(s, j) = [level_col,t(s) = j] post_t(s)
+// and H(s', j) = G_n+1(s', j) / D_n(s'),
+//   G_n(s, j) = fa_n(s) sum_s' W_n(s, s') H(s', j),   cell(n; i, j) = log sum_{s: level_row,n(s) = i} G_n(s, j).
+// A state whose level is >= ncol (>= nrow) is in no column (row); an empty cell is -inf.  EVERY COLUMN is divided by its own sum
+// after every step, the start included, and keeps its own running logarithm; in real arithmetic that sum is 1 at every step
+// (nothing binds), so the division only removes rounding drift.  Inside a column the rows share the scale: a cell more than
+// about 1e-308 below its column's total comes out -inf.  An fa entry that underflowed to 0 in the sweep is a state the walk
+// cannot pass.  Nothing of the model is written.
+// One workgroup of 256 threads per (restart, query); G lives in LDS as [S rounded up to 16][16 columns]; a step is
+// k_region_extremes' without a masked row: the states s' with mass in any column, one shared D(s') and H = G / D in place, G_n
+// on v_mfma_f64_16x16x4_f64 (A = W(s0 + i, s'_k) from the Wb row or exp(trans_value), selected to 0 on a row with fa = 0 or
+// s >= S, B = H(s'_k, j)), the row factor fa_n(s) and the column sums from the registers.  The emission: thread (i, j) of the
+// 16 x 16 sums G(s, j) over s in ascending order where the row level of n's class is i (lev: that level row in LDS).
+// q.labels / q.nlabel carry the level tables; fields 2 and 3 of a query are the row and the column level index (the host
+// checked them, and that a profile query has t - a < nslot).  Every sum has one order, fixed by S alone: a cell depends on
+// neither nrow, nslot, the restart range, the other queries nor the launch, and slot k of a profile query is the pair form's
+// table of (t - k, t) bit for bit.  Only columns s < S of fa / post are read (clamped address and select).  A D(s') that is 0
+// or not finite under mass, or a column sum that is not a finite number >= 0, sets RGN_ERR_DENOM in flags[r] and gives NaN in
+// every cell of the query.
+// grid (queries, restarts), block RGN_NT, dynamic LDS rlj_lds_bytes(S); out[((ri * nq + query) * max(nslot, 1) + slot) * nrow * ncol + i * ncol + j].
+// =============================================================================
+static inline size_t rlj_lds_bytes(int S) { const size_t SR = ((size_t)S + 15) & ~(size_t)15; return SR * (RGN_KB * 8 + 8 + 2 * 2); }
+#define RLJ_MAXSLOT 4096      // slots of a profile query
+#define RLJ_NOLEVEL 0x7fff
+// level row vi of segment n's class -> lev[0 .. SR), RLJ_NOLEVEL at s >= S
+__device__ __forceinline__ void rlj_level_row(const Dev &d, const RgnArgs &q, int n, int vi, int S, int SR, int16_t *lev) {
+    const int16_t *lv = q.labels + ((size_t)d.seg_class[n] * q.nlabel + vi) * S;
+    for (int s = threadIdx.x; s < SR; s += RGN_NT) {
+        const int v = lv[s < S ? s : S - 1];
+        lev[s] = (int16_t)(s < S ? v : RLJ_NOLEVEL);
+    }
+}
+// the table of one segment from G (divided by its column sums) and the columns' logarithms: thread (i, j) = (tid / 16, tid % 16)
+__device__ __forceinline__ void rlj_emit(const double *G, const int16_t *lev, int S, int nrow, int ncol, double logp, double *cell) {
+    const int i = threadIdx.x >> 4, j = threadIdx.x & 15;
+    double sum = 0.;
+    for (int s = 0; s < S; s++) {
+        const double g = G[s * RGN_KB + j];
+        sum += (int)lev[s] == i ? g : 0.;
+    }
+    if (i < nrow && j < ncol) cell[i * ncol + j] = sum > 0. ? log(sum) + logp : -INFINITY;
+}
+template <int TPW>
+__global__ __launch_bounds__(RGN_NT) void k_locus_joint(Dev d, int r0, int use_wb, RgnArgs q, int nrow, int ncol, int nslot, double *out, uint32_t *flags) {
+    extern __shared__ double rlj_lds[];                 // G [SR][16], fas [SR], lev [SR] (int16), idx [SR] (int16)
+    __shared__ double redc[RGN_NW][RGN_KB];
+    __shared__ int nact, s_bad;
+    const int qi = blockIdx.x, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (uniform, and known to be: the matrix instructions sit under conditions on it)
+    const int grp = tid / RGN_GL, gl = tid % RGN_GL;
+    const int ai = lane & 15, kk = lane >> 4;
+    const int S = d.S, SR = (S + 15) & ~15;
+    double *G = rlj_lds, *fas = G + (size_t)SR * RGN_KB;
+    int16_t *lev = (int16_t *)(fas + SR), *idx = lev + SR;
+    const int a = q.queries[4 * qi], t = q.queries[4 * qi + 1], vr = q.queries[4 * qi + 2], vc = q.queries[4 * qi + 3];
+    const int tab = nrow * ncol, nsl = nslot > 0 ? nslot : 1;
+    double *oq = out + ((size_t)ri * q.nq + qi) * nsl * tab;
+    if (tid == 0) s_bad = 0;
+    double logp = 0.;         // of column ai: the threads of a column carry the same value
+    bool failed = false;
+    // ---- start: G_t(s, j) = [level_col(s) = j] post_t(s), and the table of t itself ---------------------------------
+    {
+        const double *post = d.post + rs_off(d, r, t);
+        rlj_level_row(d, q, t, vc, S, SR, lev);
+        __syncthreads();
+        double part = 0.;
+        for (int e = tid; e < SR * RGN_KB; e += RGN_NT) {      // (e % 16 == ai: RGN_NT is a multiple of 16)
+            const int s = e / RGN_KB, sc = s < S ? s : S - 1;
+            const double pv = post[sc];
+            const double v = (ai < ncol && (int)lev[s] == ai) ? pv : 0.;
+            G[e] = v;
+            part += v;
+        }
+        const double Z = rgx_column_sum(part, redc);
+        failed = !rgx_take_sum(Z, false, logp);
+        for (int e = tid; e < SR * RGN_KB; e += RGN_NT) G[e] = (!failed && Z > 0.) ? G[e] / Z : 0.;
+        if (!failed && (nslot > 0 || a == t)) {
+            __syncthreads();  // (every read of the column levels is done, G is complete)
+            rlj_level_row(d, q, t, vr, S, SR, lev);
+            __syncthreads();
+            rlj_emit(G, lev, S, nrow, ncol, logp, oq);
+        }
+    }
+    for (int n = t - 1; n >= a && !failed; n--) {
+        const bool emit = nslot > 0 || n == a;
+        const auto [wb, Wt, pd] = rgn_adj(d, r, n, use_wb);
+        const double *fa = d.fa + rs_off(d, r, n);
+        for (int s = tid; s < SR; s += RGN_NT) {
+            const int sc = s < S ? s : S - 1;
+            const double fv = fa[sc];
+            fas[s] = s < S ? fv : 0.;
+        }
+        // ---- 1. the states s' with mass in any column, in state order ------------------------------------------
+        __syncthreads();      // (G of the step before, or of the start, is complete, and its table is out)
+        if (emit) rlj_level_row(d, q, n, vr, S, SR, lev);
+        const int na = __builtin_amdgcn_readfirstlane(rgn_compact(S, idx, nact, [&](int s) {
+            bool act = false;
+            for (int k = 0; k < ncol; k++) act = act || G[s * RGN_KB + k] > 0.;
+            return act;
+        }));
+        // ---- 2. D(s') and H = G / D in place ---------------------------------------------------------------------
+        if (wb) {
+            for (int j0 = 0; j0 < na; j0 += RGN_NT / RGN_GL) {
+                const int j = j0 + grp;
+                const bool ok = j < na;
+                const int sp = ok ? idx[j] : 0;
+                double p = 0.;
+                if (ok) {
+                    const double *wr = Wt + (size_t)sp * S;
+                    for (int s = gl; s < S; s += RGN_GL) p = fma(fas[s], wr[s], p);
+                }
+                const double D = group_sum(p, RGN_GL);
+                if (ok) {
+                    if (gl == 0 && !(D > 0. && D < INFINITY)) s_bad = 1;
+                    if (gl < ncol) G[sp * RGN_KB + gl] = G[sp * RGN_KB + gl] / D;
+                }
+            }
+        } else {
+            for (int j = tid; j < na; j += RGN_NT) {
+                const int sp = idx[j];
+                const double D = rgn_D_exp(d, n, sp, fas, pd);
+                if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                for (int k = 0; k < ncol; k++) G[sp * RGN_KB + k] = G[sp * RGN_KB + k] / D;
+            }
+        }
+        __syncthreads();
+        // ---- 3. G_n on the matrix cores: one instruction per (row tile, four s') ---------------------------------
+        psm_d4 acc[TPW];
+        bool rowlive[TPW];    // the lane's A row of tile u is a state the walk can pass
+#pragma unroll
+        for (int u = 0; u < TPW; u++) {
+            acc[u] = psm_d4{0., 0., 0., 0.};
+            const int s = (wave + RGN_NW * u) * 16 + ai;
+            rowlive[u] = s < S && fas[s < SR ? s : 0] != 0.;
+        }
+        for (int j0 = 0; j0 < na; j0 += 4) {
+            const int j = j0 + kk;
+            const bool ok = j < na;
+            const int sp = idx[ok ? j : 0];
+            const double hv = G[sp * RGN_KB + ai];
+            const double bv = (ok && ai < ncol) ? hv : 0.;
+#pragma unroll
+            for (int u = 0; u < TPW; u++) {
+                const int s0 = (wave + RGN_NW * u) * 16;
+                if (s0 < S) {         // (uniform over the wave)
+                    const int s = s0 + ai, sc = s < S ? s : S - 1;
+                    const bool live = ok && rowlive[u];
+                    double wv;
+                    if (wb) wv = Wt[(size_t)sp * S + sc];
+                    else wv = live ? exp(trans_value(d, n, sc, sp, pd)) : 0.;
+                    acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(live ? wv : 0., bv, acc[u], 0, 0, 0);
+                }
+            }
+        }
+        // ---- 4, 5. the row factor and the column sums, from the registers -------------------------------------
+        double part = 0.;
+#pragma unroll
+        for (int u = 0; u < TPW; u++) {
+            const int s0 = (wave + RGN_NW * u) * 16;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int s = s0 + kk + 4 * g;
+                const double fv = fas[s < SR ? s : 0];
+                const double v = (s < SR && fv != 0.) ? fv * acc[u][g] : 0.;
+                acc[u][g] = v;
+                part += v;
+            }
+        }
+        const double Z = rgx_column_sum(part, redc);
+        failed = !rgx_take_sum(Z, s_bad != 0, logp);
+        const bool live = !failed && Z > 0.;
+#pragma unroll
+        for (int u = 0; u < TPW; u++) {
+            const int s0 = (wave + RGN_NW * u) * 16;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int s = s0 + kk + 4 * g;
+                if (s < SR) G[s * RGN_KB + ai] = live ? acc[u][g] / Z : 0.;
+            }
+        }
+        // ---- 6. the table of segment n ---------------------------------------------------------------------------
+        if (emit && !failed) {
+            __syncthreads();
+            rlj_emit(G, lev, S, nrow, ncol, logp, oq + (size_t)(nslot > 0 ? t - n : 0) * tab);
+        }
+    }
+    // the slots past t - a, and every cell of a failed query: thread (i, j) owns cell (i, j) of every slot
+    {
+        const int i = tid >> 4, j = tid & 15;
+        if (i < nrow && j < ncol)
+            for (int k = failed ? 0 : (nslot > 0 ? t - a + 1 : 1); k < nsl; k++) oq[(size_t)k * tab + i * ncol + j] = __builtin_nan("");
+    }
+    if (tid == 0 && failed) atomicOr(&flags[r], RGN_ERR_DENOM);
+}
+
+// =============================================================================
 // Region conditionals: the marginal of every segment of a window [lo, hi] given k_region_prob's event E over an evidence run
 // [a, b] inside it (lo <= a <= b <= hi, one chain), and log P(E).  Under the backward kernel c_n separates the two sides, so
 //   q(c_n = s | E) = U_n(s) g_n(s) / P(E),

@@ -1863,3 +1863,220 @@ def evidence_shift(conditional, unconditional, l=None):
             part = {'total_cn_mean': np.asarray(s['total_cn_mean'])[inside], 'expected_alleles_subclonal': np.asarray(s['expected_alleles_subclonal'])[inside]}
             out[name] = summary_stats(part, lw)['ploidy_posterior_mean'] if inside.any() and lw.sum() > 0 else float('nan')
     return out
+
+
+# ---- joint posterior of copy number at two loci of a chain (rmx_locus_joint) ------------------------------
+JOINT_ARRAYS = ('joint', 'marginal_a', 'marginal_b', 'p_equal', 'p_a_higher', 'p_b_higher', 'difference_pmf', 'mean_difference', 'correlation',
+                'mutual_information', 'p_saturated')
+DEPENDENCE_ARRAYS = ('mutual_information', 'correlation', 'p_equal')
+_LOCUS_MAX_SLOTS = 4096
+_LOCUS_HOST_BYTES = 256 << 20      # the tables one device call of batch_locus_dependence brings back
+
+
+def locus_level_tables(cn_classes, bins, first_level=0):
+    """Level tables of the locus joints: (levels int16 (C, T, S), names).  First the 3 * M 'peak' tables of level_tables,
+    named 'peak_<quantity>_<clone>' -- clip(q - first_level, 0, bins - 1) of a clone's (or the tumour clones' highest) total,
+    major or minor copy number, the last bin meaning first_level + bins - 1 or more --, then one 0/1 table per mask of
+    event_tables, named as in MASK_NAMES: level 1 where the event holds."""
+    levels, names = level_tables(cn_classes, bins, first_level)
+    half = len(names) // 2
+    masks, _ = event_tables(cn_classes)
+    tabs = np.concatenate([levels[:, :half], masks.astype(np.int16)], axis=1)
+    return np.ascontiguousarray(tabs), names[:half] + list(MASK_NAMES)
+
+
+def locus_feature_name(feature, num_clones):
+    """The table name of a feature: (quantity, clone) with quantity in LEVEL_QUANTITIES and clone 1 .. M-1 or 'any', or a name
+    of MASK_NAMES."""
+    if isinstance(feature, str):
+        if feature not in MASK_NAMES:
+            raise ValueError('unknown feature %r: a (quantity, clone) pair or one of %s' % (feature, ', '.join(MASK_NAMES)))
+        return feature
+    try:
+        quantity, clone = feature
+    except (TypeError, ValueError):
+        raise ValueError('a feature is a (quantity, clone) pair or one of %s' % ', '.join(MASK_NAMES))
+    if clone != 'any' and not (isinstance(clone, (int, np.integer)) and 1 <= clone < num_clones):
+        raise ValueError('clone must be a tumour clone 1 .. %d or \'any\'' % (num_clones - 1))
+    return level_name('peak', quantity, clone)
+
+
+def locus_queries(pairs, seg_fwd_remap, chain_start, chain_end):
+    """Pairs of experiment segments (P, 2), in any order, as model segments: (segs int32 (P, 2) ordered left, right; swapped
+    bool (P,), whether the pair's first locus is the right one; cross bool (P,), whether the two lie in different chains)."""
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    fwd = np.asarray(seg_fwd_remap, dtype=np.int64)
+    if len(pr) and (pr.min() < 0 or pr.max() >= len(fwd)):
+        raise ValueError('a locus needs 0 <= segment < number of segments')
+    seg = fwd[pr]
+    swapped = seg[:, 0] > seg[:, 1]
+    segs = np.where(swapped[:, None], seg[:, ::-1], seg).astype(np.int32)
+    ce = np.asarray(chain_end, dtype=np.int64)
+    cross = np.searchsorted(ce, segs[:, 0], side='left') != np.searchsorted(ce, segs[:, 1], side='left')
+    return segs, swapped, cross
+
+
+def joint_summary(log_joint, first_level=0):
+    """What a table of two levels says, log_joint (..., bins, bins) with locus a along axis -2 and locus b along axis -1: a dict of
+      joint             (..., bins, bins)    exp(log_joint)
+      marginal_a, marginal_b  (..., bins)    its row and column sums
+      p_equal, p_a_higher, p_b_higher (...)  the mass on, below and above the diagonal
+      difference_pmf    (..., 2 bins - 1)    of level(a) - level(b), entry d + bins - 1
+      mean_difference   (...)
+      correlation       (...)                of the two levels; NaN where a marginal is degenerate
+      mutual_information (...)               in nats, clipped at 0
+      p_saturated       (...)                the mass with either level in the last, "or more" bin, where differences are not resolved.
+    Correlation and mutual information are those of the table divided by its sum (it is 1 for tables that cover every state).
+    A table with a NaN gives NaN.  first_level is carried for the caller: differences do not depend on it."""
+    lj = np.asarray(log_joint, dtype=float)
+    bins = lj.shape[-1]
+    if lj.shape[-2] != bins:
+        raise ValueError('log_joint must have shape (..., bins, bins)')
+    with np.errstate(over='ignore', invalid='ignore'):
+        J = np.exp(lj)
+    ma, mb = J.sum(axis=-1), J.sum(axis=-2)
+    lev = np.arange(bins)
+    d = lev[:, None] - lev[None, :]
+    out = {'joint': J, 'marginal_a': ma, 'marginal_b': mb,
+           'p_equal': np.where(d == 0, J, 0.).sum(axis=(-2, -1)), 'p_a_higher': np.where(d > 0, J, 0.).sum(axis=(-2, -1)),
+           'p_b_higher': np.where(d < 0, J, 0.).sum(axis=(-2, -1))}
+    pmf = np.zeros(J.shape[:-2] + (2 * bins - 1,))
+    for k in range(-(bins - 1), bins):
+        pmf[..., k + bins - 1] = np.where(d == k, J, 0.).sum(axis=(-2, -1))
+    out['difference_pmf'] = pmf
+    out['mean_difference'] = (pmf * np.arange(-(bins - 1), bins)).sum(axis=-1)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        tot = J.sum(axis=(-2, -1))
+        P = J / tot[..., None, None]
+        pa, pb = P.sum(axis=-1), P.sum(axis=-2)
+        ea, eb = (pa * lev).sum(axis=-1), (pb * lev).sum(axis=-1)
+        va, vb = (pa * lev ** 2).sum(axis=-1) - ea ** 2, (pb * lev ** 2).sum(axis=-1) - eb ** 2
+        cov = (P * (lev[:, None] * lev[None, :])).sum(axis=(-2, -1)) - ea * eb
+        degenerate = (pa.max(axis=-1) >= 1.) | (pb.max(axis=-1) >= 1.) | ~(va > 0) | ~(vb > 0)
+        corr = np.where(degenerate, np.nan, cov / np.sqrt(np.where(degenerate, 1., va * vb)))
+        out['correlation'] = np.where(np.isnan(tot), np.nan, np.clip(corr, -1., 1.))
+        # (the logarithms apart: the product of two marginals near 1e-200 is 0 in double, their cell is not)
+        lp, la, lb = (np.log(np.where(x > 0, x, 1.)) for x in (P, pa, pb))
+        mi = np.where(P > 0, P * (lp - la[..., :, None] - lb[..., None, :]), 0.).sum(axis=(-2, -1))
+        out['mutual_information'] = np.where(np.isnan(tot) | ~(tot > 0), np.nan, np.maximum(mi, 0.))
+    last = (lev[:, None] == bins - 1) | (lev[None, :] == bins - 1)
+    out['p_saturated'] = np.where(last, J, 0.).sum(axis=(-2, -1))
+    return out
+
+
+def _locus_tables(batch, feature, other, bins, first_level):
+    bins = int(bins)
+    if not 1 <= bins <= 16:
+        raise ValueError('bins must be in 1 .. 16')
+    levels, names = locus_level_tables(batch.cn_classes, bins, first_level)
+    M = np.asarray(batch.cn_classes).shape[2]
+    fi = names.index(locus_feature_name(feature, M))
+    oi = fi if other is None else names.index(locus_feature_name(other, M))
+    return bins, levels, fi, oi
+
+
+def batch_locus_joint(batch, r0, nr, pairs, seg_fwd_remap, seg_is_original, is_telomere, feature=('total', 1), other=None, bins=8, first_level=0):
+    """The exact joint posterior of `feature` at the first and `other` at the second locus of every pair, for restarts r0 ..
+    r0+nr-1 of a RemixtBatch from one device call (rmx_locus_joint).  pairs: (first, second) experiment segment indices in
+    any order; a pair whose first locus is the right one is asked left to right with the tables exchanged and comes back
+    transposed, so that axis -2 is always the pair's first locus.  other None: the same feature.  A pair in two chains is the
+    outer product of the two marginals, which (a, a) and (t, t) queries of the same call give: chains are independent under the
+    structured posterior, and the mutual information of such a pair is 0.  A dict of `log_joint` (nr, P, bins, bins), the
+    arrays of joint_summary, `bins` and `first_level`."""
+    bins, levels, fi, oi = _locus_tables(batch, feature, other, bins, first_level)
+    cs, ce = chains_from_telomeres(is_telomere)
+    segs, swapped, cross = locus_queries(pairs, seg_fwd_remap, cs, ce)
+    P = len(segs)
+    same = np.flatnonzero(~cross)
+    far = np.flatnonzero(cross)
+    q = np.zeros((len(same) + 2 * len(far), 4), dtype=np.int32)
+    # one chain: left, right, the left locus's table, the right locus's
+    q[:len(same), :2] = segs[same]
+    q[:len(same), 2] = np.where(swapped[same], oi, fi)
+    q[:len(same), 3] = np.where(swapped[same], fi, oi)
+    # two chains: the first locus alone, then the second
+    first = np.where(swapped[far], segs[far, 1], segs[far, 0])
+    second = np.where(swapped[far], segs[far, 0], segs[far, 1])
+    q[len(same):len(same) + len(far)] = np.stack([first, first, np.full(len(far), fi), np.full(len(far), fi)], axis=1)
+    q[len(same) + len(far):] = np.stack([second, second, np.full(len(far), oi), np.full(len(far), oi)], axis=1)
+    lj = np.zeros((nr, P, bins, bins))
+    if P:
+        raw = batch.locus_joint_raw(r0, nr, q, levels, bins, bins, 0)
+        t = raw[:, :len(same)]
+        lj[:, same] = np.where(swapped[same][None, :, None, None], np.swapaxes(t, -1, -2), t)
+        diag = np.arange(bins)
+        ma = raw[:, len(same):len(same) + len(far)][..., diag, diag]
+        mb = raw[:, len(same) + len(far):][..., diag, diag]
+        with np.errstate(invalid='ignore'):
+            lj[:, far] = ma[..., :, None] + mb[..., None, :]
+    out = {'log_joint': lj, 'bins': bins, 'first_level': int(first_level)}
+    out.update(joint_summary(lj, first_level))
+    return out
+
+
+def locus_windows(anchors, window, seg_fwd_remap, chain_start, chain_end):
+    """The neighbourhoods of batch_locus_dependence: segment int (A, 2 window + 1), the experiment segments window .. 1 to the
+    left of every anchor, the anchor, and 1 .. window to its right, -1 outside the anchor's chain."""
+    an = np.asarray(anchors, dtype=np.int64).reshape(-1)
+    fwd = np.asarray(seg_fwd_remap, dtype=np.int64)
+    window = int(window)
+    if window < 0:
+        raise ValueError('window must not be negative')
+    if len(an) and (an.min() < 0 or an.max() >= len(fwd)):
+        raise ValueError('an anchor needs 0 <= segment < number of segments')
+    ce = np.asarray(chain_end, dtype=np.int64)
+    seg = an[:, None] + np.arange(-window, window + 1)[None, :]
+    inside = (seg >= 0) & (seg < len(fwd))
+    chain = np.searchsorted(ce, fwd[np.clip(seg, 0, len(fwd) - 1)], side='left')
+    inside &= chain == chain[:, window:window + 1]
+    return np.where(inside, seg, -1)
+
+
+def batch_locus_dependence(batch, r0, nr, anchors, seg_fwd_remap, seg_is_original, is_telomere, window=32, feature=('total', 1), other=None, bins=8,
+                           first_level=0):
+    """The dependence profile of anchors: for every anchor (an experiment segment) and each of the `window` experiment segments
+    on either side inside its chain, joint_summary's mutual_information, correlation and p_equal of `feature` at the anchor
+    and `other` at the neighbour.  A dict of `segment` (A, 2 window + 1), experiment indices with -1 outside the chain, the
+    three arrays (nr, A, 2 window + 1), NaN there, `bins` and `first_level`.  The left half and the anchor itself come from one
+    profile query per anchor (rmx_locus_joint with nslot >= 1: the walk from the anchor leftwards emits the table at every
+    step), from which the slots of zero-length segments inserted at shared boundaries are dropped through seg_is_original;
+    the right half from one pair query per neighbour."""
+    bins, levels, fi, oi = _locus_tables(batch, feature, other, bins, first_level)
+    cs, ce = chains_from_telomeres(is_telomere)
+    fwd = np.asarray(seg_fwd_remap, dtype=np.int64)
+    orig = np.asarray(seg_is_original) != 0
+    segment = locus_windows(anchors, window, fwd, cs, ce)
+    A, W = segment.shape[0], int(window)
+    out = {'segment': segment, 'bins': bins, 'first_level': int(first_level)}
+    res = dict((k, np.full((nr, A, 2 * W + 1), np.nan)) for k in DEPENDENCE_ARRAYS)
+    if A:
+        T = fwd[segment[:, W]]
+        leftmost = np.where(segment[:, :W + 1] >= 0, segment[:, :W + 1], np.iinfo(np.int64).max).min(axis=1)
+        L = fwd[leftmost]
+        nslot = int((T - L).max()) + 1
+        if nslot > _LOCUS_MAX_SLOTS:
+            raise ValueError('the left half of a window spans more than %d model segments' % _LOCUS_MAX_SLOTS)
+        step = max(1, _LOCUS_HOST_BYTES // (max(nr, 1) * nslot * bins * bins * 8))
+        for a0 in range(0, A, step):
+            sl = slice(a0, min(a0 + step, A))
+            n = sl.stop - sl.start
+            # the anchor is the walk's start t: its table is the column one, the neighbour's the row one
+            q = np.stack([L[sl], T[sl], np.full(n, oi), np.full(n, fi)], axis=1).astype(np.int32)
+            prof = batch.locus_joint_raw(r0, nr, q, levels, bins, bins, nslot)                      # (nr, n, nslot, bins, bins)
+            tables = np.full((nr, n, 2 * W + 1, bins, bins), np.nan)
+            for i in range(n):
+                # slot k is model segment T - k: the real ones, in order, are the anchor and its neighbours leftwards
+                ks = np.flatnonzero(orig[T[a0 + i] - np.arange(T[a0 + i] - L[a0 + i] + 1)])
+                tables[:, i, W - np.arange(len(ks))] = np.swapaxes(prof[:, i, ks], -1, -2)
+            right = [(i, k) for i in range(n) for k in range(W + 1, 2 * W + 1) if segment[a0 + i, k] >= 0]
+            if right:
+                q = np.array([[T[a0 + i], fwd[segment[a0 + i, k]], fi, oi] for i, k in right], dtype=np.int32)
+                pair = batch.locus_joint_raw(r0, nr, q, levels, bins, bins, 0)
+                ii, kk = np.array(right).T
+                tables[:, ii, kk] = pair
+            with np.errstate(invalid='ignore'):
+                s = joint_summary(tables, first_level)
+            for k in DEPENDENCE_ARRAYS:
+                res[k][:, sl] = s[k]
+    out.update(res)
+    return out

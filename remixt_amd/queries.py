@@ -6,7 +6,7 @@ The four classes that answer queries -- cn_model.BreakpointModel (one restart), 
 batch), restarts.RestartGroups (several batches) and restarts.DatasetGroups (several datasets) -- get their methods from
 this table through the class decorator `answers`: one generic body per level below, no code per (query, level).
 
-Adding a query: its posteriors.batch_* function, and its entry here.
+Adding a query: its posteriors.batch_* function, and its entry here, in LATER_QUERIES (QUERIES itself is a closed list).
 
 (posteriors imports nothing of this package when it loads, and this module imports posteriors alone, so cn_model and
 restarts load it at import time without a cycle.  sample_cn, restart_overlap and ploidy_posterior_sd are no entries: the
@@ -250,7 +250,37 @@ def cn_change_prob(q):
 QUERIES = (posterior_summary, region_events, region_change_counts, region_cn_extremes, region_clone_extremes, region_cn_moments,
            event_extent, conditional_summary, event_span, event_joint, focal_events, breakend_changes, region_call,
            region_alternatives, call_confidence, cn_logprob, cn_change_prob)
-BY_NAME = dict((e.name, e) for e in QUERIES)
+
+
+@_query('locus_joint_raw', 'has no locus joints', '`bins`, `first_level` and arrays (restarts, len(pairs), ...)', shared=('bins', 'first_level'))
+def locus_joint(q, pairs, feature=('total', 1), other=None, bins=8, first_level=0):
+    """The exact joint posterior of copy number at two loci, under the structured posterior of the last variational update:
+    is the gene above the arm it sits on, do the two sides of a rearrangement carry the same total, are both genes in LOH.
+    pairs is a list of (first, second) experiment segment indices in any order; feature what is read at the first locus and
+    other at the second (None: the same) -- (quantity, clone) with quantity 'total', 'major' or 'minor' and clone a tumour
+    clone 1 .. M-1 or 'any', in the window first_level .. first_level + bins - 1 (the last bin meaning "or more"), or a mask
+    name of posteriors.MASK_NAMES (level 1: the event holds).  A dict of `bins`, `first_level`, `log_joint` (len(pairs), bins,
+    bins) with the first locus along axis -2, and the arrays of posteriors.joint_summary: joint, marginal_a, marginal_b,
+    p_equal, p_a_higher, p_b_higher, difference_pmf, mean_difference, correlation, mutual_information and p_saturated.  Two
+    loci in different chains are independent: their table is the product of the marginals."""
+    return posteriors.batch_locus_joint(*q.at, pairs, *q.maps, feature=feature, other=other, bins=bins, first_level=first_level)
+
+
+@_query('locus_joint_raw', 'has no locus joints', '`bins`, `first_level`, `segment` (len(anchors), 2 window + 1) and arrays (restarts, len(anchors), 2 window + 1)',
+        shared=('bins', 'first_level', 'segment'))
+def locus_dependence(q, anchors, window=32, feature=('total', 1), other=None, bins=8, first_level=0):
+    """How far along the chain knowing one segment tells anything about another: for every anchor (an experiment segment index)
+    and each of the `window` experiment segments on either side of it inside its chain, the mutual information (nats), the
+    correlation and the probability of equality between `feature` at the anchor and `other` at the neighbour (feature, other,
+    bins and first_level as locus_joint).  A dict of `bins`, `first_level`, `segment` (len(anchors), 2 window + 1) -- the
+    neighbours' experiment indices, the anchor in the middle, -1 outside the chain -- and `mutual_information`, `correlation`
+    and `p_equal` of that shape, NaN outside the chain."""
+    return posteriors.batch_locus_dependence(*q.at, anchors, *q.maps, window=window, feature=feature, other=other, bins=bins, first_level=first_level)
+
+
+# (QUERIES is a closed list: tests compare its names with theirs.  Later entries go here; BY_NAME and `answers` run over both)
+LATER_QUERIES = (locus_joint, locus_dependence)
+BY_NAME = dict((e.name, e) for e in QUERIES + LATER_QUERIES)
 
 
 # ---- a result along the restart axis ----------------------------------------------------------------------------------------
@@ -374,7 +404,7 @@ def answers(level):
     body, doc = LEVELS[level]
 
     def install(cls):
-        for entry in QUERIES:
+        for entry in QUERIES + LATER_QUERIES:
             setattr(cls, entry.name, _method(cls, entry, body, doc(entry)))
         return cls
     return install

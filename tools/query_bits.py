@@ -2,7 +2,8 @@
 sample_states, posterior_summary_raw, region_logprob_raw, region_counts_raw (1, 5 and 16 bins), call_logprob_raw,
 region_moments_raw (nf 1 and 4), region_extent_raw, region_pattern_raw, region_decode_raw (log-probabilities and states),
 region_kbest_raw (1, 3 and 8 ranks; log-probabilities and states), region_extremes_raw (1, 5 and 16 columns) and region_conditional_raw (log-probabilities and slots; chain windows), each with
-and without a constrain vector that leaves segments unbound (a library without an entry point leaves its arrays out).
+and without a constrain vector that leaves segments unbound, and locus_joint_raw (three table sizes and the profile form; a
+library without an entry point leaves its arrays out).
 Scenarios: the three grids of tests/test_hip_sample_cn.py (60, 40 and 24 segments at 165, 355 and 457 states) and 16 segments at
 max_copy_number 16 (more than 512 states: the <16> instantiations), three chains, four restarts after two sweeps, restarts 1 and 2
 with their snapshot retaken under the other transition model (exp(trans_value) on plain adjacencies too).  Queries: a segment, a
@@ -127,6 +128,13 @@ def collect(rs, out, kbest=True):
             win = np.array([(cs[np.searchsorted(ce, a)], ce[np.searchsorted(ce, a)]) for a in qr[:, 0]], dtype=np.int32)
             out[key('region_conditional_logp_' + tag)], out[key('region_conditional_' + tag)] = b.region_conditional_raw(
                 0, R, qr, win, masks, labels, con, cw, argmax)
+    if hasattr(b, 'locus_joint_raw'):
+        lv, ln = posteriors.locus_level_tables(b.cn_classes, 16)
+        ql = np.array([[a, z, ln.index(vr), ln.index(vc)] for a, z in runs
+                       for vr, vc in (('peak_total_any', 'peak_total_any'), ('peak_total_1', 'peak_major_2'), ('loh', 'peak_total_any'))], dtype=np.int32)
+        for nrow, ncol in ((1, 1), (5, 16), (16, 16)):
+            out[key('locus_joint%dx%d' % (nrow, ncol))] = b.locus_joint_raw(0, R, ql, lv, nrow, ncol)
+        out[key('locus_joint_profile')] = b.locus_joint_raw(0, R, ql, lv, 16, 16, int((ql[:, 1] - ql[:, 0]).max()) + 1)
     out[key('region_moments1')] = b.region_moments_raw(0, R, qm1, feats, weights, 1)
     out[key('region_moments4')] = b.region_moments_raw(0, R, qm4, feats, weights, 4)
     print('%d states, %d model segments, %d chains, %d plain and %d breakend adjacencies, %d runs, %d anchors, %d of %d segments unbound' % (

@@ -651,6 +651,40 @@ int rmx_region_kbest(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int
 int rmx_locus_joint(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nlevel, const int16_t *levels,
                     int32_t nrow, int32_t ncol, int32_t nslot, double *logp_out);
 
+/* Region automata: the exact posterior of regular path events over regions.  A deterministic finite automaton
+ * with Q <= 16 states and A <= 16 symbols reads one symbol per segment of a run and the call returns the distribution of its
+ * final state: the number of separate events of a run, whether some event spans k consecutive segments, how often copy
+ * number switches between two levels, an ordered pattern.
+ *   symbols int16 [C][nsym][S], every entry in [0, A): the symbol of a state under a state class (the levels' layout)
+ *   delta uint8 [nauto][Q][A], every entry in [0, Q), and start int32 [nauto], every entry in [0, Q)
+ *   1 <= Q <= 16, 1 <= A <= 16, 1 <= nauto <= 64
+ *   query i = (a, b, symbol table index, automaton index) over the model segments a <= b of one chain
+ *   constrain uint8 [N], or NULL for "every segment"
+ * THE AUTOMATON READS THE RUN FROM ITS LAST SEGMENT TO ITS FIRST: b, b - 1, .. a, the direction of the walk.  A segment with
+ * constrain[n] == 0 is NOT READ: its state is marginalised and the automaton does not move (unlike rmx_region_counts, where
+ * such a segment still takes part in the label changes; deliberately so: an inserted zero-length segment is no segment of a
+ * run).  With post, fa, W_n and D_n as in rmx_region_prob, sigma_n(s) the symbol of state s under the class of segment n
+ * and q0 the start state,
+ *   G_b(s, q) = post_b(s) [q = delta(q0, sigma_b(s))]                        (b not read: [q = q0])
+ *   H(s', q)  = G_n+1(s', q) / D_n(s'),   X(s, q) = fa_n(s) sum_s' W_n(s, s') H(s', q)
+ *   G_n(s, q) = sum_{q' ascending: delta(q', sigma_n(s)) = q} X(s, q')       (n not read: X(s, q))
+ *   logp_out [nr][nq][Q]: out(q) = log sum_s G_a(s, q) = log P(the automaton ends in q).
+ * A state that cannot be reached gives -inf and is no error.  Nothing binds, so in real arithmetic the total over (s, q) is 1
+ * at every step and the Q outputs sum to 1; G is still divided by its total after every step, the start included, and the
+ * logarithm is accumulated, which only removes rounding drift.  One scale carries all columns, because columns mix under
+ * delta: a column more than about 1e-308 below the total comes out -inf.  The model is not modified.
+ * A (restart, query) result is bit-identical in any restart range, any batch and order of queries, any chunking, and when
+ * the automaton is padded with unreachable states up to a larger Q.
+ * Errors: RMX_EARG with nothing launched and the output untouched for a bad restart range, nq < 1, a NULL pointer (constrain
+ * excepted), nauto, Q or A out of bounds, nsym < 1, a delta or start entry outside [0, Q), a symbol outside [0, A), a symbol
+ * table or automaton index out of range, segments outside the model, a > b or in two chains; RMX_EVALUE with the restarts
+ * listed before update_p_cn; RMX_EASSERT with the restarts listed for a normaliser D that is 0 or not finite under mass or a
+ * sum that is not a finite number >= 0: all Q entries of that query are NaN; RMX_EUNSUPPORTED above 1024 states.  The kernel
+ * has no profile id. */
+int rmx_region_automaton(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nsym, const int16_t *symbols,
+                         int32_t nauto, int32_t Q, int32_t A, const uint8_t *delta, const int32_t *start, const uint8_t *constrain,
+                         double *logp_out);
+
 /* -- module-level functions on caller-supplied dense inputs ----------------- */
 /* sum_product (:1213-1246): f [N][S], T [N-1][S][S] -> alphas, betas [N][S] */
 int rmx_sum_product(const double *f, const double *T, double *alphas, double *betas,

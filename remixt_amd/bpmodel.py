@@ -695,6 +695,37 @@ class RemixtBatch(object):
         self._ck(self._lib.rmx_locus_joint(self._handle, r0, nr, args[0], args[1], args[4], args[5], nrow, ncol, nslot, obuf.ctypes.data_as(_dp)))
         return out
 
+    def region_automaton_raw(self, r0, nr, queries, symbols, delta, start, constrain=None):
+        """The exact distribution of the final state of deterministic finite automata that read one symbol per segment of a
+        run of model segments, under the structured posterior of the last update_p_cn of restarts r0 .. r0+nr-1
+        (rmx_region_automaton).  queries int (nq, 4): segments a <= b of one chain, symbol table index, automaton index;
+        symbols int (C, nsym, S) with entries in [0, A); delta int (nauto, Q, A) with entries in [0, Q), delta[u, q, x] the
+        state after reading symbol x in state q; start int (nauto,).  THE AUTOMATON READS A RUN FROM ITS LAST SEGMENT TO ITS
+        FIRST; a segment with constrain[n] == 0 is not read (its state is marginalised, the automaton does not move).
+        Returns (nr, nq, Q): log P(the automaton ends in state q), -inf for a state that cannot be reached.  Q, A in 1 .. 16,
+        nauto in 1 .. 64."""
+        r0, nr = int(r0), int(nr)
+        q, args, _keep = self._region_args(queries, None, symbols, constrain)
+        dl = np.asarray(delta)
+        if dl.ndim != 3:
+            raise ValueError('delta must have shape (nauto, Q, A)')
+        if dl.size and (dl.min() < 0 or dl.max() > 255):
+            raise ValueError('delta entry out of the uint8 range')
+        dl = np.ascontiguousarray(dl, dtype=np.uint8)
+        st = np.asarray(start)
+        if st.shape != (dl.shape[0],):
+            raise ValueError('start must have shape (nauto,)')
+        if st.size and (st.min() < -2 ** 31 or st.max() >= 2 ** 31):
+            raise ValueError('start entry out of range')
+        st = np.ascontiguousarray(st, dtype=np.int32)
+        nauto, Q, A = dl.shape
+        out = np.zeros((max(nr, 0), q.shape[0], Q if 1 <= Q <= 16 else 1), dtype=np.float64)
+        obuf, dbuf, sbuf = out if out.size else np.zeros(1), dl if dl.size else np.zeros(1, dtype=np.uint8), st if st.size else np.zeros(1, dtype=np.int32)
+        self._ck(self._lib.rmx_region_automaton(self._handle, r0, nr, args[0], args[1], args[4], args[5], nauto, Q, A,
+                                                dbuf.ctypes.data_as(C.POINTER(C.c_uint8)), sbuf.ctypes.data_as(C.POINTER(C.c_int32)), args[6],
+                                                obuf.ctypes.data_as(_dp)))
+        return out
+
     def restart_overlap_raw(self, other, pairs, queries, perms, mode):
         """log Z (npairs, nq) of the structured posteriors of pairs of restarts over runs of model segments
         (rmx_restart_overlap): Z = sum_x q_A(x)^lam q_B(pi x)^mu, mode 0 the Bhattacharyya overlap (lam = mu = 1/2), mode 1 the
@@ -1147,6 +1178,10 @@ class RemixtModel(object):
     def locus_joint(self, queries, levels, nrow, ncol, nslot=0):
         """RemixtBatch.locus_joint_raw of this model: log-probabilities (nq, nrow, ncol), or (nq, nslot, nrow, ncol)."""
         return self._batch.locus_joint_raw(self._r, 1, queries, levels, nrow, ncol, nslot)[0]
+
+    def region_automaton(self, queries, symbols, delta, start, constrain=None):
+        """RemixtBatch.region_automaton_raw of this model: log-probabilities (nq, Q)."""
+        return self._batch.region_automaton_raw(self._r, 1, queries, symbols, delta, start, constrain)[0]
 
     def region_moments(self, queries, features, weights, nf):
         """RemixtBatch.region_moments_raw of this model: means and covariances (nq, nf + nf (nf + 1) / 2)."""

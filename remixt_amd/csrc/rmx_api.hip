@@ -3872,6 +3872,47 @@ int rmx_locus_joint(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int3
     }, max_pairs);
 }
 
+// Region automata (k_region_automaton): for every (restart, query) the log-probabilities of the Q final states of a
+// deterministic finite automaton that reads one symbol per read segment of the run, from its last segment to its first.
+// Fields 2 and 3 of a query name the symbol table and the automaton; the symbol tables travel where the label tables of the
+// siblings do, delta and start behind them in the shared table buffer.  Everything is checked before anything is queued
+// (check_queries; rmxh::automaton_shape_ok, rmxh::check_automata, rmxh::check_symbols), and no output is written on an error.
+// One workgroup computes a (restart, query) on its own.  The kernel has no profile id (KID_NONE).
+int rmx_region_automaton(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nsym, const int16_t *symbols,
+                         int32_t nauto, int32_t Q, int32_t A, const uint8_t *delta, const int32_t *start, const uint8_t *constrain, double *logp_out) { BIND(b);
+    int rc;
+    if ((rc = check_region_call(b, "region_automaton", r0, nr, nq, queries, logp_out))) return rc;
+    if (!rmxh::automaton_shape_ok(nauto, Q, A)) return fail(RMX_EARG, "region_automaton: needs 1 <= nauto <= 64, 1 <= Q <= 16 and 1 <= A <= 16");
+    if (nsym < 1 || !symbols) return fail(RMX_EARG, "region_automaton: no symbol tables");
+    if (!delta || !start) return fail(RMX_EARG, "region_automaton: no transition tables or no start states");
+    if (b->d.S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "region_automaton: more than 1024 states");
+    if ((rc = check_queries(b, "region_automaton", nq, queries, {0, nsym, "region_automaton: a query needs a symbol table index in [0, nsym)"},
+                            {0, nauto, "region_automaton: a query needs an automaton index in [0, nauto)"}))) return rc;
+    {
+        const int64_t bad = rmxh::check_automata(nauto, Q, A, delta, start);
+        if (bad != -1) return fail(RMX_EARG, "region_automaton: a transition or a start state is outside [0, Q) (entry " + std::to_string(bad) + ")");
+    }
+    if (rmxh::check_symbols(b->d.C, nsym, b->d.S, A, symbols) != -1) return fail(RMX_EARG, "region_automaton: a symbol is outside [0, A)");
+    if ((rc = require_snapshot(b, r0, nr, "region_automaton"))) return rc;
+    RgnArgs ra;
+    uint8_t *extra = nullptr;
+    const size_t start_bytes = (size_t)nauto * sizeof(int32_t), delta_bytes = (size_t)nauto * Q * A;
+    if ((rc = stage_region_tables(b, 0, nullptr, nsym, symbols, constrain, &ra, start_bytes + delta_bytes, &extra))) return rc;
+    HIPCHK(hipMemcpyAsync(extra, start, start_bytes, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemcpyAsync(extra + start_bytes, delta, delta_bytes, hipMemcpyHostToDevice, b->stream));
+    RgaArgs au;
+    au.start = (const int32_t *)extra; au.delta = extra + start_bytes; au.Q = Q; au.A = A;
+    const size_t lds = rga_lds_bytes(b->d.S);
+    const int tpw = tiles_per_wave(b->d.S);
+    auto kf = tpw == 3 ? k_region_automaton<3> : (tpw == 8 ? k_region_automaton<8> : k_region_automaton<16>);
+    if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return run_queries(b, r0, nr, nq, queries, (int)Q, KID_NONE, "region_automaton: a backward step has a zero or non-finite normaliser", logp_out,
+                       [&](const Dev &dv, int r, int n, int, int use_wb, const int32_t *dq, int nqc, double *out, uint32_t *flags) {
+        ra.queries = dq; ra.nq = nqc;
+        hipLaunchKernelGGL(kf, dim3((unsigned)nqc, n), dim3(RGN_NT), lds, b->stream, dv, r, use_wb, ra, au, out, flags);
+    });
+}
+
 #ifdef RMX_KBEST_COUNT
 // (instrumented builds only, tools/region_alternatives_time.py: the two counters of k_region_kbest, read and optionally reset)
 int rmx_kbest_counts(rmx_batch *b, uint64_t *out, int32_t reset) { BIND(b);

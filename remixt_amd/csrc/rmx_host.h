@@ -9,6 +9,7 @@
 //   kbest_k_ok, kbest_plan                                rmx_region_kbest: the rank rule and the chunks of a call
 //   extremes_ncol_ok, check_levels  rmx_region_extremes: the column rule, and that no level entry is negative
 //   locus_shape_ok, check_locus_lengths  rmx_locus_joint: the table and slot rule, and that a profile query fits its slots
+//   automaton_shape_ok, check_automata, check_symbols  rmx_region_automaton: the shape rule, and that every transition, start state and symbol is in range
 //   check_pairs, check_permutations  rmx_restart_overlap: the restart pairs lie inside the two batches, every permutation row is a bijection
 //   weighted_search      rmx_weighted_search: numpy's cumsum / searchsorted(side='right') for the weighted M-step samples
 //                        (reference remixt/cn_model.py:475-480)
@@ -247,6 +248,34 @@ inline int64_t check_locus_lengths(int32_t nq, const int32_t *queries, int32_t n
     }
     if (reason) *reason = why;
     return bad;
+}
+
+// rmx_region_automaton.  Its shape rule: 1 <= Q <= AUTOMATON_MAX_STATES (the columns of the matrix instruction's B operand),
+// 1 <= A <= AUTOMATON_MAX_SYMBOLS (the rows of the kernel's predecessor table), 1 <= nauto <= AUTOMATON_MAX_AUTOMATA
+constexpr int32_t AUTOMATON_MAX_STATES = 16;
+constexpr int32_t AUTOMATON_MAX_SYMBOLS = 16;
+constexpr int32_t AUTOMATON_MAX_AUTOMATA = 64;
+inline bool automaton_shape_ok(int32_t nauto, int32_t Q, int32_t A) {
+    return nauto >= 1 && nauto <= AUTOMATON_MAX_AUTOMATA && Q >= 1 && Q <= AUTOMATON_MAX_STATES && A >= 1 && A <= AUTOMATON_MAX_SYMBOLS;
+}
+// the transition tables delta [nauto][Q][A] hold states in [0, Q) and start [nauto] does.  Returns the index of the first bad
+// entry -- of delta as a flat index, of start[i] as nauto Q A + i -- -1 if there is none, or -2 for arguments that describe no
+// tables (a shape outside the rule, or a missing pointer)
+inline int64_t check_automata(int32_t nauto, int32_t Q, int32_t A, const uint8_t *delta, const int32_t *start) {
+    if (!automaton_shape_ok(nauto, Q, A) || !delta || !start) return -2;
+    const int64_t n = (int64_t)nauto * Q * A;      // (at most 64 x 16 x 16)
+    for (int64_t i = 0; i < n; i++) if ((int32_t)delta[i] >= Q) return i;
+    for (int32_t i = 0; i < nauto; i++) if (start[i] < 0 || start[i] >= Q) return n + i;
+    return -1;
+}
+// the symbol tables [C][nsym][S] of a call hold symbols in [0, A).  Returns the index of the first entry outside, -1 if there
+// is none, or -2 for arguments that describe no table (a negative extent, A < 1, or entries without a pointer)
+inline int64_t check_symbols(int64_t C, int64_t nsym, int64_t S, int32_t A, const int16_t *symbols) {
+    if (C < 0 || nsym < 0 || S < 0 || A < 1) return -2;
+    const uint64_t n = (uint64_t)C * (uint64_t)nsym * (uint64_t)S;      // (each extent is below 2^31 in a batch; the caller's are int32)
+    if (n > 0 && !symbols) return -2;
+    for (uint64_t i = 0; i < n; i++) if (symbols[i] < 0 || (int32_t)symbols[i] >= A) return (int64_t)i;
+    return -1;
 }
 
 // rmx_restart_overlap.  Its pairs [npairs][2]: a restart of batch A in [0, RA) and one of batch B in [0, RB).  Returns the index

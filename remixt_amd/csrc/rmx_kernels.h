@@ -8158,6 +8158,231 @@ __global__ __launch_bounds__(RGN_NT) void k_restart_overlap(Dev d, int use_wb, R
 }
 
 // =============================================================================
+// Region automata: for a query (a, b, symbol table, automaton) over the model segments [a, b] of one chain, the
+// exact distribution of the final state of a deterministic finite automaton (Q <= 16 states, A <= 16 symbols, transition table
+// delta [Q][A], start state q0) that reads one symbol per segment, sigma_n(s) = the symbol of state s under the state class of
+// segment n, FROM THE LAST SEGMENT TO THE FIRST: b, b - 1, .. a, the walk's own direction.  A segment with constrain[n] == 0
+// is not read: its state is marginalised and the automaton does not move.  The pair (copy-number state, automaton state) is a
+// Markov chain under the structured posterior: with H(s', q) = G_n+1(s', q) / D_n(s'),
+//   G_b(s, q) = post_b(s) [q = delta(q0, sigma_b(s))]                                     (b not read: [q = q0])
+//   X(s, q)   = fa_n(s) sum_s' W_n(s, s') H(s', q)
+//   G_n(s, q) = sum_{q' ascending: delta(q', sigma_n(s)) = q} X(s, q')                    (n not read: X(s, q))
+//   out(q)    = log sum_s G_a(s, q) = log P(the automaton ends in q).
+// Nothing binds: in real arithmetic the total over (s, q) is 1 at every step.  G is still divided by its total after every
+// step, the start included, and the logarithms are added up, which only removes drift.  ONE scale carries all columns, because
+// columns mix under delta: a column more than about 1e-308 below the total comes out -inf.  Nothing of the model is written.
+// One workgroup of 256 threads per (restart, query).  G lives in LDS as [S rounded up to 16][16 columns]; a step is
+//   1. the states s' with mass in any of the 16 columns (the columns >= Q stay 0: the set does not depend on Q), compacted in
+//      state order by a ballot;
+//   2. one D(s') for those, as in k_region_counts; lane j divides column j in place;
+//   3. X on v_mfma_f64_16x16x4_f64 with k_region_counts' lane map, ONE instruction per (row tile, four s'): A = W(s0 + i, s'_k)
+//      from the Wb row (or exp(trans_value)), selected to 0 where fa = 0 or s >= S, B = H(s'_k, j).  There is no masked row;
+//   4. the epilogue through LDS: fa X goes from the accumulators to G once every wave has finished reading H; thread (s, q)
+//      then adds X(s, q') for q' = 0 .. 15 in ascending order wherever bit q' of pred[sigma_n(s)][q] is set -- an operand is
+//      selected, never multiplied by 0.  pred [A][16] (16 bits each: the q' with delta(q', symbol) = q) is built once per
+//      workgroup.  A row's 16 columns belong to 16 lanes of one wave in one round: the row is read before it is written (the
+//      discipline of k_region_moments' second pass, a loop over LDS that holds no accumulator).  On a segment that is not read
+//      the epilogue is the identity.  sym: the symbol row of n in LDS, loaded after the barrier that ends the previous step's
+//      epilogue;
+//   5. the total in a fixed order, and G divided by it in place.
+// q.labels / q.nlabel carry the symbol tables; fields 2 and 3 of a query are the symbol table and the automaton (the host
+// checked them, every symbol in [0, A), every delta entry in [0, Q) and every start state).  Every sum has one order, fixed by
+// S alone: a (restart, query) result depends on neither the restart range, the other queries, the launch, nor on unreachable
+// states that pad the automaton to a larger Q (their columns hold +0, and adding +0 changes no bit).  Only columns s < S of fa /
+// post are read (clamped address and select).  A D(s') that is 0 or not finite under mass, or a total that is not a finite
+// number >= 0, sets RGN_ERR_DENOM in flags[r] and gives NaN in all Q entries; a state that cannot be reached gives -inf.
+// grid (queries, restarts), block RGN_NT, dynamic LDS rga_lds_bytes(S); out[(ri * nq + query) * Q + q].
+// =============================================================================
+static inline size_t rga_lds_bytes(int S) { const size_t SR = ((size_t)S + 15) & ~(size_t)15; return SR * (RGN_KB * 8 + 8 + 2 * 2); }
+struct RgaArgs {
+    const uint8_t *delta;     // [nauto][Q][A]
+    const int32_t *start;     // [nauto]
+    int Q, A;
+};
+// the symbol row si of segment n's class -> sym[0 .. SR), 0 at s >= S
+__device__ __forceinline__ void rga_symbol_row(const Dev &d, const RgnArgs &q, int n, int si, int S, int SR, int16_t *sym) {
+    const int16_t *sv = q.labels + ((size_t)d.seg_class[n] * q.nlabel + si) * S;
+    for (int s = threadIdx.x; s < SR; s += RGN_NT) {
+        const int v = sv[s < S ? s : S - 1];
+        sym[s] = (int16_t)(s < S ? v : 0);
+    }
+}
+template <int TPW>
+__global__ __launch_bounds__(RGN_NT) void k_region_automaton(Dev d, int r0, int use_wb, RgnArgs q, RgaArgs au, double *out, uint32_t *flags) {
+    extern __shared__ double rga_lds[];                 // G [SR][16], fas [SR], sym [SR] (int16), idx [SR] (int16)
+    __shared__ double red[RGN_NW], redc[RGN_NW][RGN_KB];
+    __shared__ uint16_t pred[RGN_KB][RGN_KB];           // [symbol][q]: bit q' set where delta(q', symbol) = q
+    __shared__ int nact, s_bad;
+    const int qi = blockIdx.x, ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (uniform, and known to be: the matrix instructions sit under conditions on it)
+    const int grp = tid / RGN_GL, gl = tid % RGN_GL;
+    const int ai = lane & 15, kk = lane >> 4;
+    const int S = d.S, SR = (S + 15) & ~15;
+    double *G = rga_lds, *fas = G + (size_t)SR * RGN_KB;
+    int16_t *sym = (int16_t *)(fas + SR), *idx = sym + SR;
+    const int a = q.queries[4 * qi], b = q.queries[4 * qi + 1], si = q.queries[4 * qi + 2], ui = q.queries[4 * qi + 3];
+    const int Q = au.Q, A = au.A;
+    const int q0 = au.start[ui];
+    if (tid == 0) s_bad = 0;
+    {
+        const uint8_t *dl = au.delta + (size_t)ui * Q * A;
+        const int sy = tid >> 4, qq = tid & 15;         // (RGN_NT = 16 symbols x 16 states)
+        unsigned m = 0u;
+        for (int p = 0; p < Q; p++) {
+            const int to = dl[p * A + (sy < A ? sy : 0)];
+            m |= (sy < A && to == qq) ? 1u << p : 0u;
+        }
+        pred[sy][qq] = (uint16_t)m;
+    }
+    double logp = 0.;
+    bool failed = false;
+    // ---- start: G_b(s, q) = post_b(s) [q = delta(q0, sigma_b(s))], or [q = q0] where b is not read ---------------------
+    {
+        const double *post = d.post + rs_off(d, r, b);
+        const bool rd = !q.constrain || q.constrain[b];
+        rga_symbol_row(d, q, b, si, S, SR, sym);
+        __syncthreads();
+        double part = 0.;
+        for (int e = tid; e < SR * RGN_KB; e += RGN_NT) {      // (e % 16 == ai: RGN_NT is a multiple of 16)
+            const int s = e / RGN_KB, sc = s < S ? s : S - 1;
+            const double pv = post[sc];
+            const bool on = rd ? ((pred[sym[s]][ai] >> q0) & 1) != 0 : ai == q0;
+            const double v = (s < S && on) ? pv : 0.;
+            G[e] = v;
+            part += v;
+        }
+        const double Z = rgn_block_sum(part, red);
+        const bool okz = rgn_take_sum(Z, false, logp, failed);
+        for (int e = tid; e < SR * RGN_KB; e += RGN_NT) G[e] = okz ? G[e] / Z : 0.;
+    }
+    for (int n = b - 1; n >= a && !failed && logp > -INFINITY; n--) {
+        const auto [wb, Wt, pd] = rgn_adj(d, r, n, use_wb);
+        const double *fa = d.fa + rs_off(d, r, n);
+        const bool rd = !q.constrain || q.constrain[n];
+        for (int s = tid; s < SR; s += RGN_NT) {
+            const int sc = s < S ? s : S - 1;
+            const double fv = fa[sc];
+            fas[s] = s < S ? fv : 0.;
+        }
+        // ---- 1. the states s' with mass in any column, in state order ------------------------------------------
+        __syncthreads();      // (G of the step before, or of the start, is complete, and its symbol row has been read)
+        if (rd) rga_symbol_row(d, q, n, si, S, SR, sym);
+        const int na = __builtin_amdgcn_readfirstlane(rgn_compact(S, idx, nact, [&](int s) {
+            bool act = false;
+            for (int k = 0; k < RGN_KB; k++) act = act || G[s * RGN_KB + k] > 0.;
+            return act;
+        }));
+        // ---- 2. D(s') and H = G / D in place ---------------------------------------------------------------------
+        if (wb) {
+            for (int j0 = 0; j0 < na; j0 += RGN_NT / RGN_GL) {
+                const int j = j0 + grp;
+                const bool ok = j < na;
+                const int sp = ok ? idx[j] : 0;
+                double p = 0.;
+                if (ok) {
+                    const double *wr = Wt + (size_t)sp * S;
+                    for (int s = gl; s < S; s += RGN_GL) p = fma(fas[s], wr[s], p);
+                }
+                const double D = group_sum(p, RGN_GL);
+                if (ok) {
+                    if (gl == 0 && !(D > 0. && D < INFINITY)) s_bad = 1;
+                    G[sp * RGN_KB + gl] = G[sp * RGN_KB + gl] / D;
+                }
+            }
+        } else {
+            for (int j = tid; j < na; j += RGN_NT) {
+                const int sp = idx[j];
+                const double D = rgn_D_exp(d, n, sp, fas, pd);
+                if (!(D > 0. && D < INFINITY)) s_bad = 1;
+                for (int k = 0; k < RGN_KB; k++) G[sp * RGN_KB + k] = G[sp * RGN_KB + k] / D;
+            }
+        }
+        __syncthreads();
+        // ---- 3. X on the matrix cores: one instruction per (row tile, four s') -----------------------------------
+        psm_d4 acc[TPW];
+        bool rowlive[TPW];    // the lane's A row of tile u is a state the walk can pass
+#pragma unroll
+        for (int u = 0; u < TPW; u++) {
+            acc[u] = psm_d4{0., 0., 0., 0.};
+            const int s = (wave + RGN_NW * u) * 16 + ai;
+            rowlive[u] = s < S && fas[s < SR ? s : 0] != 0.;
+        }
+        for (int j0 = 0; j0 < na; j0 += 4) {
+            const int j = j0 + kk;
+            const bool ok = j < na;
+            const int sp = idx[ok ? j : 0];
+            const double hv = G[sp * RGN_KB + ai];
+            const double bv = ok ? hv : 0.;
+#pragma unroll
+            for (int u = 0; u < TPW; u++) {
+                const int s0 = (wave + RGN_NW * u) * 16;
+                if (s0 < S) {         // (uniform over the wave)
+                    const int s = s0 + ai, sc = s < S ? s : S - 1;
+                    const bool live = ok && rowlive[u];
+                    double wv;
+                    if (wb) wv = Wt[(size_t)sp * S + sc];
+                    else wv = live ? exp(trans_value(d, n, sc, sp, pd)) : 0.;
+                    acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(live ? wv : 0., bv, acc[u], 0, 0, 0);
+                }
+            }
+        }
+        // ---- 4. fa X to LDS once every wave has finished reading H, then G_n(s, q) from the row of X ------------------
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < TPW; u++) {
+            const int s0 = (wave + RGN_NW * u) * 16;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int s = s0 + kk + 4 * g;
+                if (s < SR) {
+                    const double fv = fas[s];
+                    G[s * RGN_KB + ai] = fv != 0. ? fv * acc[u][g] : 0.;
+                }
+            }
+        }
+        __syncthreads();
+        // (a row's 16 columns belong to 16 lanes of one wave in one round: every lane has read the row before any lane of the wave
+        // writes it)
+        double part = 0.;
+        if (rd) {
+#pragma unroll 1
+            for (int e = tid; e < SR * RGN_KB; e += RGN_NT) {         // (column e % 16 == ai)
+                const int s = e / RGN_KB;
+                const unsigned pm = pred[sym[s]][ai];
+                const double *xr = G + s * RGN_KB;
+                double v = 0.;
+#pragma unroll
+                for (int p = 0; p < RGN_KB; p++) {
+                    const double x = xr[p];
+                    v += ((pm >> p) & 1u) ? x : 0.;
+                }
+                G[e] = v;
+                part += v;
+            }
+        } else {
+            for (int e = tid; e < SR * RGN_KB; e += RGN_NT) part += G[e];
+        }
+        // ---- 5. the total in a fixed order (its barriers also publish G), and G divided by it ------------------------------
+        const double Z = rgn_block_sum(part, red);
+        const bool okz = rgn_take_sum(Z, s_bad != 0, logp, failed);
+        for (int e = tid; e < SR * RGN_KB; e += RGN_NT) G[e] = okz ? G[e] / Z : 0.;
+    }
+    // ---- out(q) = log sum_s G_a(s, q) -------------------------------------------------------------------------------
+    __syncthreads();
+    {
+        const double t = rgn_column_sums(G, S, Q, redc);
+        if (tid < Q) {
+            double v;
+            if (failed) v = __builtin_nan("");
+            else if (!(logp > -INFINITY) || t == 0.) v = -INFINITY;
+            else v = logp + log(t);
+            out[((size_t)ri * q.nq + qi) * Q + tid] = v;
+        }
+    }
+    if (tid == 0 && failed) atomicOr(&flags[r], RGN_ERR_DENOM);
+}
+
+// =============================================================================
 // Region alternatives: the K most probable pairwise distinct configurations of a region under the structured posterior of the
 // last update_p_cn, and their probabilities (K <= 8).  It is k_region_decode's recursion with a rank axis: every state keeps
 // its K best partial paths instead of one,

@@ -5,6 +5,8 @@ segment's state class; the device evaluates all of them in one read of the margi
 `RemixtBatch.posterior_summary_raw`).  This module is the host side: the weight tables (`feature_matrix`), the map from a
 decoded path back to state indices (`cn_to_states`), the named arrays of a result (`unpack`) and the two whole-genome
 expectations (`summary_stats`).  numpy only."""
+import collections
+
 import numpy as np
 
 # the arrays a fit result gains with config cn_posterior_summary (all in experiment segment order) and the two stats
@@ -2080,3 +2082,212 @@ def batch_locus_dependence(batch, r0, nr, anchors, seg_fwd_remap, seg_is_origina
                 res[k][:, sl] = s[k]
     out.update(res)
     return out
+
+
+# ---- posterior of regular path events: automaton queries over regions (rmx_region_automaton) ---------------
+# delta int (Q, A): delta[q, x] the state after reading symbol x in state q; start the start state; alphabet = A; value an int
+# per state (the count the state stands for, say) or None.  THE DEVICE READS A REGION FROM ITS LAST SEGMENT TO ITS FIRST: the
+# builders below are symmetric under reversal, reverse_automaton turns a left-to-right automaton into one for that order.
+Automaton = collections.namedtuple('Automaton', 'delta start alphabet value')
+_AUTOMATON_MAX = 16
+
+
+def _event_table(cn_classes, event):
+    """A boolean (C, S) table: a mask name of MASK_NAMES, or the table itself."""
+    cn = np.asarray(cn_classes)
+    if isinstance(event, str):
+        if event not in MASK_NAMES:
+            raise ValueError('unknown event %r: one of %s, or a boolean (classes, states) table' % (event, ', '.join(MASK_NAMES)))
+        return event_tables(cn)[0][:, MASK_NAMES.index(event)] != 0
+    tab = np.asarray(event)
+    if tab.shape != cn.shape[:2]:
+        raise ValueError('an event table must have shape (num_classes, num_cn_states)')
+    return tab != 0
+
+
+def symbols_from(cn_classes, parts):
+    """A symbol table int16 (C, S) from at most 15 parts, each a mask name of MASK_NAMES or a boolean (classes, states)
+    table: the symbol of a state is 1 + the index of the first part that holds there, 0 if none holds."""
+    parts = list(parts)
+    if len(parts) > _AUTOMATON_MAX - 1:
+        raise ValueError('at most %d parts' % (_AUTOMATON_MAX - 1))
+    cn = np.asarray(cn_classes)
+    sym = np.zeros(cn.shape[:2], dtype=np.int16)
+    for i in reversed(range(len(parts))):
+        sym[_event_table(cn, parts[i])] = i + 1
+    return sym
+
+
+def level_mask(cn_classes, quantity, clone, lo, hi):
+    """A boolean (C, S) table: lo <= quantity <= hi, quantity 'total', 'major' or 'minor' of tumour clone 1 .. M-1, or with
+    clone 'any' the highest over the tumour clones."""
+    q = _level_quantity(cn_classes, quantity)
+    M = np.asarray(cn_classes).shape[2]
+    if clone != 'any' and not (isinstance(clone, (int, np.integer)) and 1 <= clone < M):
+        raise ValueError('clone must be a tumour clone 1 .. %d or \'any\'' % (M - 1))
+    v = q.max(axis=-1) if clone == 'any' else q[:, :, clone - 1]
+    return (v >= lo) & (v <= hi)
+
+
+def automaton_runs(bins):
+    """The number of maximal runs of symbol 1 among the read segments (alphabet 2).  State 2 c + e: c runs so far, saturating
+    at bins - 1 (the last count means bins - 1 or more), e whether the last read segment was in the event.  Q = 2 bins,
+    bins <= 8; value is c."""
+    bins = int(bins)
+    if not 1 <= bins <= 8:
+        raise ValueError('bins must be in 1 .. 8')
+    delta = np.zeros((2 * bins, 2), dtype=np.uint8)
+    for c in range(bins):
+        for e in (0, 1):
+            delta[2 * c + e, 0] = 2 * c
+            delta[2 * c + e, 1] = 2 * c + 1 if e else 2 * min(c + 1, bins - 1) + 1
+    return Automaton(delta, 0, 2, tuple(c for c in range(bins) for _ in (0, 1)))
+
+
+def automaton_run_of(k):
+    """Whether some run of symbol 1 spans at least k read segments (alphabet 2).  The state is the length of the current run,
+    state k absorbing: P(state k) is the answer.  Q = k + 1, 1 <= k <= 15; value is the state itself."""
+    k = int(k)
+    if not 1 <= k <= 15:
+        raise ValueError('k must be in 1 .. 15')
+    delta = np.zeros((k + 1, 2), dtype=np.uint8)
+    for q in range(k + 1):
+        delta[q, 0] = k if q == k else 0
+        delta[q, 1] = min(q + 1, k)
+    return Automaton(delta, 0, 2, tuple(range(k + 1)))
+
+
+def automaton_switches(bins):
+    """The number of switches between two levels (alphabet 3: symbols 1 and 2 are the levels, symbol 0 is ignored).  State 0:
+    neither level read yet; state 1 + 2 c + (v - 1): c switches so far, saturating at bins - 1, the level read last v.
+    Q = 1 + 2 bins, bins <= 7; value is c."""
+    bins = int(bins)
+    if not 1 <= bins <= 7:
+        raise ValueError('bins must be in 1 .. 7')
+    delta = np.zeros((1 + 2 * bins, 3), dtype=np.uint8)
+    delta[0] = (0, 1, 2)
+    for c in range(bins):
+        for v in (1, 2):
+            q = 1 + 2 * c + (v - 1)
+            delta[q, 0] = q
+            delta[q, v] = q
+            delta[q, 3 - v] = 1 + 2 * min(c + 1, bins - 1) + (2 - v)
+    return Automaton(delta, 0, 3, (0,) + tuple(c for c in range(bins) for _ in (0, 1)))
+
+
+def _check_automaton(automaton):
+    delta = np.asarray(automaton.delta)
+    if delta.ndim != 2 or not (1 <= delta.shape[0] <= _AUTOMATON_MAX and 1 <= delta.shape[1] <= _AUTOMATON_MAX):
+        raise ValueError('delta must have shape (Q, A) with Q and A in 1 .. %d' % _AUTOMATON_MAX)
+    Q = delta.shape[0]
+    if delta.min() < 0 or delta.max() >= Q or not 0 <= int(automaton.start) < Q:
+        raise ValueError('delta and start must hold states in [0, Q)')
+    return delta.astype(np.uint8), int(automaton.start)
+
+
+def reverse_automaton(delta, start, accept):
+    """For users who think left to right: a deterministic automaton (delta (Q, A), start, accept: the accepting states, as
+    indices or a boolean (Q,)) that reads a region first segment to last -> (Automaton, accept' boolean) that accepts the
+    same regions read last segment to first, by the subset construction of the reversed language: a state is the set of
+    original states from which the symbols read so far lead to acceptance.  ValueError above 16 states."""
+    delta = np.asarray(delta, dtype=np.int64)
+    Q, A = delta.shape
+    acc = np.zeros(Q, dtype=bool)
+    acc[np.asarray(accept)] = True
+    first = frozenset(np.flatnonzero(acc).tolist())
+    index, rows, todo = {first: 0}, [], [first]
+    while todo:
+        cur = todo.pop(0)
+        row = []
+        for x in range(A):
+            nxt = frozenset(q for q in range(Q) if int(delta[q, x]) in cur)
+            if nxt not in index:
+                if len(index) >= _AUTOMATON_MAX:
+                    raise ValueError('the reversed automaton has more than %d states' % _AUTOMATON_MAX)
+                index[nxt] = len(index)
+                todo.append(nxt)
+            row.append(index[nxt])
+        rows.append(row)
+    sets = sorted(index, key=index.get)
+    return (Automaton(np.array(rows, dtype=np.uint8), 0, A, None), np.array([int(start) in s for s in sets], dtype=bool))
+
+
+def _one_chain_queries(regions, seg_fwd_remap, seg_is_original, is_telomere, what):
+    cs, ce = chains_from_telomeres(is_telomere)
+    runs, piece_region, constrain = region_queries(regions, seg_fwd_remap, seg_is_original, cs, ce)
+    R = len(np.asarray(regions).reshape(-1, 2))
+    split = np.flatnonzero(np.bincount(piece_region, minlength=R) > 1)
+    if len(split):
+        reg = np.asarray(regions).reshape(-1, 2)[split[0]]
+        raise ValueError('%s: region %d (%d, %d) lies in two chains: the automaton\'s state does not cross a chain end' % (what, split[0], reg[0], reg[1]))
+    return runs, constrain, R
+
+
+def batch_region_automaton(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, automaton, symbols, accept=None):
+    """The exact distribution of the final state of `automaton` (an Automaton) over regions, for restarts r0 .. r0+nr-1 of a
+    RemixtBatch from one device call (rmx_region_automaton).  regions: (first, last) experiment segment indices, each inside
+    one chain (ValueError otherwise).  symbols: an int (classes, states) table with entries in [0, alphabet), as symbols_from
+    gives.  The automaton reads a region FROM ITS LAST SEGMENT TO ITS FIRST; zero-length segments inserted at shared
+    boundaries are not read.  A dict of `log_final` and `final` (nr, R, Q), and with accept (state indices or a boolean (Q,))
+    `p_accept` (nr, R)."""
+    delta, start = _check_automaton(automaton)
+    sym = np.asarray(symbols)
+    if sym.shape != np.asarray(batch.cn_classes).shape[:2]:
+        raise ValueError('symbols must have shape (num_classes, num_cn_states)')
+    runs, constrain, R = _one_chain_queries(regions, seg_fwd_remap, seg_is_original, is_telomere, 'region_automaton')
+    Q = delta.shape[0]
+    lf = np.zeros((nr, R, Q))
+    if R:
+        q = np.zeros((R, 4), dtype=np.int32)
+        q[:, :2] = runs
+        lf = batch.region_automaton_raw(r0, nr, q, sym[:, None, :], delta[None], np.array([start]), constrain)
+    with np.errstate(over='ignore'):
+        out = {'log_final': lf, 'final': np.exp(lf)}
+    if accept is not None:
+        acc = np.zeros(Q, dtype=bool)
+        acc[np.asarray(accept)] = True
+        out['p_accept'] = np.clip(out['final'][..., acc].sum(axis=-1), 0., 1.)
+    return out
+
+
+def _piece_final(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, automaton, event):
+    """(final (nr, P, Q) probabilities of every region piece, piece_region, R): one query per piece of a region split at chain ends."""
+    delta, start = _check_automaton(automaton)
+    sym = symbols_from(batch.cn_classes, [event])
+    cs, ce = chains_from_telomeres(is_telomere)
+    runs, piece_region, constrain = region_queries(regions, seg_fwd_remap, seg_is_original, cs, ce)
+    P, R = len(runs), len(np.asarray(regions).reshape(-1, 2))
+    if P == 0:
+        return np.zeros((nr, 0, delta.shape[0])), piece_region, R
+    q = np.zeros((P, 4), dtype=np.int32)
+    q[:, :2] = runs
+    with np.errstate(over='ignore'):
+        return np.exp(batch.region_automaton_raw(r0, nr, q, sym[:, None, :], delta[None], np.array([start]), constrain)), piece_region, R
+
+
+def batch_event_runs(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, event, bins=8):
+    """How many separate events a region holds: the distribution of the number of maximal runs of real segments in `event` (a
+    mask name of MASK_NAMES or a boolean (classes, states) table), for restarts r0 .. r0+nr-1 of a RemixtBatch from one
+    device call.  A dict of `num_events` (nr, R, bins) -- entry k the probability of exactly k runs, the last that of
+    bins - 1 or more -- and `p_any` (nr, R), the probability of at least one.  A run cannot cross a chromosome end, so the
+    pieces of a region split at chain ends are asked one by one and their counts add (combine_counts); zero-length segments
+    inserted at shared boundaries neither start, extend nor end a run."""
+    au = automaton_runs(bins)
+    bins = len(au.value) // 2
+    final, piece_region, R = _piece_final(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, au, event)
+    pmf = final.reshape(final.shape[:2] + (bins, 2)).sum(axis=-1)
+    with np.errstate(divide='ignore'):
+        counts = np.clip(combine_counts(np.log(pmf), piece_region, R), 0., 1.)
+    return {'num_events': counts, 'p_any': np.clip(1. - counts[..., 0], 0., 1.)}
+
+
+def batch_event_run_of(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, event, k):
+    """Whether `event` (as batch_event_runs) is supported by at least k consecutive real segments somewhere in a region: a dict
+    of `p_run` (nr, R).  Pieces of a region split at chain ends are joined as 1 - prod (1 - p): chains are independent and a
+    run cannot cross a chromosome end."""
+    au = automaton_run_of(k)
+    final, piece_region, R = _piece_final(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, au, event)
+    miss = np.ones((nr, R))
+    for j, reg in enumerate(np.asarray(piece_region)):
+        miss[:, reg] *= np.clip(1. - final[:, j, -1], 0., 1.)
+    return {'p_run': 1. - miss}

@@ -6,7 +6,7 @@ The four classes that answer queries -- cn_model.BreakpointModel (one restart), 
 batch), restarts.RestartGroups (several batches) and restarts.DatasetGroups (several datasets) -- get their methods from
 this table through the class decorator `answers`: one generic body per level below, no code per (query, level).
 
-Adding a query: its posteriors.batch_* function, and its entry here, in LATER_QUERIES (QUERIES itself is a closed list).
+Adding a query: its posteriors.batch_* function, and its entry here, in a later tuple such as AUTOMATON_QUERIES (QUERIES and LATER_QUERIES are closed lists).
 
 (posteriors imports nothing of this package when it loads, and this module imports posteriors alone, so cn_model and
 restarts load it at import time without a cycle.  sample_cn, restart_overlap and ploidy_posterior_sd are no entries: the
@@ -280,7 +280,41 @@ def locus_dependence(q, anchors, window=32, feature=('total', 1), other=None, bi
 
 # (QUERIES is a closed list: tests compare its names with theirs.  Later entries go here; BY_NAME and `answers` run over both)
 LATER_QUERIES = (locus_joint, locus_dependence)
-BY_NAME = dict((e.name, e) for e in QUERIES + LATER_QUERIES)
+
+
+@_query('region_automaton_raw', 'has no region automata', 'a dict of arrays (restarts, len(regions), ...)')
+def region_automaton(q, regions, automaton, symbols, accept=None):
+    """The exact posterior, under the structured posterior of the last variational update, of a regular property of regions
+    ((first, last) experiment segment indices, each inside one chain): automaton is a posteriors.Automaton with at most 16
+    states over at most 16 symbols -- posteriors.automaton_runs, automaton_run_of, automaton_switches, or
+    posteriors.reverse_automaton of a left-to-right one --, symbols an int (classes, states) table as posteriors.symbols_from
+    gives.  The automaton reads a region FROM ITS LAST SEGMENT TO ITS FIRST, one symbol per real segment.  A dict of `log_final`
+    and `final` (len(regions), Q), the distribution of the automaton's final state, and with accept (state indices or a
+    boolean per state) `p_accept` (len(regions),)."""
+    return posteriors.batch_region_automaton(*q.at, regions, *q.maps, automaton=automaton, symbols=symbols, accept=accept)
+
+
+@_query('region_automaton_raw', 'has no region automata', 'a dict of arrays (restarts, len(regions), ...)')
+def event_runs(q, regions, event, bins=8):
+    """How many separate events regions hold ((first, last) experiment segment indices): three distinct homozygous deletions
+    or one.  event is a mask name of posteriors.MASK_NAMES or a boolean (classes, states) table (posteriors.level_mask).  A
+    dict of `num_events` (len(regions), bins) -- entry k the exact posterior probability of exactly k maximal runs of real
+    segments in the event, the last entry that of bins - 1 or more -- and `p_any` (len(regions),).  A run does not cross a
+    chromosome end."""
+    return posteriors.batch_event_runs(*q.at, regions, *q.maps, event=event, bins=bins)
+
+
+@_query('region_automaton_raw', 'has no region automata', 'a dict of arrays (restarts, len(regions))')
+def event_run_of(q, regions, event, k):
+    """Whether an event (as event_runs) is supported by at least k consecutive real segments somewhere in a region: a dict of
+    `p_run` (len(regions),), the exact posterior probability.  A one-segment blip is not a call."""
+    return posteriors.batch_event_run_of(*q.at, regions, *q.maps, event=event, k=k)
+
+
+# (LATER_QUERIES is compared with a closed list too; the automaton queries have a tuple of their own)
+AUTOMATON_QUERIES = (region_automaton, event_runs, event_run_of)
+ALL_QUERIES = QUERIES + LATER_QUERIES + AUTOMATON_QUERIES
+BY_NAME = dict((e.name, e) for e in ALL_QUERIES)
 
 
 # ---- a result along the restart axis ----------------------------------------------------------------------------------------
@@ -404,7 +438,7 @@ def answers(level):
     body, doc = LEVELS[level]
 
     def install(cls):
-        for entry in QUERIES + LATER_QUERIES:
+        for entry in ALL_QUERIES:
             setattr(cls, entry.name, _method(cls, entry, body, doc(entry)))
         return cls
     return install

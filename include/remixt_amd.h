@@ -685,6 +685,26 @@ int rmx_region_automaton(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const
                          int32_t nauto, int32_t Q, int32_t A, const uint8_t *delta, const int32_t *start, const uint8_t *constrain,
                          double *logp_out);
 
+/* Path entropy: the exact Shannon entropy, in nats, of the copy-number path posterior over any run of segments,
+ * as two arrays from which the host forms every run's entropy by prefix sums.  Under the structured posterior of the last
+ * update_p_cn (the forward recursion of bpmodel.pyx:1213-1246) a chain is Markov with the backward kernel
+ * q(c_n = s | c_n+1 = s') = fa_n(s) W_n(s, s') / D_n(s'), so  H(c_a .. c_b) = marg_b + sum_{n = a}^{b-1} step_n  with, for an
+ * adjacency n -> n + 1 and post, fa, W_n as in rmx_region_prob,
+ *   D(s')  = sum_s fa_n(s) W_n(s, s')
+ *   E1(s') = sum_s fa_n(s) log fa_n(s) W_n(s, s')            (fa = 0: the term is 0)
+ *   E2(s') = sum_s fa_n(s) W_n(s, s') log W_n(s, s')         (W = 0: the term is 0)
+ *   step_n = H(c_n | c_n+1) = sum_{s': post_n+1(s') > 0} post_n+1(s') (log D(s') - (E1(s') + E2(s')) / D(s'))
+ *   marg_n = H(post_n) = -sum_{s: post_n(s) > 0} post_n(s) log post_n(s)
+ * marginal_out, step_out [nr][n1 - n0]: entry n - n0 of a restart's row; either may be NULL, not both.  step_n is +0.0 where
+ * segment n ends a chain (there is no adjacency).  Both are >= 0; a sum that rounding left below zero is returned as +0.0.
+ * The scale of a row of fa cancels.  The model is not modified.
+ * An entry is bit-identical in any restart range, any segment range and any chunking.
+ * Errors: RMX_EARG with nothing launched and the outputs untouched for a bad restart range, a segment range without
+ * 0 <= n0 < n1 <= num_segments, or two NULL outputs; RMX_EVALUE with the restarts listed before update_p_cn; RMX_EASSERT with
+ * the restarts listed where a D(s') is 0 or not finite under post_n+1(s') > 0 or a result is not a finite number: that entry is
+ * NaN; RMX_EUNSUPPORTED above 1024 states.  The kernels have no profile id. */
+int rmx_path_entropy(rmx_batch *b, int32_t r0, int32_t nr, int32_t n0, int32_t n1, double *marginal_out, double *step_out);
+
 /* -- module-level functions on caller-supplied dense inputs ----------------- */
 /* sum_product (:1213-1246): f [N][S], T [N-1][S][S] -> alphas, betas [N][S] */
 int rmx_sum_product(const double *f, const double *T, double *alphas, double *betas,

@@ -726,6 +726,21 @@ class RemixtBatch(object):
                                                 obuf.ctypes.data_as(_dp)))
         return out
 
+    def path_entropy_raw(self, r0, nr, n0=0, n1=None):
+        """The two arrays from which the entropy (nats) of the copy-number path posterior over any run of model segments
+        follows, under the structured posterior of the last update_p_cn of restarts r0 .. r0+nr-1 (rmx_path_entropy), for the
+        model segments n0 .. n1-1 (n1 None: to the last): (marginal, step), (nr, n1 - n0) each.  marginal[n] = H(post_n);
+        step[n] = H(c_n | c_n+1), +0.0 where segment n ends a chain.  H(c_a .. c_b) = marginal[b] + sum step[a .. b-1] inside
+        one chain (posteriors.entropy_runs)."""
+        r0, nr, n0 = int(r0), int(nr), int(n0)
+        n1 = self.num_segments if n1 is None else int(n1)
+        width = n1 - n0 if 0 <= n0 < n1 <= self.num_segments else 1
+        marg = np.zeros((max(nr, 0), width), dtype=np.float64)
+        step = np.zeros((max(nr, 0), width), dtype=np.float64)
+        mbuf, sbuf = (marg, step) if marg.size else (np.zeros(1), np.zeros(1))
+        self._ck(self._lib.rmx_path_entropy(self._handle, r0, nr, n0, n1, mbuf.ctypes.data_as(_dp), sbuf.ctypes.data_as(_dp)))
+        return marg, step
+
     def restart_overlap_raw(self, other, pairs, queries, perms, mode):
         """log Z (npairs, nq) of the structured posteriors of pairs of restarts over runs of model segments
         (rmx_restart_overlap): Z = sum_x q_A(x)^lam q_B(pi x)^mu, mode 0 the Bhattacharyya overlap (lam = mu = 1/2), mode 1 the
@@ -1182,6 +1197,11 @@ class RemixtModel(object):
     def region_automaton(self, queries, symbols, delta, start, constrain=None):
         """RemixtBatch.region_automaton_raw of this model: log-probabilities (nq, Q)."""
         return self._batch.region_automaton_raw(self._r, 1, queries, symbols, delta, start, constrain)[0]
+
+    def path_entropy(self, n0=0, n1=None):
+        """RemixtBatch.path_entropy_raw of this model: (marginal, step), (n1 - n0,) each."""
+        marg, step = self._batch.path_entropy_raw(self._r, 1, n0, n1)
+        return marg[0], step[0]
 
     def region_moments(self, queries, features, weights, nf):
         """RemixtBatch.region_moments_raw of this model: means and covariances (nq, nf + nf (nf + 1) / 2)."""

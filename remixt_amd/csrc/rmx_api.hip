@@ -64,7 +64,8 @@ static const char *kLaterKernelNames[KID_PROFILE_ALL - KID_ALL] = {"k_region_con
 // The third range is closed too (tests/test_conditional_posterior_cpu.py pins rmx_num_profile_ids() == rmx_num_kernels() + 1 with
 // k_region_conditional last, tests/test_hip_region_conditional.py pins RMX_EARG at rmx_num_profile_ids()): k_region_kbest has no
 // profile id.  Its launches run without a ProfScope; tools time it with rmx_timer_start / rmx_timer_stop.  Nor has k_locus_joint:
-// it goes through run_queries with KID_NONE, under which run_queries opens no ProfScope.
+// it goes through run_queries with KID_NONE, under which run_queries opens no ProfScope.  Nor have k_path_entropy and
+// k_path_entropy_adj: rmx_path_entropy launches them without a ProfScope.
 enum { KID_NONE = -1 };
 
 struct ProfRec { int id; hipEvent_t a, b; };
@@ -3911,6 +3912,62 @@ int rmx_region_automaton(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const
         ra.queries = dq; ra.nq = nqc;
         hipLaunchKernelGGL(kf, dim3((unsigned)nqc, n), dim3(RGN_NT), lds, b->stream, dv, r, use_wb, ra, au, out, flags);
     });
+}
+
+// Path entropy (k_path_entropy, k_path_entropy_adj): marg_n = H(post_n) and step_n = H(c_n | c_n+1) of the segments
+// [n0, n1) of restarts r0 .. r0+nr-1, from the fa plane, the transition snapshot and the marginals of the last update_p_cn.  The
+// range is cut into chunks of rmxh::entropy_chunk segments so that the two output planes of a chunk stay within the 64 MiB
+// staging buffer run_queries uses (b->d_rgn); a chunk's work lists (rmxh::entropy_tiles: tiles of 16 plain adjacencies of one
+// transition class, then the breakend adjacencies, then the chain ends, which only get their marginal entropy) are staged in the
+// table buffer.  Within a chunk, one launch of each kernel per run of restarts of one transition model.  Every (restart,
+// adjacency) is computed on its own in an order fixed by the state count: neither range nor the chunking changes a bit of it.
+// The kernels have no profile id.
+int rmx_path_entropy(rmx_batch *b, int32_t r0, int32_t nr, int32_t n0, int32_t n1, double *marginal_out, double *step_out) { BIND(b);
+    if (!b || r0 < 0 || nr < 1 || (int64_t)r0 + nr > b->R) return fail(RMX_EARG, "bad restart range");
+    if (!rmxh::entropy_range_ok(b->d.N, n0, n1)) return fail(RMX_EARG, "path_entropy: needs 0 <= n0 < n1 <= num_segments");
+    if (!marginal_out && !step_out) return fail(RMX_EARG, "path_entropy: no output requested");
+    if (b->d.S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "path_entropy: more than 1024 states");
+    int rc;
+    if ((rc = require_snapshot(b, r0, nr, "path_entropy"))) return rc;
+    if (!b->d_rflags && (rc = dalloc(b, &b->d_rflags, b->R))) return rc;
+    const int nseg = n1 - n0, nrc = std::min(nr, 65535);
+    const int chunk = (int)rmxh::entropy_chunk(nrc, nseg, (int64_t)64 << 20);
+    if ((rc = grow(b, &b->d_rgn, &b->rgn_cap, (size_t)2 * nrc * chunk))) return rc;
+    double *dmarg = b->d_rgn, *dstep = b->d_rgn + (size_t)nrc * chunk;
+    const int tpw = tiles_per_wave(b->d.S);
+    auto kf = tpw == 3 ? k_path_entropy<3> : (tpw == 8 ? k_path_entropy<8> : k_path_entropy<16>);
+    HIPCHK(hipMemsetAsync(b->d_rflags + r0, 0, sizeof(uint32_t) * nr, b->stream));
+    std::vector<std::vector<int32_t>> lists;      // (kept until the stream has run: the copies below read them)
+    for (int c0 = n0; c0 < n1; c0 += chunk) {
+        const int c1 = std::min(n1, c0 + chunk), nc = c1 - c0;
+        const rmxh::EntropyCounts cnt = rmxh::entropy_tiles(c0, c1, b->tclass.data(), b->brk_slot.data(), b->d.TC, nullptr, nullptr);
+        if (cnt.tiles < 0) return fail(RMX_EARG, "path_entropy: no work lists");
+        const size_t tile_ints = (size_t)cnt.tiles * (1 + rmxh::ENTROPY_TILE);
+        lists.emplace_back(tile_ints + (size_t)nc);
+        std::vector<int32_t> &L = lists.back();
+        rmxh::entropy_tiles(c0, c1, b->tclass.data(), b->brk_slot.data(), b->d.TC, L.data(), L.data() + tile_ints);
+        size_t nlist = (size_t)cnt.singles;
+        for (int n = c0; n < c1; n++) if (b->tclass[n] < 0) L[tile_ints + nlist++] = n;
+        if ((rc = grow(b, &b->d_rgt, &b->rgt_cap, (tile_ints + nlist) * sizeof(int32_t)))) return rc;
+        HIPCHK(hipMemcpyAsync(b->d_rgt, L.data(), (tile_ints + nlist) * sizeof(int32_t), hipMemcpyHostToDevice, b->stream));
+        const int32_t *dtiles = (const int32_t *)b->d_rgt, *dlist = dtiles + tile_ints;
+        for (int rb = 0; rb < nr; rb += nrc) {
+            const int nrr = std::min(nrc, nr - rb);
+            rc = for_model_runs(b, r0, rb, rb + nrr, [&](int i, int j, int, const Dev &dv, int use_wb) -> int {
+                double *om = dmarg + (size_t)(i - rb) * nc, *os = dstep + (size_t)(i - rb) * nc;
+                if (cnt.tiles > 0) hipLaunchKernelGGL(kf, dim3((unsigned)cnt.tiles, j - i), dim3(RGN_NT), 0, b->stream, dv, r0 + i, use_wb, dtiles, c0, nc, om, os, b->d_rflags);
+                if (nlist > 0) hipLaunchKernelGGL(k_path_entropy_adj, dim3((unsigned)nlist, j - i), dim3(RGN_NT), 0, b->stream, dv, r0 + i, dlist, c0, nc, om, os, b->d_rflags);
+                HIPCHK(hipGetLastError());
+                return RMX_OK;
+            });
+            if (rc) return rc;
+            // device [nrr][nc] -> host rows (rb .. rb+nrr)[c0 - n0 .. c1 - n0)
+            const size_t h0 = (size_t)rb * nseg + (size_t)(c0 - n0);
+            if (marginal_out) HIPCHK(hipMemcpy2DAsync(marginal_out + h0, (size_t)nseg * 8, dmarg, (size_t)nc * 8, (size_t)nc * 8, nrr, hipMemcpyDeviceToHost, b->stream));
+            if (step_out) HIPCHK(hipMemcpy2DAsync(step_out + h0, (size_t)nseg * 8, dstep, (size_t)nc * 8, (size_t)nc * 8, nrr, hipMemcpyDeviceToHost, b->stream));
+        }
+    }
+    return report_flags(b, b->d_rflags, r0, nr, "path_entropy: a normaliser is zero or not finite under posterior mass, or an entropy is not finite");
 }
 
 #ifdef RMX_KBEST_COUNT

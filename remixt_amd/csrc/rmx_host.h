@@ -10,6 +10,7 @@
 //   extremes_ncol_ok, check_levels  rmx_region_extremes: the column rule, and that no level entry is negative
 //   locus_shape_ok, check_locus_lengths  rmx_locus_joint: the table and slot rule, and that a profile query fits its slots
 //   automaton_shape_ok, check_automata, check_symbols  rmx_region_automaton: the shape rule, and that every transition, start state and symbol is in range
+//   entropy_range_ok, entropy_tiles, entropy_chunk  rmx_path_entropy: the range rule, the work lists of a range and the chunks of a call
 //   check_pairs, check_permutations  rmx_restart_overlap: the restart pairs lie inside the two batches, every permutation row is a bijection
 //   weighted_search      rmx_weighted_search: numpy's cumsum / searchsorted(side='right') for the weighted M-step samples
 //                        (reference remixt/cn_model.py:475-480)
@@ -276,6 +277,55 @@ inline int64_t check_symbols(int64_t C, int64_t nsym, int64_t S, int32_t A, cons
     if (n > 0 && !symbols) return -2;
     for (uint64_t i = 0; i < n; i++) if (symbols[i] < 0 || (int32_t)symbols[i] >= A) return (int64_t)i;
     return -1;
+}
+
+// rmx_path_entropy.  Its segment range [n0, n1) of a model of N segments: 0 <= n0 < n1 <= N
+inline bool entropy_range_ok(int64_t N, int64_t n0, int64_t n1) { return n0 >= 0 && n0 < n1 && n1 <= N; }
+// the work lists of the range [n0, n1): the plain adjacencies n -> n + 1 (tclass[n] in [0, TC), brk_slot[n] < 0) bucketed by
+// transition class, classes ascending and n ascending inside a class, into tiles of ENTROPY_TILE indices -- tiles_out
+// [tiles][1 + ENTROPY_TILE] = class, then the indices, the last tile of a class padded with -1; the breakend adjacencies
+// (tclass[n] >= 0, brk_slot[n] >= 0) in ascending n -> singles_out [singles].  Chain ends (tclass[n] < 0) go into neither.
+// Returns the two counts; with a null output pointer that list is only counted.  {-1, -1} for arguments that describe no range
+// (a negative n0, n1 < n0, missing tables, TC < 0) or a class at or beyond TC
+constexpr int32_t ENTROPY_TILE = 16;
+struct EntropyCounts { int64_t tiles, singles; };
+inline EntropyCounts entropy_tiles(int32_t n0, int32_t n1, const int32_t *tclass, const int32_t *brk_slot, int32_t TC, int32_t *tiles_out, int32_t *singles_out) {
+    if (n0 < 0 || n1 < n0 || !tclass || !brk_slot || TC < 0) return {-1, -1};
+    std::vector<int64_t> cnt((size_t)TC, 0);
+    int64_t singles = 0;
+    for (int32_t n = n0; n < n1; n++) {
+        if (tclass[n] < 0) continue;
+        if (tclass[n] >= TC) return {-1, -1};
+        if (brk_slot[n] >= 0) { if (singles_out) singles_out[singles] = n; singles++; }
+        else cnt[(size_t)tclass[n]]++;
+    }
+    // first tile of a class, then the number of indices placed in it so far
+    std::vector<int64_t> first((size_t)TC, 0);
+    int64_t tiles = 0;
+    for (int32_t c = 0; c < TC; c++) { first[(size_t)c] = tiles; tiles += (cnt[(size_t)c] + ENTROPY_TILE - 1) / ENTROPY_TILE; }
+    if (tiles_out) {
+        for (int32_t c = 0; c < TC; c++)
+            for (int64_t t = first[(size_t)c]; t < (c + 1 < TC ? first[(size_t)c + 1] : tiles); t++) {
+                int32_t *row = tiles_out + t * (1 + ENTROPY_TILE);
+                row[0] = c;
+                std::fill(row + 1, row + 1 + ENTROPY_TILE, (int32_t)-1);
+            }
+        std::fill(cnt.begin(), cnt.end(), (int64_t)0);
+        for (int32_t n = n0; n < n1; n++) {
+            if (tclass[n] < 0 || brk_slot[n] >= 0) continue;
+            const size_t c = (size_t)tclass[n];
+            const int64_t k = cnt[c]++;
+            tiles_out[(first[c] + k / ENTROPY_TILE) * (1 + ENTROPY_TILE) + 1 + k % ENTROPY_TILE] = n;
+        }
+    }
+    return {tiles, singles};
+}
+// segments per staging chunk of a call over nr restarts and nseg segments: the two output planes of a chunk, nr x chunk doubles
+// each, stay inside budget_bytes; at least 1 (a budget below one segment still makes progress), at most nseg
+inline int64_t entropy_chunk(int64_t nr, int64_t nseg, int64_t budget_bytes) {
+    if (nr < 1 || nseg < 1) return 1;
+    const int64_t per_seg = nr > INT64_MAX / 16 ? INT64_MAX : nr * 16;
+    return std::max<int64_t>(1, std::min<int64_t>(nseg, budget_bytes / per_seg));
 }
 
 // rmx_restart_overlap.  Its pairs [npairs][2]: a restart of batch A in [0, RA) and one of batch B in [0, RB).  Returns the index

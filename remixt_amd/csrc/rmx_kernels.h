@@ -8158,6 +8158,196 @@ __global__ __launch_bounds__(RGN_NT) void k_restart_overlap(Dev d, int use_wb, R
 }
 
 // =============================================================================
+// Path entropy: the two arrays from which the host forms the Shannon entropy (nats) of the path posterior over
+// any run of segments.  With post, fa, W_n and D_n as in k_region_prob, for an adjacency n -> n + 1 (tclass[n] >= 0)
+//   D(s')  = sum_s fa_n(s) W_n(s, s'),   E(s') = sum_s fa_n(s) W_n(s, s') (log fa_n(s) + log W_n(s, s'))   (a zero factor: the term is 0)
+//   step_n = H(c_n | c_n+1) = sum_{s': post_n+1(s') > 0} post_n+1(s') (log D(s') - E(s') / D(s')),   marg_n = -sum_s post_n(s) log post_n(s)
+// and step_n = +0.0 at a chain end.  The adjacencies do not depend on one another, and those of one transition class share their
+// S x S weights, so the plain ones are a product on the FP64 matrix instruction:
+//   k_path_entropy<TPW>: one workgroup per (tile of up to 16 plain adjacencies of ONE class, restart); tiles [ntiles][17] = class,
+//     then 16 segment indices, -1 padded (rmxh::entropy_tiles).  Rows of the instruction are the 16 adjacencies: the A operands
+//     fa and fa log fa come from LDS, staged PEN_KB states of the summed dimension at a time (one logarithm per (adjacency, state)).
+//     Columns are 16 states s': the B operands are rows of Wf (s' contiguous: 128-byte runs) and Wf Tval elementwise; where the
+//     snapshot's model is not the current one (use_wb == 0), exp(Tval) and Tval of the run's Dev.  A wave owns the column tiles
+//     wave + RGN_NW u, u < TPW, and keeps their D and E accumulators (E takes both of its products) in registers over all blocks.
+//     The epilogue selects post_n+1(s') (log D - E / D) per (adjacency, s'), sums a row over the lane's tiles in ascending u, over
+//     the 16 lanes by the fixed butterfly and over the waves in wave order; marg of the tile's segments is formed by 16 lanes per row.
+//   k_path_entropy_adj: one workgroup per (listed segment, restart) for the breakend adjacencies, on exp(trans_value) with the
+//     thread owning s' (the siblings' "exp" D pass), and for the chain ends (marg only).
+// Every sum has one order fixed by S alone: an entry depends on neither the ranges, the chunking, the tile nor the row it sits in.
+// Rows of a padded tile are computed on zeros and not stored; only columns s < S of fa / post are read.  A D(s') that is 0 or not
+// finite under post_n+1(s') > 0, or a result that is not finite, gives NaN and RGN_ERR_DENOM in flags[r].  A sum that rounding
+// left below zero is stored as +0.0 (an entropy is >= 0).  out: marg, step [restart of the launch][nc] at column n - nbase.
+// =============================================================================
+#define PEN_KB 64      // states of the summed dimension per staged block of the A operands
+typedef double pen_d4 __attribute__((ext_vector_type(4)));
+// -sum_s post(s) log post(s) over a row by the 16 lanes of a group (gl: the lane's index in it); every lane gets it
+__device__ __forceinline__ double pen_marg16(const double *post, int S, int gl) {
+    double p = 0.;
+    for (int s = gl; s < S; s += RGN_GL) p += xlogx(post[s]);
+    return 0. - group_sum(p, RGN_GL);
+}
+// one term of step_n; a bad normaliser or a result that is not finite sets bad
+__device__ __forceinline__ double pen_term(double p, double D, double E, bool &bad) {
+    if (!(p > 0.)) return 0.;
+    const double t = p * (log(D) - E / D);
+    if (!(D > 0. && D < INFINITY) || !(fabs(t) < INFINITY)) bad = true;
+    return t;
+}
+template <int TPW>
+__global__ __launch_bounds__(RGN_NT) void k_path_entropy(Dev d, int r0, int use_wb, const int32_t *tiles, int nbase, int nc, double *marg, double *step, uint32_t *flags) {
+    __shared__ double A0[PEN_KB][RGN_KB + 1], A1[PEN_KB][RGN_KB + 1];      // fa, fa log fa of the block: [state][adjacency]
+    __shared__ double red[RGN_NW][RGN_KB];
+    __shared__ int nidx[RGN_KB], s_bad[RGN_KB], s_badm[RGN_KB];      // a row's step / marg failed
+    const int ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ai = lane & 15, kk = lane >> 4;
+    const int S = d.S;
+    const int32_t *tile = tiles + (size_t)blockIdx.x * (RGN_KB + 1);
+    const int tc = tile[0];
+    if (tid < RGN_KB) { nidx[tid] = tile[1 + tid]; s_bad[tid] = 0; s_badm[tid] = 0; }
+    __syncthreads();
+    const double *Tv = d.Tval + (size_t)tc * S * S, *Wf = d.Wf + (size_t)tc * S * S;
+    // ---- marg of the tile's segments: 16 lanes per row -------------------------------------------------------------------------
+    {
+        const int m = tid / RGN_GL, n = nidx[m];
+        const double H = pen_marg16(d.post + rs_off(d, r, n >= 0 ? n : 0), S, tid % RGN_GL);
+        if (n >= 0 && tid % RGN_GL == 0) {
+            const bool ok = fabs(H) < INFINITY;
+            if (!ok) s_badm[m] = 1;
+            marg[(size_t)ri * nc + (n - nbase)] = ok ? (H < 0. ? 0. : H) : __builtin_nan("");
+        }
+    }
+    // ---- D and E of every (adjacency, s'): the product over s, PEN_KB states at a time ----------------------------------------------
+    pen_d4 accD[TPW], accE[TPW];
+#pragma unroll
+    for (int u = 0; u < TPW; u++) { accD[u] = pen_d4{0., 0., 0., 0.}; accE[u] = pen_d4{0., 0., 0., 0.}; }
+    for (int kb = 0; kb < S; kb += PEN_KB) {
+        __syncthreads();      // (every wave has read the last block)
+        for (int e = tid; e < RGN_KB * PEN_KB; e += RGN_NT) {
+            const int m = e / PEN_KB, k = e % PEN_KB, s = kb + k, n = nidx[m];
+            const bool ok = n >= 0 && s < S;
+            const double raw = d.fa[rs_off(d, r, n >= 0 ? n : 0) + (s < S ? s : S - 1)];
+            const double v = ok ? raw : 0.;
+            A0[k][m] = v;
+            A1[k][m] = xlogx(v);
+        }
+        __syncthreads();
+        const int kend = S - kb < PEN_KB ? S - kb : PEN_KB;
+        for (int k0 = 0; k0 < kend; k0 += 4) {
+            const int s = kb + k0 + kk;
+            const bool sok = s < S;
+            const size_t row = (size_t)(sok ? s : S - 1) * S;
+            const double a0 = A0[k0 + kk][ai], a1 = A1[k0 + kk][ai];      // (zeros at s >= S)
+#pragma unroll
+            for (int u = 0; u < TPW; u++) {
+                const int c0 = (wave + RGN_NW * u) * 16;
+                if (c0 < S) {         // (uniform over the wave)
+                    const int sp = c0 + ai;
+                    const bool ok = sok && sp < S;
+                    const size_t at = row + (sp < S ? sp : S - 1);
+                    const double t = Tv[at];
+                    const double w = use_wb ? Wf[at] : exp(t);
+                    const double bw = ok ? w : 0., bt = (ok && w > 0.) ? w * t : 0.;
+                    accD[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, bw, accD[u], 0, 0, 0);
+                    accE[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, bw, accE[u], 0, 0, 0);
+                    accE[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, bt, accE[u], 0, 0, 0);
+                }
+            }
+        }
+    }
+    // ---- step: lane (ai, kk) holds column s' = c0 + ai of the rows kk + 4 g -------------------------------------------------------
+    double part[4] = {0., 0., 0., 0.};
+    bool bad[4] = {false, false, false, false};
+#pragma unroll
+    for (int u = 0; u < TPW; u++) {
+        const int c0 = (wave + RGN_NW * u) * 16;
+        if (c0 < S) {
+            const int sp = c0 + ai;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int n = nidx[kk + 4 * g];
+                const double raw = d.post[rs_off(d, r, n >= 0 ? n + 1 : 0) + (sp < S ? sp : S - 1)];
+                part[g] += pen_term((n >= 0 && sp < S) ? raw : 0., accD[u][g], accE[u][g], bad[g]);
+            }
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+        const double v = group_sum(part[g], RGN_GL);
+        if (bad[g]) s_bad[kk + 4 * g] = 1;
+        if (ai == 0) red[wave][kk + 4 * g] = v;
+    }
+    __syncthreads();
+    if (tid < 64) {
+        bool fail = false;
+        if (tid < RGN_KB && nidx[tid] >= 0) {
+            double t = 0.;
+#pragma unroll
+            for (int i = 0; i < RGN_NW; i++) t += red[i][tid];
+            fail = s_bad[tid] != 0 || !(fabs(t) < INFINITY);
+            step[(size_t)ri * nc + (nidx[tid] - nbase)] = fail ? __builtin_nan("") : (t < 0. ? 0. : t);
+        }
+        if (tid < RGN_KB && s_badm[tid]) fail = true;
+        if (__ballot(fail) && tid == 0) atomicOr(&flags[r], RGN_ERR_DENOM);
+    }
+}
+// the breakend adjacencies and the chain ends of a range: list [nlist] of segment indices, grid (nlist, restarts)
+__global__ __launch_bounds__(RGN_NT) void k_path_entropy_adj(Dev d, int r0, const int32_t *list, int nbase, int nc, double *marg, double *step, uint32_t *flags) {
+    __shared__ double fas[RGN_MAXS], flf[RGN_MAXS];
+    __shared__ double red[RGN_NT / 64];
+    __shared__ int s_bad;
+    const int n = list[blockIdx.x], ri = blockIdx.y, r = r0 + ri, tid = threadIdx.x;
+    const int S = d.S;
+    if (tid == 0) s_bad = 0;
+    double H;
+    {
+        const double *post = d.post + rs_off(d, r, n);
+        double p = 0.;
+        for (int s = tid; s < S; s += RGN_NT) p += xlogx(post[s]);
+        H = 0. - rgn_block_sum(p, red);
+    }
+    double st = 0.;
+    if (d.tclass[n] >= 0) {      // (uniform over the workgroup)
+        const double *pd = rgn_adj(d, r, n, 0).pd;      // (the restart's pd_lt on a breakend adjacency; the weights are exp(trans_value))
+        const double *fa = d.fa + rs_off(d, r, n), *post1 = d.post + rs_off(d, r, n + 1);
+        for (int s = tid; s < S; s += RGN_NT) {
+            const double v = fa[s];
+            fas[s] = v;
+            flf[s] = xlogx(v);
+        }
+        __syncthreads();
+        double part = 0.;
+        bool bad = false;
+        for (int sp = tid; sp < S; sp += RGN_NT) {
+            const double p = post1[sp];
+            if (p > 0.) {
+                double D = 0., E = 0.;
+                for (int s = 0; s < S; s++) {
+                    const double f = fas[s];
+                    if (f != 0.) {
+                        const double t = trans_value(d, n, s, sp, pd), w = exp(t);
+                        if (w > 0.) {
+                            D = fma(f, w, D);
+                            E = fma(flf[s], w, E);
+                            E = fma(f * w, t, E);
+                        }
+                    }
+                }
+                part += pen_term(p, D, E, bad);
+            }
+        }
+        if (bad) s_bad = 1;
+        st = rgn_block_sum(part, red);      // (its barriers also publish s_bad)
+    }
+    if (tid == 0) {
+        const bool okH = fabs(H) < INFINITY, okS = !s_bad && fabs(st) < INFINITY;
+        marg[(size_t)ri * nc + (n - nbase)] = okH ? (H < 0. ? 0. : H) : __builtin_nan("");
+        step[(size_t)ri * nc + (n - nbase)] = okS ? (st < 0. ? 0. : st) : __builtin_nan("");
+        if (!okH || !okS) atomicOr(&flags[r], RGN_ERR_DENOM);
+    }
+}
+
+// =============================================================================
 // Region automata: for a query (a, b, symbol table, automaton) over the model segments [a, b] of one chain, the
 // exact distribution of the final state of a deterministic finite automaton (Q <= 16 states, A <= 16 symbols, transition table
 // delta [Q][A], start state q0) that reads one symbol per segment, sigma_n(s) = the symbol of state s under the state class of

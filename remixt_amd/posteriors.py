@@ -2291,3 +2291,83 @@ def batch_event_run_of(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, i
     for j, reg in enumerate(np.asarray(piece_region)):
         miss[:, reg] *= np.clip(1. - final[:, j, -1], 0., 1.)
     return {'p_run': 1. - miss}
+
+
+# ---- entropy of the path posterior over regions (rmx_path_entropy) ---------------------------------------------
+PATH_ENTROPY_ARRAYS = ('path_entropy', 'inserted_slack', 'marginal_entropy_sum', 'total_correlation', 'perplexity', 'entropy_per_segment')
+
+
+def _prefix(a):
+    """Prefix sums along the last axis with a leading zero: sum a[..., i:j] = p[..., j] - p[..., i]."""
+    a = np.asarray(a, dtype=float)
+    return np.concatenate([np.zeros(a.shape[:-1] + (1,)), np.cumsum(a, axis=-1)], axis=-1)
+
+
+def entropy_runs(marginal, step, runs, seg_is_original):
+    """The entropy (nats) of the path posterior over runs of model segments from the two arrays of path_entropy_raw
+    (marginal, step: (..., N1); marginal[n] = H(post_n), step[n] = H(c_n | c_n+1)).  runs int (P, 2): segments a <= b of one
+    chain each, b a real segment.  A dict of arrays (..., P):
+      path_entropy          H(c_a .. c_b) = marginal[b] + sum step[a .. b-1]: the chain is Markov, so the chain rule stops after
+                            one condition.  The path is over the model run, inserted zero-length segments included
+      marginal_entropy_sum  sum marginal[a .. b]
+      inserted_slack        sum of step[m] over the inserted segments m of the run.  H(real segments of the run) lies in
+                            [path_entropy - inserted_slack, path_entropy]: H(c_I | c_R) = sum_m H(c_m | c_{I > m}, c_R) over
+                            the inserted m in descending order, and every term is <= H(c_m | c_m+1) because c_m+1 is among its
+                            conditions and dropping conditions raises an entropy
+    and `num_segments` int (P,), the real segments of each run.  Everything is a difference of prefix sums."""
+    marg, st = np.asarray(marginal, dtype=float), np.asarray(step, dtype=float)
+    r = np.asarray(runs, dtype=np.int64).reshape(-1, 2)
+    real = np.asarray(seg_is_original) != 0
+    a, b = r[:, 0], r[:, 1]
+    if len(r) and (a.min() < 0 or b.max() >= marg.shape[-1] or (a > b).any()):
+        raise ValueError('a run needs 0 <= first <= last < number of model segments')
+    ps, pm, pi = _prefix(st), _prefix(marg), _prefix(np.where(real, 0., st))
+    nreal = np.concatenate([[0], np.cumsum(real)]).astype(np.int64)
+    return {'path_entropy': marg[..., b] + (ps[..., b] - ps[..., a]),
+            'marginal_entropy_sum': pm[..., b + 1] - pm[..., a],
+            'inserted_slack': pi[..., b] - pi[..., a],
+            'num_segments': nreal[b + 1] - nreal[a]}
+
+
+def batch_path_entropy(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere):
+    """How uncertain regions are, for restarts r0 .. r0+nr-1 of a RemixtBatch from one device call over all segments
+    (path_entropy_raw); everything else is prefix sums here.  regions: (first, last) experiment segment indices; None: one
+    region, the genome.  A dict of arrays with a leading restart axis, nats:
+      segment_entropy (nr, N)      H of every experiment segment's marginal
+      step_entropy (nr, N - 1)     the model steps from seg_fwd_remap[i] up to but not including seg_fwd_remap[i + 1] added up:
+                                   the entropy of segment i and the inserted segments behind it given segment i + 1; NaN where
+                                   no reference adjacency joins i and i + 1
+      adjacent_information (nr, N - 1)  I(c_i; c_i+1) = H(c_i) - H(c_i | c_i+1) where no inserted segment separates the two; NaN
+                                   otherwise, and where no reference adjacency joins them
+    and per region, (nr, R): path_entropy (pieces in different chains add: chains are independent), inserted_slack,
+    marginal_entropy_sum, total_correlation = marginal_entropy_sum - path_entropy, perplexity = exp(path_entropy) and
+    entropy_per_segment = path_entropy over the number of real segments (entropy_runs)."""
+    fwd = np.asarray(seg_fwd_remap, dtype=np.int64)
+    N = len(fwd)
+    marg, step = batch.path_entropy_raw(r0, nr)
+    marg, step = np.asarray(marg, dtype=float), np.asarray(step, dtype=float)
+    out = {'segment_entropy': marg[:, fwd]}
+    ps = _prefix(step)
+    _, joined = adjacency_regions(fwd, is_telomere)
+    se = np.full((nr, max(N - 1, 0)), np.nan)
+    ai = np.full((nr, max(N - 1, 0)), np.nan)
+    if len(joined):
+        se[:, joined] = ps[:, fwd[joined + 1]] - ps[:, fwd[joined]]
+        direct = joined[fwd[joined + 1] == fwd[joined] + 1]
+        ai[:, direct] = marg[:, fwd[direct]] - step[:, fwd[direct]]
+    out['step_entropy'], out['adjacent_information'] = se, ai
+    reg = genome_region(np.zeros((0, 2), dtype=np.int64), N) if regions is None else np.asarray(regions, dtype=np.int64).reshape(-1, 2)
+    R = len(reg)
+    cs, ce = chains_from_telomeres(is_telomere)
+    runs, piece_region, _ = region_queries(reg, fwd, seg_is_original, cs, ce)
+    pieces = entropy_runs(marg, step, runs, seg_is_original)
+    for k in ('path_entropy', 'inserted_slack', 'marginal_entropy_sum'):
+        out[k] = combine(pieces[k], piece_region, R)
+    nreal = np.zeros(R)
+    np.add.at(nreal, np.asarray(piece_region), pieces['num_segments'])
+    out['total_correlation'] = out['marginal_entropy_sum'] - out['path_entropy']
+    with np.errstate(over='ignore'):                       # (a genome's perplexity is beyond the doubles: inf)
+        out['perplexity'] = np.exp(out['path_entropy'])
+    with np.errstate(invalid='ignore', divide='ignore'):
+        out['entropy_per_segment'] = out['path_entropy'] / nreal
+    return out

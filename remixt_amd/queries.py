@@ -317,6 +317,32 @@ ALL_QUERIES = QUERIES + LATER_QUERIES + AUTOMATON_QUERIES
 BY_NAME = dict((e.name, e) for e in ALL_QUERIES)
 
 
+@_query('path_entropy_raw', 'has no path entropy', 'a dict of arrays with a leading restart axis')
+def path_entropy(q, regions=None):
+    """How uncertain regions are at all: the exact Shannon entropy, in nats, of the copy-number path posterior of the last
+    variational update over regions ((first, last) experiment segment indices; None: one region, the genome).  A dict of
+    `segment_entropy` (N,), the entropy of every segment's marginal; `step_entropy` (N - 1,), H(c_n | c_n+1) between experiment
+    segments n and n + 1, and `adjacent_information` (N - 1,), their mutual information, both NaN where no reference adjacency
+    joins them; and per region `path_entropy`, the entropy of the joint configuration of the region (chains add),
+    `inserted_slack` (the entropy of the real segments alone lies in [path_entropy - inserted_slack, path_entropy]: the
+    zero-length segments inserted at breakends are part of the path), `marginal_entropy_sum`, `total_correlation` (what the sum
+    of the marginal entropies overstates), `perplexity` = exp(path_entropy), the effective number of configurations, and
+    `entropy_per_segment` (posteriors.batch_path_entropy)."""
+    return posteriors.batch_path_entropy(*q.at, regions, *q.maps)
+
+
+# (ALL_QUERIES and BY_NAME are compared with closed lists as well: `entry` looks a name up in every tuple, `answers` installs them all)
+ENTROPY_QUERIES = (path_entropy,)
+
+
+def entry(name):
+    """The table's entry of a query by its name, whichever tuple holds it."""
+    for e in ALL_QUERIES + ENTROPY_QUERIES:
+        if e.name == name:
+            return e
+    raise KeyError(name)
+
+
 # ---- a result along the restart axis ----------------------------------------------------------------------------------------
 def _join(parts, shared=(), extend=(), each=()):
     """One query's results from several groups of restarts, as of all their restarts in order.  Lists over restarts are
@@ -438,7 +464,7 @@ def answers(level):
     body, doc = LEVELS[level]
 
     def install(cls):
-        for entry in ALL_QUERIES:
-            setattr(cls, entry.name, _method(cls, entry, body, doc(entry)))
+        for e in ALL_QUERIES + ENTROPY_QUERIES:
+            setattr(cls, e.name, _method(cls, e, body, doc(e)))
         return cls
     return install

@@ -705,6 +705,38 @@ int rmx_region_automaton(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const
  * NaN; RMX_EUNSUPPORTED above 1024 states.  The kernels have no profile id. */
 int rmx_path_entropy(rmx_batch *b, int32_t r0, int32_t nr, int32_t n0, int32_t n1, double *marginal_out, double *step_out);
 
+/* Region sums: the exact posterior distribution of a length-weighted event occupancy over regions: of the
+ * additive functional sum_n w_n level_n(c_n) of the path over a run, with non-negative integer weights and levels -- how many
+ * segments of a run are in an event, how many weight units of it are, how many copies its segments carry between them.
+ *   levels int16 [C][nlevel][S], every entry >= 0: the level of a state under a state class (rmx_region_extremes' layout);
+ *     a mask is a 0/1 table
+ *   weights int32 [nwt], every entry >= 0: a flat pool
+ *   query i = (a, b, level table index, weight offset o) over the model segments a <= b of one chain: segment n of the run
+ *     has the weight w_n = weights[o + n - a]; 0 <= o and o + (b - a) < nwt
+ *   1 <= nbins <= 64, and nbins <= the bins the kernel's LDS plan holds at S states: 64 up to 304 states, 32 up to 608, 16 up
+ *     to 1024 (rmxh::sums_max_bins in remixt_amd/csrc/rmx_host.h)
+ * There is no constrain vector: a weight of 0 is "this segment does not count".  With B = nbins, the increment
+ * d_n(s) = min((int64) w_n level_n(s), B - 1) under the class of segment n, and post, fa, W_n and D_n as in rmx_region_prob,
+ *   G_b(s, k) = post_b(s) [k = d_b(s)]
+ *   H(s', k)  = G_n+1(s', k) / D_n(s'),   X(s, k) = fa_n(s) sum_s' W_n(s, s') H(s', k)
+ *   G_n(s, k) = X(s, k - d_n(s))                          for d_n(s) <= k < B - 1   (0 for k < d_n(s))
+ *   G_n(s, B-1) = sum_{k' = B-1-d_n(s)}^{B-1} X(s, k')    (ascending k'; d = 0: X(s, B-1))
+ *   logp_out [nr][nq][B]: out(k) = log sum_s G_a(s, k) = log P(sum_n w_n level(c_n) == k); the last bin: >= B - 1.
+ * A bin that cannot be reached gives -inf and is no error.  Nothing binds, so in real arithmetic the total over (s, k) is 1 at
+ * every step and the B outputs sum to 1; G is still divided by its total after every step, the start included, and the
+ * logarithm is accumulated, which only removes rounding drift.  ONE SCALE CARRIES ALL COLUMNS, because columns mix under the
+ * shift: a bin more than about 1e-308 below the total comes out -inf.  The model is not modified.
+ * A (restart, query) result is bit-identical in any restart range, any batch and order of queries, any chunking, and wherever
+ * its weights lie in the pool.
+ * Errors: RMX_EARG with nothing launched and the output untouched for a bad restart range, nq < 1, a NULL pointer, nlevel < 1,
+ * nwt < 1, nbins outside [1, 64], a negative level or weight, a level index or a weight span out of range, segments outside
+ * the model, a > b or in two chains; RMX_EVALUE with the restarts listed before update_p_cn; RMX_EASSERT with the restarts
+ * listed for a normaliser D that is 0 or not finite under mass or a total that is not a finite number >= 0: all B entries of
+ * that query are NaN; RMX_EUNSUPPORTED above 1024 states, or for more bins than the LDS plan holds at the batch's state count
+ * (an argument check: nothing is launched).  The kernel has no profile id. */
+int rmx_region_sums(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nlevel, const int16_t *levels,
+                    int32_t nwt, const int32_t *weights, int32_t nbins, double *logp_out);
+
 /* -- module-level functions on caller-supplied dense inputs ----------------- */
 /* sum_product (:1213-1246): f [N][S], T [N-1][S][S] -> alphas, betas [N][S] */
 int rmx_sum_product(const double *f, const double *T, double *alphas, double *betas,

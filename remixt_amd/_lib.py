@@ -122,6 +122,8 @@ SYMBOLS = {
     "rmx_region_automaton": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int16),
                                        C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _dp]),
     "rmx_path_entropy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp]),
+    "rmx_region_sums": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int16),
+                                  C.c_int32, C.POINTER(C.c_int32), C.c_int32, _dp]),
 }
 
 _lib = None

@@ -726,6 +726,28 @@ class RemixtBatch(object):
                                                 obuf.ctypes.data_as(_dp)))
         return out
 
+    def region_sums_raw(self, r0, nr, queries, levels, weights, bins):
+        """The exact distribution of sum_n w_n level(c_n) over runs of model segments, under the structured posterior of the
+        last update_p_cn of restarts r0 .. r0+nr-1 (rmx_region_sums).  queries int (nq, 4): segments a <= b of one chain,
+        level table index, offset o of the run's weights in the pool; levels int (C, nlevel, S), every entry >= 0 (a mask is
+        a 0/1 table); weights int (nwt,), every entry >= 0: segment n of a run has weight weights[o + n - a], and 0 is "this
+        segment does not count".  Returns (nr, nq, bins): log P(the sum == k), the last bin log P(the sum >= bins - 1); -inf
+        for a value that cannot be reached.  Exact for these integer weights.  bins in 1 .. 64 and at most
+        posteriors.sums_max_bins(num_cn_states)."""
+        r0, nr, bins = int(r0), int(nr), int(bins)
+        q, args, _keep = self._region_args(queries, None, levels, None)
+        wt = np.asarray(weights)
+        if wt.ndim != 1:
+            raise ValueError('weights must have shape (nwt,)')
+        if wt.size and (wt.min() < -2 ** 31 or wt.max() >= 2 ** 31):
+            raise ValueError('weight out of the int32 range')
+        wt = np.ascontiguousarray(wt, dtype=np.int32)
+        out = np.zeros((max(nr, 0), q.shape[0], bins if 1 <= bins <= 64 else 1), dtype=np.float64)
+        obuf, wbuf = out if out.size else np.zeros(1), wt if wt.size else np.zeros(1, dtype=np.int32)
+        self._ck(self._lib.rmx_region_sums(self._handle, r0, nr, args[0], args[1], args[4], args[5], wt.shape[0],
+                                           wbuf.ctypes.data_as(C.POINTER(C.c_int32)), bins, obuf.ctypes.data_as(_dp)))
+        return out
+
     def path_entropy_raw(self, r0, nr, n0=0, n1=None):
         """The two arrays from which the entropy (nats) of the copy-number path posterior over any run of model segments
         follows, under the structured posterior of the last update_p_cn of restarts r0 .. r0+nr-1 (rmx_path_entropy), for the
@@ -1197,6 +1219,10 @@ class RemixtModel(object):
     def region_automaton(self, queries, symbols, delta, start, constrain=None):
         """RemixtBatch.region_automaton_raw of this model: log-probabilities (nq, Q)."""
         return self._batch.region_automaton_raw(self._r, 1, queries, symbols, delta, start, constrain)[0]
+
+    def region_sums(self, queries, levels, weights, bins):
+        """RemixtBatch.region_sums_raw of this model: log-probabilities (nq, bins)."""
+        return self._batch.region_sums_raw(self._r, 1, queries, levels, weights, bins)[0]
 
     def path_entropy(self, n0=0, n1=None):
         """RemixtBatch.path_entropy_raw of this model: (marginal, step), (n1 - n0,) each."""

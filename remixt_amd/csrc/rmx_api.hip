@@ -20,6 +20,7 @@
 #include <memory>
 
 #include "rmx_kernels.h"
+#include "rmx_region_sums.h"
 #include "rmx_host.h"
 
 // ---------------------------------------------------------------------------
@@ -3968,6 +3969,58 @@ int rmx_path_entropy(rmx_batch *b, int32_t r0, int32_t nr, int32_t n0, int32_t n
         }
     }
     return report_flags(b, b->d_rflags, r0, nr, "path_entropy: a normaliser is zero or not finite under posterior mass, or an entropy is not finite");
+}
+
+// Region sums (k_region_sums): for every (restart, query) the log-probabilities of the nbins values of
+// sum_n w_n level(c_n) over the run, the last bin absorbing.  Fields 2 and 3 of a query name the level table and the offset of the
+// run's weights in the pool; the level tables travel where the label tables of the siblings do, the weight pool behind them in
+// the shared table buffer.  Everything is checked before anything is queued (check_queries; rmxh::check_levels, check_weights,
+// check_sum_spans, sums_max_bins), and no output is written on an error.  One workgroup computes a (restart, query) on its own.
+// The kernel has no profile id (KID_NONE).
+using SumsKernel = void (*)(Dev, int, int, RgnArgs, const int32_t *, int, double *, uint32_t *);
+// (tpw row tiles per wave, ct column tiles) -> the instantiation; null for a pair that rmxh::sums_max_bins rules out: four column
+// tiles hold at most 304 states, 19 row tiles, which is never 16 per wave
+static SumsKernel region_sums_kernel(int tpw, int ct) {
+    if (ct == 1) return tpw == 3 ? k_region_sums<3, 1> : (tpw == 8 ? k_region_sums<8, 1> : k_region_sums<16, 1>);
+    if (ct == 2) return tpw == 3 ? k_region_sums<3, 2> : (tpw == 8 ? k_region_sums<8, 2> : k_region_sums<16, 2>);
+    return tpw == 3 ? k_region_sums<3, 4> : (tpw == 8 ? k_region_sums<8, 4> : nullptr);
+}
+int rmx_region_sums(rmx_batch *b, int32_t r0, int32_t nr, int32_t nq, const int32_t *queries, int32_t nlevel, const int16_t *levels,
+                    int32_t nwt, const int32_t *weights, int32_t nbins, double *logp_out) { BIND(b);
+    int rc;
+    if ((rc = check_region_call(b, "region_sums", r0, nr, nq, queries, logp_out))) return rc;
+    if (nlevel < 1 || !levels) return fail(RMX_EARG, "region_sums: no level tables");
+    if (nwt < 1 || !weights) return fail(RMX_EARG, "region_sums: no weights");
+    if (!rmxh::sums_column_tiles(nbins)) return fail(RMX_EARG, "region_sums: nbins must be in [1, 64]");
+    if (b->d.S > RGN_MAXS) return fail(RMX_EUNSUPPORTED, "region_sums: more than 1024 states");
+    if ((rc = check_queries(b, "region_sums", nq, queries, {0, nlevel, "region_sums: a query needs a level table index in [0, nlevel)"},
+                            {0, nwt, "region_sums: a query needs a weight offset in [0, nwt)"}))) return rc;
+    {
+        const int64_t bad = rmxh::check_sum_spans(nq, queries, nwt);
+        if (bad != -1) return fail(RMX_EARG, "region_sums: the weights of a query leave the pool (query " + std::to_string(bad) + ")");
+    }
+    if (rmxh::check_levels(b->d.C, nlevel, b->d.S, levels) != -1) return fail(RMX_EARG, "region_sums: a level entry is negative");
+    if (rmxh::check_weights(nwt, weights) != -1) return fail(RMX_EARG, "region_sums: a weight is negative");
+    if (nbins > rmxh::sums_max_bins(b->d.S))
+        return fail(RMX_EUNSUPPORTED, "region_sums: at " + std::to_string(b->d.S) + " states the kernel holds at most " + std::to_string(rmxh::sums_max_bins(b->d.S)) + " bins");
+    if ((rc = require_snapshot(b, r0, nr, "region_sums"))) return rc;
+    RgnArgs ra;
+    uint8_t *extra = nullptr;
+    const size_t wt_bytes = (size_t)nwt * sizeof(int32_t);
+    if ((rc = stage_region_tables(b, 0, nullptr, nlevel, levels, nullptr, &ra, wt_bytes, &extra))) return rc;
+    HIPCHK(hipMemcpyAsync(extra, weights, wt_bytes, hipMemcpyHostToDevice, b->stream));
+    const int32_t *dwts = (const int32_t *)extra;
+    const int ct = rmxh::sums_column_tiles(nbins), tpw = tiles_per_wave(b->d.S);
+    const size_t lds = rgs_lds_bytes(b->d.S, ct);
+    if ((int64_t)lds != rmxh::sums_lds_bytes(b->d.S, nbins)) return fail(RMX_EASSERT, "region_sums: the host's and the kernel's LDS plans differ");
+    const SumsKernel kf = region_sums_kernel(tpw, ct);
+    if (!kf) return fail(RMX_EASSERT, "region_sums: no kernel for this state count and these bins");
+    if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return run_queries(b, r0, nr, nq, queries, (int)nbins, KID_NONE, "region_sums: a backward step has a zero or non-finite normaliser", logp_out,
+                       [&](const Dev &dv, int r, int n, int, int use_wb, const int32_t *dq, int nqc, double *out, uint32_t *flags) {
+        ra.queries = dq; ra.nq = nqc;
+        hipLaunchKernelGGL(kf, dim3((unsigned)nqc, n), dim3(RGN_NT), lds, b->stream, dv, r, use_wb, ra, dwts, (int)nbins, out, flags);
+    });
 }
 
 #ifdef RMX_KBEST_COUNT

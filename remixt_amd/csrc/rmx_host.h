@@ -10,6 +10,7 @@
 //   extremes_ncol_ok, check_levels  rmx_region_extremes: the column rule, and that no level entry is negative
 //   locus_shape_ok, check_locus_lengths  rmx_locus_joint: the table and slot rule, and that a profile query fits its slots
 //   automaton_shape_ok, check_automata, check_symbols  rmx_region_automaton: the shape rule, and that every transition, start state and symbol is in range
+//   sums_max_bins, sums_lds_bytes, sum_increment, check_weights, check_sum_spans  rmx_region_sums: the bins the LDS plan holds, the saturating increment, the weight pool's rules
 //   entropy_range_ok, entropy_tiles, entropy_chunk  rmx_path_entropy: the range rule, the work lists of a range and the chunks of a call
 //   check_pairs, check_permutations  rmx_restart_overlap: the restart pairs lie inside the two batches, every permutation row is a bijection
 //   weighted_search      rmx_weighted_search: numpy's cumsum / searchsorted(side='right') for the weighted M-step samples
@@ -276,6 +277,58 @@ inline int64_t check_symbols(int64_t C, int64_t nsym, int64_t S, int32_t A, cons
     const uint64_t n = (uint64_t)C * (uint64_t)nsym * (uint64_t)S;      // (each extent is below 2^31 in a batch; the caller's are int32)
     if (n > 0 && !symbols) return -2;
     for (uint64_t i = 0; i < n; i++) if (symbols[i] < 0 || (int32_t)symbols[i] >= A) return (int64_t)i;
+    return -1;
+}
+
+// rmx_region_sums.  The kernel keeps G [S rounded up to 16][16 CT] doubles in LDS, CT = 1, 2 or 4 column tiles
+// of 16 bins, beside a row of doubles, one int16 level row and the compacted int16 index: SR (128 CT + 12) bytes, which must
+// fit the 160 KiB of a workgroup together with the kernel's static LDS (SUMS_STATIC_LDS bytes at the most).  So the most
+// bins a call may ask for is 64 up to 304 states, 32 up to 608 and 16 up to SUMS_MAX_STATES; 0 beyond (unsupported)
+constexpr int32_t SUMS_MAX_BINS = 64;
+constexpr int32_t SUMS_MAX_STATES = 1024;
+constexpr int64_t SUMS_LDS_LIMIT = 160 * 1024;
+constexpr int64_t SUMS_STATIC_LDS = 64;
+// the column tiles of 16 that hold nbins bins: 1, 2 or 4 (0 for nbins outside [1, SUMS_MAX_BINS])
+inline int32_t sums_column_tiles(int32_t nbins) {
+    if (nbins < 1 || nbins > SUMS_MAX_BINS) return 0;
+    return nbins <= 16 ? 1 : (nbins <= 32 ? 2 : 4);
+}
+// the dynamic LDS of a call with nbins bins at S states, in bytes (0 for arguments outside the rules above)
+inline int64_t sums_lds_bytes(int32_t S, int32_t nbins) {
+    const int32_t ct = sums_column_tiles(nbins);
+    if (S < 1 || S > SUMS_MAX_STATES || !ct) return 0;
+    const int64_t SR = ((int64_t)S + 15) / 16 * 16;
+    return SR * (128 * (int64_t)ct + 12);
+}
+inline int32_t sums_max_bins(int32_t S) {
+    for (int32_t nbins = SUMS_MAX_BINS; nbins >= 16; nbins /= 2) {
+        const int64_t lds = sums_lds_bytes(S, nbins);
+        if (lds > 0 && lds + SUMS_STATIC_LDS <= SUMS_LDS_LIMIT) return nbins;
+    }
+    return 0;
+}
+// the increment of a state of level `level` on a segment of weight w: min(w level, nbins - 1) with a 64-bit product (w up to
+// 2^31 - 1 times a level up to 32767 overflows 32 bits).  w, level >= 0 and nbins >= 1 are the caller's to check
+inline int32_t sum_increment(int32_t w, int32_t level, int32_t nbins) {
+    const int64_t p = (int64_t)w * (int64_t)level;
+    return p < (int64_t)nbins - 1 ? (int32_t)p : nbins - 1;
+}
+// the weight pool [nwt] holds no negative entry.  Returns the index of the first entry that does, -1 if there is none, or -2
+// for arguments that describe no pool
+inline int64_t check_weights(int64_t nwt, const int32_t *weights) {
+    if (nwt < 0 || (nwt > 0 && !weights)) return -2;
+    for (int64_t i = 0; i < nwt; i++) if (weights[i] < 0) return i;
+    return -1;
+}
+// every query [nq][4] = (a, b, .., o) with a <= b keeps its weights o .. o + (b - a) inside the pool: 0 <= o and
+// o + (b - a) < nwt (no overflow for any int32 triple).  Returns the index of the first query that does not (a > b is one),
+// -1 if there is none, or -2 for arguments that describe no queries
+inline int64_t check_sum_spans(int32_t nq, const int32_t *queries, int64_t nwt) {
+    if (nq < 0 || (nq > 0 && !queries) || nwt < 0) return -2;
+    for (int32_t i = 0; i < nq; i++) {
+        const int64_t a = queries[4 * (size_t)i], b = queries[4 * (size_t)i + 1], o = queries[4 * (size_t)i + 3];
+        if (a > b || o < 0 || o + (b - a) >= nwt) return i;
+    }
     return -1;
 }
 

@@ -2371,3 +2371,233 @@ def batch_path_entropy(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, i
     with np.errstate(invalid='ignore', divide='ignore'):
         out['entropy_per_segment'] = out['path_entropy'] / nreal
     return out
+
+
+# ---- posterior of length-weighted event occupancy over regions (rmx_region_sums) -------------------------------
+# how much of a region is in an event: the distribution of sum_n w_n level(c_n) over the region's segments, with non-negative
+# integer weights w_n and levels.  EXACT for integer weights (weights='segments', or lengths that are multiples of the unit); for
+# real lengths the floor and the ceil weights give two distributions that BRACKET the true one, rigorously: for every path,
+# unit * (floor sum) <= true weighted sum <= unit * (ceil sum).  The bracket is as wide as the number of real segments whose
+# length is no multiple of the unit: an arm-sized region of thousands of unequal segments gets a loose bracket.
+SUMS_MAX_BINS = 64
+OCCUPANCY_WEIGHTS = ('length', 'segments')
+
+
+def sums_max_bins(num_states):
+    """The most bins rmx_region_sums takes at num_states copy-number states (rmxh::sums_max_bins, from the kernel's LDS plan):
+    64 up to 304 states, 32 up to 608, 16 up to 1024, 0 beyond."""
+    S = int(num_states)
+    if S < 1 or S > 1024:
+        return 0
+    SR = (S + 15) // 16 * 16
+    for bins in (64, 32, 16):
+        if SR * (128 * {64: 4, 32: 2, 16: 1}[bins] + 12) + 64 <= 160 * 1024:
+            return bins
+    return 0
+
+
+def _integer_weights(lengths, unit):
+    """(floor(l / unit), ceil(l / unit)) as int64.  A ratio within a few ulps of an integer is that integer (1000 / (2500 / 45)
+    is 18): unit * floor <= l <= unit * ceil then holds up to the rounding of the product."""
+    ratio = lengths / unit
+    near = np.round(ratio)
+    whole = np.abs(ratio - near) <= 8 * np.finfo(float).eps * np.maximum(near, 1.)
+    wf, wc = np.where(whole, near, np.floor(ratio)), np.where(whole, near, np.ceil(ratio))
+    return wf.astype(np.int64), wc.astype(np.int64)
+
+
+def quantise_lengths(lengths, bins, vmax=1, unit=None):
+    """Integer weights for real segment lengths: (unit, w_floor, w_ceil, exact) with w_floor = floor(l / unit) and
+    w_ceil = ceil(l / unit), int64.  For every choice of levels in 0 .. vmax, unit * sum w_floor level <= sum l level <=
+    unit * sum w_ceil level: the two integer sums bracket the true one.  unit None: the smallest unit for which
+    sum ceil(l_n / unit) * vmax <= bins - 1, so that nothing saturates; if even one unit per segment of positive length does
+    not fit, the smallest unit for which the FLOOR sum fits (the ceil side then saturates, and its last bin says so).
+    exact: the two weight vectors are equal -- every length is a multiple of the unit, and the distribution is exact."""
+    l = np.asarray(lengths, dtype=float).reshape(-1)
+    bins, vmax = int(bins), max(int(vmax), 1)
+    if bins < 1:
+        raise ValueError('bins must be at least 1')
+    if len(l) and not (np.isfinite(l).all() and l.min() >= 0):
+        raise ValueError('lengths must be finite and >= 0')
+    cap = (bins - 1) // vmax                   # the most weight units a region may hold
+    if unit is not None:
+        unit = float(unit)
+        if not unit > 0:
+            raise ValueError('unit must be positive')
+    elif not (l > 0).any():
+        unit = 1.
+    else:
+        pos = l[l > 0]
+        ceil_fits = len(pos) <= cap
+
+        def fits(u):
+            wf, wc = _integer_weights(pos, u)
+            return (wc if ceil_fits else wf).sum() <= cap
+        # the sums only change at u = l_n / k, so the smallest unit that fits is one of those.  (The floor sum fits only PAST such
+        # a point, where no smallest unit exists: a part in 1e12 above it.)  The largest candidate fits: every ceil is 1 there,
+        # every floor 0
+        cand = np.unique((pos[:, None] / np.arange(1, max(cap, 1) + 2)[None, :]).reshape(-1))
+        if not ceil_fits:
+            cand = cand * (1 + 1e-12)
+        lo, hi = 0, len(cand) - 1
+        while lo < hi:
+            mid = (lo + hi) // 2
+            if fits(cand[mid]):
+                hi = mid
+            else:
+                lo = mid + 1
+        unit = float(cand[lo])
+    wf, wc = _integer_weights(l, unit)
+    return unit, wf, wc, bool(np.array_equal(wf, wc))
+
+
+def _sum_levels(cn_classes, event):
+    """An int (C, S) level table: a mask name of MASK_NAMES or a boolean (classes, states) table (level 1 where the event holds),
+    or a (quantity, clone) feature as locus_joint takes it (the level is that copy number)."""
+    cn = np.asarray(cn_classes)
+    if isinstance(event, tuple) and len(event) == 2 and isinstance(event[0], str):
+        quantity, clone = event
+        q = _level_quantity(cn, quantity)
+        M = cn.shape[2]
+        if clone != 'any' and not (isinstance(clone, (int, np.integer)) and 1 <= clone < M):
+            raise ValueError('clone must be a tumour clone 1 .. %d or \'any\'' % (M - 1))
+        return (q.max(axis=-1) if clone == 'any' else q[:, :, clone - 1]).astype(np.int64)
+    return _event_table(cn, event).astype(np.int64)
+
+
+def _check_levels(batch, levels):
+    lv = np.asarray(levels)
+    if lv.shape != np.asarray(batch.cn_classes).shape[:2]:
+        raise ValueError('levels must have shape (num_classes, num_cn_states)')
+    if lv.size and (lv.min() < 0 or lv.max() > 32767):
+        raise ValueError('levels must lie in 0 .. 32767')
+    return lv.astype(np.int16)
+
+
+def _sum_bins(batch, bins):
+    most = sums_max_bins(batch.num_cn_states)
+    bins = most if bins is None else int(bins)
+    if not 1 <= bins <= SUMS_MAX_BINS:
+        raise ValueError('bins must be in 1 .. %d' % SUMS_MAX_BINS)
+    if bins > most:
+        raise ValueError('at %d states a region sum holds at most %d bins' % (batch.num_cn_states, most))
+    return bins
+
+
+def _piece_sums(batch, r0, nr, runs, piece_region, R, levels, piece_weights, bins):
+    """One device call for several weightings of the same pieces: piece_weights a list over weightings of lists over pieces of
+    int weight vectors (one entry per model segment of the piece) -> a list over weightings of probabilities (nr, R, bins),
+    the pieces of a region convolved (combine_counts)."""
+    P = len(runs)
+    if P == 0:
+        empty = np.zeros((nr, R, bins))
+        empty[..., 0] = 1.
+        return [empty.copy() for _ in piece_weights]
+    pool = np.concatenate([np.asarray(w, dtype=np.int64) for ws in piece_weights for w in ws])
+    if pool.min() < 0 or pool.max() >= 2 ** 31:
+        raise ValueError('weights must lie in 0 .. 2^31 - 1')
+    q = np.zeros((len(piece_weights) * P, 4), dtype=np.int32)
+    at = 0
+    for k, ws in enumerate(piece_weights):
+        for j, w in enumerate(ws):
+            if len(w) != runs[j][1] - runs[j][0] + 1:
+                raise ValueError('a piece needs one weight per model segment')
+            q[k * P + j] = (runs[j][0], runs[j][1], 0, at)
+            at += len(w)
+    logp = batch.region_sums_raw(r0, nr, q, levels[:, None, :], pool.astype(np.int32), bins)
+    return [np.clip(combine_counts(logp[:, k * P:(k + 1) * P], piece_region, R), 0., 1.) for k in range(len(piece_weights))]
+
+
+def batch_region_sums(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, levels, weights, bins=None):
+    """The exact posterior distribution of sum_n weights[n] levels(c_n) over the model segments of regions, for restarts r0 ..
+    r0+nr-1 of a RemixtBatch from one device call (rmx_region_sums).  regions: (first, last) experiment segment indices;
+    levels: an int (classes, states) table, every entry >= 0; weights: int (num model segments,), every entry >= 0, PER MODEL
+    SEGMENT (0: the segment does not count -- give the inserted zero-length segments 0); bins None: the most the batch's state
+    count allows (sums_max_bins).  Exact for these integer weights.  Pieces of a region in several chains are joined with
+    combine_counts: chains are independent, sums add, and the last bin absorbs.  A dict of `bins`, `pmf` (nr, R, bins) --
+    entry k the probability that the sum is k, the last entry that of bins - 1 or more --, `mean` (nr, R) of the sum capped at
+    bins - 1, and `p_saturated` (nr, R), the last bin."""
+    bins = _sum_bins(batch, bins)
+    lv = _check_levels(batch, levels)
+    w = np.asarray(weights)
+    if w.shape != (batch.num_segments,) or (w.size and w.min() < 0) or not np.issubdtype(w.dtype, np.integer):
+        raise ValueError('weights must be non-negative integers, one per model segment')
+    cs, ce = chains_from_telomeres(is_telomere)
+    runs, piece_region, _ = region_queries(regions, seg_fwd_remap, seg_is_original, cs, ce)
+    R = len(np.asarray(regions).reshape(-1, 2))
+    pmf, = _piece_sums(batch, r0, nr, runs, piece_region, R, lv, [[w[a:b + 1] for a, b in runs]], bins)
+    return {'bins': bins, 'pmf': pmf, 'mean': (pmf * np.arange(bins)).sum(axis=-1), 'p_saturated': pmf[..., -1]}
+
+
+def batch_event_occupancy(batch, r0, nr, regions, seg_fwd_remap, seg_is_original, is_telomere, l1, event, weights='length', bins=None, unit=None):
+    """How much of a region is in an event: the posterior distribution of the weighted occupancy sum_n w_n level(c_n) over the
+    real segments of regions, for restarts r0 .. r0+nr-1 of a RemixtBatch from ONE device call that holds both the floor and
+    the ceil queries (rmx_region_sums).  regions: (first, last) experiment segment indices; l1: the model segments' lengths.
+    event: a mask name of MASK_NAMES or a boolean (classes, states) table (level_mask) -- level 1 where the event holds --, or a
+    (quantity, clone) feature as locus_joint takes it (the level is that copy number: 'the segments carry at least twelve
+    copies between them').  weights 'segments': every real segment weighs 1, and the result is EXACT.  weights 'length': a
+    real segment weighs its length in units of `unit` (None: per region, quantise_lengths' choice for `bins` and the
+    table's highest level); the result is exact where every length of the region is a multiple of the unit (`exact`), and
+    otherwise a RIGOROUS BRACKET: for every path unit * (floor sum) <= true weighted sum <= unit * (ceil sum), so pmf_floor
+    and pmf_ceil are the distributions of a lower and of an upper bound of the true sum, not approximations of its
+    distribution.  The bracket is as wide as the number of real segments whose length is no multiple of the unit: arm-sized
+    regions of thousands of unequal segments get a loose bracket.  Inserted zero-length segments weigh 0.  bins None: the
+    most the batch's state count allows (sums_max_bins).  A dict of
+      bins; unit (R,); length (R,), the summed length of the region's real segments (their number under 'segments'); exact (R,)
+      pmf_floor, pmf_ceil (nr, R, bins)   entry k: P(the integer sum is k), the last entry that of bins - 1 or more
+      mean_floor, mean_ceil (nr, R)       unit * the mean of the integer sums: a lower and an upper bound of the mean weighted
+                                          occupancy.  The floor sum capped at bins - 1 is still a lower bound; where the ceil
+                                          sum can pass the last bin and that bin has mass, its mean bounds nothing: mean_ceil
+                                          is inf there
+      p_saturated (nr, R)                 the last bin of pmf_ceil: the mass whose ceil sum is not resolved.
+    occupancy_at_least turns it into bounds of P(weighted fraction >= f)."""
+    if weights not in OCCUPANCY_WEIGHTS:
+        raise ValueError('weights must be one of %s' % ', '.join(OCCUPANCY_WEIGHTS))
+    bins = _sum_bins(batch, bins)
+    lv = _check_levels(batch, _sum_levels(batch.cn_classes, event))
+    vmax = int(lv.max()) if lv.size else 1
+    real = np.asarray(seg_is_original) != 0
+    seg_len = np.where(real, np.asarray(l1, dtype=float), 0.) if weights == 'length' else real.astype(float)
+    cs, ce = chains_from_telomeres(is_telomere)
+    runs, piece_region, _ = region_queries(regions, seg_fwd_remap, seg_is_original, cs, ce)
+    R = len(np.asarray(regions).reshape(-1, 2))
+    units, length, exact, capped = np.ones(R), np.zeros(R), np.ones(R, dtype=bool), np.zeros(R, dtype=bool)
+    wfloor, wceil = [None] * len(runs), [None] * len(runs)
+    for reg in range(R):
+        pieces = np.flatnonzero(np.asarray(piece_region) == reg)
+        ls = [seg_len[runs[j][0]:runs[j][1] + 1] for j in pieces]
+        whole = np.concatenate(ls) if ls else np.zeros(0)
+        length[reg] = whole.sum()
+        u, wf, wc, ex = quantise_lengths(whole, bins, vmax, 1. if weights == 'segments' else unit)
+        units[reg], exact[reg] = u, ex
+        capped[reg] = int(wc.sum()) * vmax > bins - 1          # the ceil sum can pass the last bin
+        at = 0
+        for j, x in zip(pieces, ls):
+            wfloor[j], wceil[j] = wf[at:at + len(x)], wc[at:at + len(x)]
+            at += len(x)
+    lo, hi = _piece_sums(batch, r0, nr, runs, piece_region, R, lv, [wfloor, wceil], bins)
+    k = np.arange(bins)
+    mean_ceil = np.where(capped[None, :] & (hi[..., -1] > 0), np.inf, (hi * k).sum(axis=-1) * units)
+    return {'bins': bins, 'unit': units, 'length': length, 'exact': exact, 'pmf_floor': lo, 'pmf_ceil': hi,
+            'mean_floor': (lo * k).sum(axis=-1) * units, 'mean_ceil': mean_ceil, 'p_saturated': hi[..., -1]}
+
+
+def occupancy_at_least(out, fraction):
+    """(lower, upper), each (..., R): bounds of P(the weighted occupancy is at least `fraction` of the region's length) from a
+    batch_event_occupancy dict (for a 0/1 event: 'at least half of the arm is in LOH').  With the threshold
+    t = ceil(fraction * length / unit) in integer units, lower = P(floor sum >= t) and upper = P(ceil sum >= t): the floor sum
+    is an integer below the true sum in units and the ceil sum one above it (a ratio within a few ulps of an integer counts as
+    that integer, as in quantise_lengths).  The two coincide where `exact`.  A threshold past
+    the last bin is not resolved: lower is 0 there and upper the last bin of pmf_ceil."""
+    bins = int(out['bins'])
+    with np.errstate(invalid='ignore'):
+        ratio = float(fraction) * np.asarray(out['length'], dtype=float) / np.asarray(out['unit'], dtype=float)
+    near = np.round(ratio)            # (quantise_lengths' rule: a ratio within a few ulps of an integer is that integer, not the next)
+    with np.errstate(invalid='ignore'):
+        t = np.where(np.abs(ratio - near) <= 8 * np.finfo(float).eps * np.maximum(near, 1.), near, np.ceil(ratio))
+    t = np.clip(np.where(np.isfinite(t), t, 0), 0, bins).astype(np.int64)
+    k = np.arange(bins)
+    tail = k[None, :] >= t[:, None]                                    # (R, bins)
+    lower = np.where(tail, np.asarray(out['pmf_floor']), 0.).sum(axis=-1)
+    upper = np.where(np.minimum(t, bins - 1)[:, None] <= k[None, :], np.asarray(out['pmf_ceil']), 0.).sum(axis=-1)
+    return np.clip(lower, 0., 1.), np.clip(upper, 0., 1.)

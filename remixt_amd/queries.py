@@ -335,9 +335,43 @@ def path_entropy(q, regions=None):
 ENTROPY_QUERIES = (path_entropy,)
 
 
+@_query('region_sums_raw', 'has no region sums', '`bins` and arrays (restarts, len(regions), ...)', shared=('bins', 'unit', 'length', 'exact'))
+def region_sums(q, regions, levels, weights, bins=None):
+    """The exact posterior distribution, under the structured posterior of the last variational update, of the additive
+    functional sum_n weights[n] levels(c_n) over regions ((first, last) experiment segment indices): levels an int
+    (classes, states) table with entries >= 0, weights non-negative integers PER MODEL SEGMENT (0: the segment does not count;
+    give the inserted zero-length segments 0), bins None: the most the state count allows (posteriors.sums_max_bins).  Exact
+    for these integer weights.  A dict of `bins`, `pmf` (len(regions), bins) -- entry k the probability that the sum is k,
+    the last entry that of bins - 1 or more --, `mean` and `p_saturated` (len(regions),).  Pieces of a region in several
+    chains add."""
+    return posteriors.batch_region_sums(*q.at, regions, *q.maps, levels=levels, weights=weights, bins=bins)
+
+
+@_query('region_sums_raw', 'has no region sums', '`bins`, `unit`, `length`, `exact` (len(regions),) and arrays (restarts, len(regions), ...)',
+        shared=('bins', 'unit', 'length', 'exact'))
+def event_occupancy(q, regions, event, weights='length', bins=None, unit=None):
+    """How much of a region is in an event -- 'at least half of 17p is in LOH', 'the gene's segments carry at least twelve
+    copies between them', 'how many of these segments are subclonal' -- as a distribution, not a mean and an SD: regions is a
+    list of (first, last) experiment segment indices; event a mask name of posteriors.MASK_NAMES, a boolean
+    (classes, states) table (posteriors.level_mask), or a (quantity, clone) feature as locus_joint takes it (the level is that
+    copy number).  weights 'segments': every real segment weighs 1 and the distribution is EXACT.  weights 'length': a real
+    segment weighs its length in units of `unit` (None: chosen per region so that nothing saturates); exact where every
+    length is a multiple of the unit (`exact`), otherwise a RIGOROUS BRACKET and no approximation: for every path
+    unit * (floor sum) <= true weighted sum <= unit * (ceil sum).  The bracket is as wide as the number of real segments whose
+    length is no multiple of the unit, so arm-sized regions of thousands of unequal segments get a loose bracket.  A dict of
+    `bins`, `unit`, `length`, `exact` (len(regions),), `pmf_floor` and `pmf_ceil` (len(regions), bins; the last entry means
+    bins - 1 units or more), `mean_floor`, `mean_ceil` and `p_saturated` (len(regions),); posteriors.occupancy_at_least gives
+    the bounds of P(weighted fraction >= f) (posteriors.batch_event_occupancy)."""
+    return posteriors.batch_event_occupancy(*q.at, regions, *q.maps, q.model.l1, event, weights=weights, bins=bins, unit=unit)
+
+
+# (the closed lists above stay what they are: `entry` looks a name up in every tuple, `answers` installs them all)
+SUM_QUERIES = (region_sums, event_occupancy)
+
+
 def entry(name):
     """The table's entry of a query by its name, whichever tuple holds it."""
-    for e in ALL_QUERIES + ENTROPY_QUERIES:
+    for e in ALL_QUERIES + ENTROPY_QUERIES + SUM_QUERIES:
         if e.name == name:
             return e
     raise KeyError(name)
@@ -464,7 +498,7 @@ def answers(level):
     body, doc = LEVELS[level]
 
     def install(cls):
-        for e in ALL_QUERIES + ENTROPY_QUERIES:
+        for e in ALL_QUERIES + ENTROPY_QUERIES + SUM_QUERIES:
             setattr(cls, e.name, _method(cls, e, body, doc(e)))
         return cls
     return install

@@ -4,8 +4,9 @@ region_moments_raw (nf 1 and 4), region_extent_raw, region_pattern_raw, region_d
 region_kbest_raw (1, 3 and 8 ranks; log-probabilities and states), region_extremes_raw (1, 5 and 16 columns) and region_conditional_raw (log-probabilities and slots; chain windows), each with
 and without a constrain vector that leaves segments unbound, locus_joint_raw (three table sizes and the profile form), and
 region_automaton_raw (three automata padded to 16 states, with and without the constrain vector, in the 165-state and the
-617-state scenario) and path_entropy_raw (both arrays over all segments, in the same two scenarios); a library without an entry
-point leaves its arrays out.
+617-state scenario), path_entropy_raw (both arrays over all segments, in the same two scenarios) and region_sums_raw (a mask and
+a copy-number table under three weightings, one saturating: 16 and 64 bins at 165 states, 16 bins in the 617-state scenario, the
+16-tile form); a library without an entry point leaves its arrays out.
 Scenarios: the three grids of tests/test_hip_sample_cn.py (60, 40 and 24 segments at 165, 355 and 457 states) and 16 segments at
 max_copy_number 16 (more than 512 states: the <16> instantiations), three chains, four restarts after two sweeps, restarts 1 and 2
 with their snapshot retaken under the other transition model (exp(trans_value) on plain adjacencies too).  Queries: a segment, a
@@ -149,6 +150,13 @@ def collect(rs, out, kbest=True):
             out[key('region_automaton_' + tag)] = b.region_automaton_raw(0, R, qa, sy, dl, np.zeros(len(aus), dtype=np.int32), con)
     if hasattr(b, 'path_entropy_raw') and (S == 165 or S > 512):      # (the 3-tile and the 16-tile form; restarts 1 and 2 on exp(Tval))
         out[key('path_entropy_marginal')], out[key('path_entropy_step')] = b.path_entropy_raw(0, R)
+    if hasattr(b, 'region_sums_raw') and (S == 165 or S > 512):      # (three row tiles at 16 and 64 bins; the 16-tile form at 16 bins)
+        lt = np.stack([masks[:, 1].astype(np.int16), posteriors._level_quantity(b.cn_classes, 'total').max(axis=-1).astype(np.int16)], axis=1)
+        pool = np.concatenate([bound.astype(np.int32), np.arange(N1, dtype=np.int32) % 4, [2 ** 31 - 1]])
+        # weights: seg_is_original with segments left out, 0 .. 3 by position, and the run's last segment on the saturating entry
+        qs = np.array([[a, z, li, off] for a, z in runs for li in (0, 1) for off in (a, N1 + a, 2 * N1 - (z - a))], dtype=np.int32)
+        for bins in sorted({16, posteriors.sums_max_bins(S)}):
+            out[key('region_sums%d' % bins)] = b.region_sums_raw(0, R, qs, lt, pool, bins)
     out[key('region_moments1')] = b.region_moments_raw(0, R, qm1, feats, weights, 1)
     out[key('region_moments4')] = b.region_moments_raw(0, R, qm4, feats, weights, 4)
     print('%d states, %d model segments, %d chains, %d plain and %d breakend adjacencies, %d runs, %d anchors, %d of %d segments unbound' % (
